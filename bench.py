@@ -2,14 +2,20 @@
 """Headline benchmark: images/sec of the SimpleBaseline-ResNet50 training step (256x256, bs=64 per
 GPU, bf16 activations/weights with fp32 accumulation) on the HIP engine -- BASELINE.json configs[1].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one full training iteration on a synthetic batch already resident in HBM: weight packs,
 forward, Gaussian target render from joints, MSE loss + gradient, arg-max decode, backward,
-[gradient all-reduce], fused Adam -- one hipGraph replay.  Rank 0 prints ONE JSON line with
-throughput, the roofline of the dominant kernel (per-launch HIP-event timing, measured live) and
-a CPU baseline (the oracle's plain-PyTorch restatement on the host cores, bounded sample).
+[gradient all-reduce], fused Adam -- one hipGraph replay.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (throughput, ms_per_step).
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32).
+--full also measures everything else, in the same process after the timed steps: the exposed cost
+of the gradient exchange (N > 1), EPE/AUC parity against golden G7, inference throughput, the
+roofline of the dominant kernel (per-launch HIP-event timing, measured live), the other
+configurations of BASELINE.json and a CPU baseline (the oracle's plain-PyTorch restatement on the
+host cores, bounded sample).
 """
 import argparse
 import json
@@ -89,6 +95,26 @@ def synthetic_batch(batch, size, device, seed=9001):
     images = torch.from_numpy(rng.randn(batch, 3, size, size).astype(np.float32)).to(device)
     joints = torch.from_numpy(rng.uniform(20, size - 20, size=(batch, 21, 2)).astype(np.float32)).to(device)
     return images, joints
+
+
+DUMP_SAMPLE = 1 << 22          # elements kept of a larger output (a fixed, seeded sample): 16 MB each, 64 MB at most in all
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <dirname>/<name>.npy in float32.  An
+    output of more than DUMP_SAMPLE elements is reduced to the same seeded sample of its flattened elements in every run (indices
+    depend on the size only), so that two builds can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_LIMIT_BYTES >> 20} MB")
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def profile_kernels(step, iters=3, plan=None, fwd_only=False):
@@ -345,7 +371,15 @@ def main():
     ap.add_argument("--train-only", action="store_true",
                     help="training replays only (no inference graph, no per-launch profile, no extra configurations): the process the "
                          "PMC passes of tools/refresh_profiles.sh count a training step's HBM bytes on")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the exposed cost of the gradient "
+                         "exchange (N > 1), EPE/AUC parity, inference throughput, the kernel roofline, the extra configurations and the "
+                         "CPU baseline (each still subject to the --no-* / --train-only switches above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, heat-maps, decoded keypoints, updated weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this parent (which has made no GPU call yet) starts the N ranks
@@ -381,6 +415,8 @@ def main():
             inf()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"heatmaps": inf.heatmaps, "preds": inf.preds, "maxvals": inf.maxvals})
         key = (f"hrnet{args.hrnet_width}" if args.hrnet_width else f"r{args.depth}", args.size)
         print(json.dumps({"metric": METRIC, "value": round(args.batch * args.steps / dt, 1), "unit": "images/s", "n_gpus": 1,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -425,11 +461,15 @@ def main():
     loss_val = float(step.loss)
     ms = elapsed / args.steps * 1e3
     value = world * args.batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what a caller of TrainStep holds after the last timed step: its loss, heat-maps and decode, and the updated weights
+        dump_outputs(args.dump_outputs, {"loss": step.loss, "heatmaps": step.plan.out_nchw, "preds": step.preds, "maxvals": step.maxvals,
+                                         "weights": model.arena().flat})
     # what the gradient exchange costs the step: the same ranks, the same step, with the collectives stubbed out
     # (GradSync.stub: stream hand-over, staging and the per-bucket Adam launches stay).  Default transport only -- the
     # single-graph transport (--comm lh) holds its collectives inside the captured graph.
     exposed = None
-    if world > 1 and sync is not None and args.comm == "torch":
+    if args.full and world > 1 and sync is not None and args.comm == "torch":
         def timed(k):
             barrier()
             t_ = time.perf_counter()
@@ -484,9 +524,9 @@ def main():
     out["step_roofline"] = step_roofline(wkey, True, value / world, es)
     out["c_abi_calls_per_step"] = sum(1 for c in step.plan.packs + step.plan.fwd + step.plan.bwd if hasattr(c, "fn")) + 4
 
-    if rank == 0 and not args.train_only:
+    if args.full and rank == 0 and not args.train_only:
         out["epe_auc_parity"] = epe_auc_parity()
-    if rank == 0 and world == 1 and not args.train_only:
+    if args.full and rank == 0 and world == 1 and not args.train_only:
         # eval-mode forward + decode throughput (the "infer" half of the metric)
         torch.cuda.synchronize()
         inf = InferStep(model, args.batch, args.size, args.size)

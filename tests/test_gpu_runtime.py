@@ -1065,14 +1065,14 @@ def test_bench_gpus_2_starts_two_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--depth", "18",
-                        "--batch", "4", "--size", "128", "--no-cpu-baseline", "--no-roofline", "--no-extra"],
+                        "--batch", "4", "--size", "128", "--full", "--no-cpu-baseline", "--no-roofline", "--no-extra"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["dist_backend"] == "gloo", out
     assert out["config"]["global_batch"] == 8 and out["value"] > 0
-    # the exposed cost of the gradient exchange (step with collectives - step with GradSync stubbed), printed for every N > 1
+    # the exposed cost of the gradient exchange (step with collectives - step with GradSync stubbed), printed for every N > 1 under --full
     ex = out["allreduce_exposed"]
     assert isinstance(out["allreduce_exposed_ms"], float) and ex["ms_per_step_with_collectives"] > 0 and ex["ms_per_step_collectives_stubbed"] > 0
     # a rank count the launcher did not create is refused

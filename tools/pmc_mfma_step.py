@@ -2,7 +2,7 @@
 """MFMA utilisation of EVERY kernel of the bench step, at the shapes the step runs, from one rocprofv3 PMC pass:
 
     rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d DIR -o m -- \
-        python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-extra
+        python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline --no-extra
     python tools/pmc_mfma_step.py DIR/.../m_counter_collection.csv out.txt
 
 Per kernel name (mean over its dispatches): duration under the counter run, MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES /
@@ -46,4 +46,4 @@ def main(path, out, title):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-extra")
+    main(sys.argv[1], sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline --no-extra")
