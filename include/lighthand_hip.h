@@ -507,6 +507,22 @@ int lh_adam_tick(const double* hyper, int* step, float* derived, void* stream);
 int lh_adam_apply(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long numel, const float* derived,
                   float grad_scale, void* stream);
 
+/* Dynamic loss scaling (torch.amp.GradScaler + optimizer.step()) decided on the device, so that it lives inside a captured
+ * step.  Per step, in this order on one stream:
+ *   lh_amp_check           partial[k] (device int32[lh_amp_check_blocks()]) = 1 where workgroup k saw an inf / NaN in the RAW
+ *                          gradient (before unscaling); every slot is rewritten at every call.  grad 16-byte aligned.
+ *   lh_amp_update          found_inf = OR of partial; inv = extra / scale (fp64, rounded to fp32); skipped += found_inf; then
+ *                          torch._amp_update_scale_ on scale (fp32) / growth_tracker (int32) with amp_hyper (device fp64[3]) =
+ *                          { growth_factor, backoff_factor, growth_interval }; only when found_inf == 0 the tick of
+ *                          lh_adam_tick (step += 1, derived).
+ *   lh_adam_apply_guarded  lh_adam_apply with grad_scale = *inv, returning before it touches memory when *found_inf. */
+int lh_amp_check_blocks(void);
+int lh_amp_check(const float* grad, long numel, int* partial, void* stream);
+int lh_amp_update(const int* partial, const double* amp_hyper, float* scale, int* growth_tracker, int* found_inf, int* skipped,
+                  float* inv, double extra, const double* hyper, int* step, float* derived, void* stream);
+int lh_adam_apply_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long numel, const float* derived,
+                          const int* found_inf, const float* inv, void* stream);
+
 /* Bias gradient of the head's 1x1 convolution (pose_resnet.py:169-175; loss.backward()): out[c] = sum over n, h, w of an
  * NCHW fp32 gradient.  fp64 partials in a fixed order (deterministic).  workspace >= lh_channel_sum_workspace_bytes(c). */
 size_t lh_channel_sum_workspace_bytes(int c);

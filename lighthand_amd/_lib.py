@@ -185,6 +185,10 @@ SIGNATURES = {
     "lh_adam_step": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _F, _P]),
     "lh_adam_tick": (_I, [_P, _P, _P, _P]),
     "lh_adam_apply": (_I, [_P, _P, _P, _P, _L, _P, _F, _P]),
+    "lh_amp_check_blocks": (_I, []),
+    "lh_amp_check": (_I, [_P, _L, _P, _P]),
+    "lh_amp_update": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "lh_adam_apply_guarded": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P]),
 }
 
 _lib = None

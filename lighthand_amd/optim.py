@@ -109,7 +109,12 @@ class Adam(torch.optim.Optimizer):
               "lh_adam_apply")
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0):
+    def step(self, closure=None, grad_scale=1.0, amp=None):
+        """grad_scale: the factor the gradients are multiplied by before the update (static loss scaling: extra / S).
+        amp (an ``amp.DynamicLossScale``): dynamic loss scaling on the device -- the gradients carry the scaler's current scale,
+        grad_scale is the extra factor (1 / world size), and the update is skipped when a gradient is inf / NaN.  Arena only."""
+        if amp is not None and not self.sliceable():
+            raise _lib.LightHandError("Adam.step(amp=...): dynamic loss scaling needs the parameter arena (bind_arena) and one param group")
         loss = closure() if closure is not None else None
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
@@ -123,6 +128,14 @@ class Adam(torch.optim.Optimizer):
                 if "exp_avg" not in s:
                     s["exp_avg"] = torch.zeros_like(arena.flat)
                     s["exp_avg_sq"] = torch.zeros_like(arena.flat)
+                if amp is not None:
+                    # the check reads the whole arena, alignment padding included (zero-initialised, never written)
+                    amp.check_and_update(arena.flat_grad.data_ptr(), arena.numel, grad_scale, st["hyper"].data_ptr(),
+                                         st["step"].data_ptr(), st["derived"].data_ptr(), stream)
+                    check(lib.lh_adam_apply_guarded(arena.flat.data_ptr(), arena.flat_grad.data_ptr(), s["exp_avg"].data_ptr(),
+                                                    s["exp_avg_sq"].data_ptr(), arena.numel, st["derived"].data_ptr(),
+                                                    amp.found_inf.data_ptr(), amp._inv.data_ptr(), stream), "lh_adam_apply_guarded")
+                    continue
                 check(lib.lh_adam_step(arena.flat.data_ptr(), arena.flat_grad.data_ptr(), s["exp_avg"].data_ptr(),
                                        s["exp_avg_sq"].data_ptr(), arena.numel, st["hyper"].data_ptr(), st["step"].data_ptr(),
                                        st["derived"].data_ptr(), float(grad_scale), stream), "lh_adam_step")

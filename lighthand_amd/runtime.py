@@ -14,6 +14,7 @@ import torch
 
 from . import _lib, heatmap
 from ._lib import LightHandError, check
+from .amp import DynamicLossScale
 from .optim import Adam
 
 
@@ -81,16 +82,34 @@ class TrainStep:
         # (lh_mse_heatmap), every gradient of the backward pass carries S, Adam divides it out again -- the loss value, the
         # moments and the update are those of the unscaled step, but heat-map gradients of 1e-7 no longer flush to zero in
         # the 16-bit backward pass.  bf16 / fp32 need none (fp32's exponent range).
-        if loss_scale is None:
-            loss_scale = 1024.0 if self.plan.tdtype == torch.float16 else 1.0
-        self.loss_scale = float(loss_scale)
-        self._loss_scale_dev = torch.tensor([self.loss_scale], dtype=torch.float32, device=dev) if self.loss_scale != 1.0 else None
-        self.grad_scale /= self.loss_scale
+        # loss_scale="dynamic" or an amp.DynamicLossScale: torch.amp.GradScaler's dynamic scaling, decided on the device inside the
+        # step (Adam.step(amp=...)): the update is skipped when a gradient is inf / NaN, the scale backs off / grows, and
+        # lh_mse_heatmap reads the new scale at the next replay.  Data parallel: the check reads the ALL-REDUCED gradients -- an
+        # inf / NaN of any rank survives the sum (and the bf16 bucket staging), so every rank takes the same decision and keeps the
+        # same scale without a collective of its own.  Pass one instance to several steps (e.g. a short last batch) to share it.
+        self.scaler = None
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError(f"loss_scale must be None, a number, 'dynamic' or a DynamicLossScale, not {loss_scale!r}")
+            loss_scale = DynamicLossScale(device=dev)
+        if isinstance(loss_scale, DynamicLossScale):
+            self.scaler = loss_scale
+            self.loss_scale = "dynamic"
+            self._loss_scale_dev = self.scaler.scale_tensor
+        else:
+            if loss_scale is None:
+                loss_scale = 1024.0 if self.plan.tdtype == torch.float16 else 1.0
+            self.loss_scale = float(loss_scale)
+            self._loss_scale_dev = torch.tensor([self.loss_scale], dtype=torch.float32, device=dev) if self.loss_scale != 1.0 else None
+            self.grad_scale /= self.loss_scale
         # LH_ADAM_SLICES=1: Adam slice by slice under the backward pass (Adam.apply_slice) -- the parameters of a gradient
         # bucket are updated as soon as the bucket is final (data parallel: right behind its all-reduce), on a side stream.
         # Bit-identical, and measured SLOWER on one GPU (9.73-9.80 vs 9.61-9.63 ms: a 1 GB stream through HBM and the
         # Infinity Cache under the backward kernels costs more than the 0.15 ms tail it removes), hence off by default.
         self.adam_slices = os.environ.get("LH_ADAM_SLICES", "0") == "1" and hasattr(self.optimizer, "sliceable") and self.optimizer.sliceable()
+        if self.adam_slices and self.scaler is not None:
+            raise LightHandError("LH_ADAM_SLICES=1 cannot be combined with dynamic loss scaling: a bucket updated under the backward "
+                                 "pass cannot be undone when a later bucket holds an inf / NaN")
         self._adam_stream = torch.cuda.Stream() if self.adam_slices and grad_sync is None else None
         self._adam_segs = None
         self.graphs = None
@@ -134,7 +153,7 @@ class TrainStep:
         self._fwd_loss(stream)
         if not self.adam_slices:
             self.plan.run_backward(stream)
-            self.optimizer.step(grad_scale=self.grad_scale)
+            self._adam_step()
             return
         # the backward list runs as ONE pass; where a slice of the arena has all its gradients, its update starts on the
         # side stream behind events of every stream used so far (nothing waits for it until the end of the step)
@@ -206,7 +225,7 @@ class TrainStep:
             return
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.optimizer.step(grad_scale=self.grad_scale)
+            self._adam_step()
         self.graphs.append((g, "adam"))
 
     def _update_after(self, bucket):
@@ -226,7 +245,13 @@ class TrainStep:
                 self.grad_sync.launch(self.arena.flat_grad, bucket, after=self._update_after(bucket))
         self.grad_sync.wait_all()
         if not self.adam_slices:
+            self._adam_step()
+
+    def _adam_step(self):
+        if self.scaler is None:
             self.optimizer.step(grad_scale=self.grad_scale)
+        else:
+            self.optimizer.step(grad_scale=self.grad_scale, amp=self.scaler)
 
     def _optimizer_snapshot(self):
         """Adam moments and device step counters as they are BEFORE the warm-up / capture iterations: a resumed run
@@ -234,11 +259,14 @@ class TrainStep:
         st = self.optimizer.state.get("flat")
         moments = {k: st[k].clone() for k in ("exp_avg", "exp_avg_sq")} if st and "exp_avg" in st else None
         steps = {gi: d["step"].clone() for gi, d in self.optimizer._dev.items()}
-        return moments, steps
+        return moments, steps, self.scaler._snapshot() if self.scaler is not None else None
 
     def _optimizer_restore(self, snap):
-        """Undo the warm-up iteration on the optimizer side (weights / BN buffers are restored by ``__call__``)."""
-        moments, steps = snap
+        """Undo the warm-up iteration on the optimizer side (weights / BN buffers are restored by ``__call__``), the dynamic loss
+        scale's included: capture must not consume a growth tick or a backoff."""
+        moments, steps, scaler = snap
+        if scaler is not None:
+            self.scaler._restore(scaler)
         st = self.optimizer.state.get("flat")
         if st and "exp_avg" in st:
             for k in ("exp_avg", "exp_avg_sq"):

@@ -14,7 +14,9 @@ synthetic samples; the reference's datasets are not redistributable), ``--no_gra
 ``--drop_last`` (skip the short last batch: the reference trains and validates on it, src/tools/train.py:27-38 builds both
 loaders with the default ``drop_last=False``), ``--lr_resume_fix`` (on resume, continue the cosine schedule where the saved run
 left it; the reference builds a FRESH ``CosineAnnealingLR`` behind ``optimizer.load_state_dict``, src/tools/train.py:50-58, and
-that is the default here too).
+that is the default here too), ``--loss_scale {auto,dynamic,<float>}`` (``auto``: the static default of ``TrainStep``, 1024 for
+fp16 and none otherwise; ``dynamic``: torch.amp.GradScaler-style dynamic scaling on the device -- the checkpoint then also holds
+``scaler_state_dict`` and a resume restores it, and the per-epoch line reports the scale and the skipped steps).
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -69,6 +71,8 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--transfer_from", default=None, type=str, help="checkpoint --transfer loads (default: the reference's path)")
     p.add_argument("--drop_last", action="store_true", help="skip the short last batch of the training epoch (reference: trained on)")
     p.add_argument("--lr_resume_fix", action="store_true", help="resume the cosine schedule at the saved epoch (reference: fresh schedule)")
+    p.add_argument("--loss_scale", default="auto", type=_loss_scale_arg,
+                   help="auto (static: 1024 for fp16, none otherwise), dynamic (GradScaler-style, on the device) or a static factor")
     args = p.parse_args(argv)
     args.phase = phase
     args.model = args.root.split("/")[0]                  # src/tools/dataset.py:59 overwrites it from the name
@@ -135,16 +139,40 @@ def _sample_kind(ds):
     return "f32", None
 
 
-def save_checkpoint(model, args, epoch, optimizer, best_loss, count, ment="good"):
-    """Same file name and dict keys as src/tools/dataset.py:340-367; only rank 0 writes."""
+def _loss_scale_arg(v):
+    if v in ("auto", "dynamic"):
+        return v
+    try:
+        return float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--loss_scale takes auto, dynamic or a number, not {v!r}")
+
+
+def save_checkpoint(model, args, epoch, optimizer, best_loss, count, ment="good", scaler=None):
+    """Same file name and dict keys as src/tools/dataset.py:340-367; only rank 0 writes.  With a dynamic loss scale (``scaler``,
+    --loss_scale dynamic) one more key, ``scaler_state_dict`` (torch.amp.GradScaler's format)."""
     d = os.path.join(args.output_dir, "checkpoint-{}".format(ment))
     if int(os.environ.get("RANK", "0")) != 0:
         return d
     os.makedirs(d, exist_ok=True)
-    torch.save({"epoch": epoch, "optimizer_state_dict": optimizer.state_dict(), "best_loss": best_loss, "count": count,
-                "model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}},
-               os.path.join(d, "state_dict.bin"))
+    sd = {"epoch": epoch, "optimizer_state_dict": optimizer.state_dict(), "best_loss": best_loss, "count": count,
+          "model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}}
+    if scaler is not None:
+        sd["scaler_state_dict"] = scaler.state_dict()
+    torch.save(sd, os.path.join(d, "state_dict.bin"))
     return d
+
+
+def load_scaler_state(scaler, args):
+    """--loss_scale dynamic on a resume (the checkpoint logic of load_model_state): the saved scale and growth tracker, when the
+    checkpoint holds them.  Returns True when a state was loaded."""
+    ckpt = os.path.join(args.output_dir, "checkpoint-good", "state_dict.bin")
+    if args.reset or not os.path.isfile(ckpt):
+        return False
+    state = torch.load(ckpt, map_location="cpu").get("scaler_state_dict")
+    if state:
+        scaler.load_state_dict(state)
+    return bool(state)
 
 
 def resume_checkpoint(model, path):
@@ -196,12 +224,13 @@ def make_scheduler(optimizer, args, epo, opt_state):
     return torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=args.epoch)
 
 
-def run_epochs(args, epo, train_loader, train_batch, validate_fn, save_fn, optimizer, scheduler, stopper, log=print, rank=0, world=1):
+def run_epochs(args, epo, train_loader, train_batch, validate_fn, save_fn, optimizer, scheduler, stopper, log=print, rank=0, world=1,
+               scaler=None):
     """The epoch loop of src/tools/train.py:60-117 with the device work behind three callables: train_batch(it, batch) runs one
     iteration (any batch size: the short last batch included) and returns a callable that reads the running loss (called once per
     logging interval: the only device->host read of the loop), validate_fn() -> (val_loss, pck, epe), save_fn(epoch, best, count).
     Same order as the reference: train, validate, best / count bookkeeping, checkpoint on improvement, break on count == --count,
-    THEN scheduler.step()."""
+    THEN scheduler.step().  ``scaler``: a dynamic loss scale, whose scale and skipped steps the per-epoch line reports."""
     for epoch in range(epo, args.epoch):
         t0, seen = time.time(), 0
         for it, batch in enumerate(train_loader):
@@ -212,7 +241,8 @@ def run_epochs(args, epo, train_loader, train_batch, validate_fn, save_fn, optim
                     f"{world * seen / (time.time() - t0 + 1e-9):.0f} img/s lr {optimizer.param_groups[0]['lr']:.2e}")
         val_loss, pck, epe = validate_fn()
         if rank == 0:
-            log(f"epoch {epoch} valid loss {val_loss:.6f} pck {pck:.2f}% epe {epe * 0.26:.2f} mm")     # method.py:131
+            amp = f" loss scale {scaler.scale:g} skipped {scaler.skipped_steps}" if scaler is not None else ""
+            log(f"epoch {epoch} valid loss {val_loss:.6f} pck {pck:.2f}% epe {epe * 0.26:.2f} mm{amp}")     # method.py:131
         improved, stop = stopper.update(val_loss)     # val_loss is rank-invariant (reduce_validation): collective decision
         if improved:
             save_fn(epoch, stopper.best_loss, stopper.count)
@@ -280,6 +310,7 @@ def main(args, train_set=None, val_set=None):
     """``train_set`` / ``val_set``: any Dataset of (image, joint_2d, ...) samples (module docstring); without them
     ``--synthetic N`` builds seeded synthetic ones.  Under torch.distributed every rank must be given ITS shard."""
     from lighthand_amd import parallel
+    from lighthand_amd.amp import DynamicLossScale
     from lighthand_amd.optim import Adam
     from lighthand_amd.runtime import InferStep, TrainStep
 
@@ -312,11 +343,16 @@ def main(args, train_set=None, val_set=None):
     model = build_model(args).cuda().set_precision(args.precision)
     best_loss, epo, count, opt_state = load_model_state(model, args)
     optimizer = Adam(model.parameters(), lr=args.lr)
+    # one dynamic loss scale for the full-size step and the short last batch's step
+    scaler = DynamicLossScale() if args.loss_scale == "dynamic" else None
+    if scaler is not None:
+        load_scaler_state(scaler, args)
+    loss_scale = scaler if scaler is not None else None if args.loss_scale == "auto" else args.loss_scale
     sync = parallel.GradSync(world) if world > 1 else None
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
-                     input_u8=raw_hw, color_jitter=jitter)
+                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale)
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order
     steps = {args.batch_size: step}
 
@@ -330,7 +366,7 @@ def main(args, train_set=None, val_set=None):
             os.environ["LH_AUTOTUNE"] = "0"
             try:
                 st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
-                                          input_u8=raw_hw, color_jitter=jitter)
+                                          input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale)
             finally:
                 if prev is None:
                     os.environ.pop("LH_AUTOTUNE", None)
@@ -354,8 +390,8 @@ def main(args, train_set=None, val_set=None):
     stopper = EarlyStop(best_loss, count, args.count)
     return run_epochs(args, epo, train_loader, train_batch,
                       lambda: validate(model, val_loader, args, val_step_for if val_kind == "u8" else None),
-                      lambda epoch, best, cnt: save_checkpoint(model, args, epoch, optimizer, best, cnt, "good"),
-                      optimizer, scheduler, stopper, rank=rank, world=world)
+                      lambda epoch, best, cnt: save_checkpoint(model, args, epoch, optimizer, best, cnt, "good", scaler=scaler),
+                      optimizer, scheduler, stopper, rank=rank, world=world, scaler=scaler)
 
 
 if __name__ == "__main__":
