@@ -64,6 +64,18 @@ size_t lh_image_jitter_workspace_bytes(int n);
 int lh_image_u8_jitter_to_nhwc4(const unsigned char* hwc, void* out, int n, int hs, int ws, int h, int w, int pad, int wp,
                                 const float* mean3, const float* std3, const float* factors_dev, const int* order_dev,
                                 void* workspace, int dtype, void* stream);
+/* uint8 HWC -> per-image affine warp (inv_dev fp32 [n][6], output pixel-index coordinates, black outside the frame)
+ * -> bilinear resize -> [ColorJitter when factors_dev != NULL] -> Normalize -> padded NHWC4 in the run dtype.
+ * Output pixel (ox, oy) samples the resized frame at u = (a ox + b oy + c, d ox + e oy + f), inv = [a b c d e f]: inside
+ * [-0.5, w-0.5] x [-0.5, h-0.5] with the resize rule above, outside as 0 (cv2.warpAffine's constant border); the
+ * identity reproduces lh_image_u8_to_nhwc4 / lh_image_u8_jitter_to_nhwc4 bit for bit.  The contrast op's grey mean is that
+ * of the warped image.  workspace: lh_image_jitter_workspace_bytes(n), unused (may be NULL) without jitter. */
+int lh_image_u8_warp_to_nhwc4(const unsigned char* hwc, void* out, int n, int hs, int ws, int h, int w, int pad, int wp,
+                              const float* mean3, const float* std3, const float* inv_dev,
+                              const float* factors_dev, const int* order_dev, void* workspace, int dtype, void* stream);
+/* points fp32 [b][j][pstride] -> out fp32 [b][j][ostride]: (x, y) through the forward matrix fwd_dev fp32 [b][6].  Points
+ * that leave the frame are kept; out may alias pts when the strides agree. */
+int lh_affine_points(const float* pts, int pstride, const float* fwd_dev, float* out, int ostride, int b, int j, void* stream);
 /* NHWC (run dtype) -> NCHW fp32 heatmaps (what model(images) returns, pose_resnet.py:246)
  * and the inverse for the incoming gradient. c_stride = channel stride of the NHWC side. */
 int lh_nhwc_to_nchw_f32(const void* nhwc, float* nchw, int n, int h, int w, int c, int c_stride,

@@ -267,6 +267,161 @@ extern "C" int lh_image_u8_jitter_to_nhwc4(const unsigned char* hwc, void* out, 
     return LH_OK;
 }
 
+// Per-image affine warp in front of the resize (lh_image_u8_warp_to_nhwc4): output pixel (ox, oy) of the h x w frame samples
+// the resized frame at u = inv[b] . (ox, oy, 1), both in output pixel-index coordinates (pixel centres on the integers).
+// Inside [-0.5, w-0.5] x [-0.5, h-0.5] the sample is the resize rule below at u; outside the pixel is black (0 before
+// ColorJitter and Normalize: cv2.warpAffine's constant border).  The matrix is applied before the resize arithmetic, so the
+// identity gives ux = 1*ox + 0*oy + 0 = ox exactly and the plain kernels' output bit for bit (-ffp-contract=off).
+__device__ __forceinline__ void u8_warp_bilinear(const U8Args& p, const float* inv, int b, int oy, int ox, float* c) {
+    const float* m = inv + b * 6;
+    const float ux = m[0] * ox + m[1] * oy + m[2], uy = m[3] * ox + m[4] * oy + m[5];
+    if (!(ux >= -0.5f && ux <= p.w - 0.5f && uy >= -0.5f && uy <= p.h - 0.5f)) {     // NaN lands here too
+        c[0] = c[1] = c[2] = 0.f;
+        return;
+    }
+    const float sy = (float)p.hs / p.h, sx = (float)p.ws / p.w;
+    float fy = (uy + 0.5f) * sy - 0.5f, fx = (ux + 0.5f) * sx - 0.5f;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    // u up to w-0.5 reaches ws-0.5 in the source: the upper clamp only keeps the gather in bounds (x1 == x0 there, so the
+    // weight does not matter and the value is the plain rule's)
+    const int y0 = min((int)fy, p.hs - 1), x0 = min((int)fx, p.ws - 1);
+    const int y1 = y0 + 1 < p.hs ? y0 + 1 : p.hs - 1, x1 = x0 + 1 < p.ws ? x0 + 1 : p.ws - 1;
+    const float wy = fy - y0, wx = fx - x0;
+    const unsigned char* base = p.src + (long)b * p.hs * p.ws * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a00 = base[((long)y0 * p.ws + x0) * 3 + ch], a01 = base[((long)y0 * p.ws + x1) * 3 + ch];
+        const float a10 = base[((long)y1 * p.ws + x0) * 3 + ch], a11 = base[((long)y1 * p.ws + x1) * 3 + ch];
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        c[ch] = (top + (bot - top) * wy) * (1.f / 255.f);
+    }
+}
+
+// ---- the same three kernels behind a per-image affine warp (lh_image_u8_warp_to_nhwc4).  Siblings rather than a runtime
+// switch in the kernels above: those compile to the ISA they had before the warp existed.
+template <typename T>
+__global__ void image_u8_warp_to_nhwc4_kernel(const U8Args p, const float* inv) {
+    const long total = (long)p.n * p.hp * p.wp;
+    T* dst = (T*)p.dst;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % p.wp);
+        const long t = i / p.wp;
+        const int y = (int)(t % p.hp), b = (int)(t / p.hp);
+        const int oy = y - p.pad, ox = x - p.pad;
+        float v[3] = {0.f, 0.f, 0.f};
+        if ((unsigned)oy < (unsigned)p.h && (unsigned)ox < (unsigned)p.w) {
+            float c[3];
+            u8_warp_bilinear(p, inv, b, oy, ox, c);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
+        }
+        T* o = dst + i * 4;
+        o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]); o[3] = from_f<T>(0.f);
+    }
+}
+
+// contrast's grey mean is taken over the WARPED image, black fill included (the reference warps offline, then jitters online)
+__global__ __launch_bounds__(256) void jitter_mean_warp_kernel(const U8Args p, const float* factors, const int* order, double* partial,
+                                                               const float* inv) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, strip = blockIdx.x;
+    const float* f = factors + b * 4;
+    const int* ord = order + b * 4;
+    int kc = 4;                                         // position of the contrast op (4 = absent)
+    for (int k = 3; k >= 0; --k)
+        if (ord[k] == 1) kc = k;
+    double acc = 0.0;
+    const int rows = (p.h + CJ_STRIPS - 1) / CJ_STRIPS;
+    const int y0 = strip * rows, y1 = min(p.h, y0 + rows);
+    if (kc < 4)
+        for (int i = threadIdx.x; i < (y1 - y0) * p.w; i += 256) {
+            float c[3];
+            u8_warp_bilinear(p, inv, b, y0 + i / p.w, i % p.w, c);
+            cj_apply(c, f, ord, 0, kc, 0.f);
+            acc += (double)cj_gray(c);
+        }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[b * CJ_STRIPS + strip] = red[0];
+}
+
+template <typename T>
+__global__ void image_u8_warp_jitter_to_nhwc4_kernel(const U8Args p, const float* factors, const int* order, const double* partial,
+                                                     const float* inv) {
+    const long total = (long)p.n * p.hp * p.wp;
+    T* dst = (T*)p.dst;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % p.wp);
+        const long t = i / p.wp;
+        const int y = (int)(t % p.hp), b = (int)(t / p.hp);
+        const int oy = y - p.pad, ox = x - p.pad;
+        float v[3] = {0.f, 0.f, 0.f};
+        if ((unsigned)oy < (unsigned)p.h && (unsigned)ox < (unsigned)p.w) {
+            double m = 0.0;
+            for (int k = 0; k < CJ_STRIPS; ++k) m += partial[b * CJ_STRIPS + k];
+            const float mean = (float)(m / ((double)p.h * p.w));
+            float c[3];
+            u8_warp_bilinear(p, inv, b, oy, ox, c);
+            cj_apply(c, factors + b * 4, order + b * 4, 0, 4, mean);         // black pixels are jittered too
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
+        }
+        T* o = dst + i * 4;
+        o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]); o[3] = from_f<T>(0.f);
+    }
+}
+
+extern "C" int lh_image_u8_warp_to_nhwc4(const unsigned char* hwc, void* out, int n, int hs, int ws, int h, int w, int pad, int wp,
+                                         const float* mean3, const float* std3, const float* inv_dev, const float* factors_dev,
+                                         const int* order_dev, void* workspace, int dtype, void* stream) {
+    LH_REQUIRE(hwc && out && mean3 && std3 && inv_dev && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad,
+               "lh_image_u8_warp_to_nhwc4: bad arguments");
+    LH_REQUIRE(!factors_dev || (order_dev && workspace), "lh_image_u8_warp_to_nhwc4: ColorJitter needs order_dev and workspace (null)");
+    U8Args a;
+    a.src = hwc; a.dst = out; a.n = n; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
+    const long total = (long)n * a.hp * wp;
+    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    if (!factors_dev) {
+        LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((image_u8_warp_to_nhwc4_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a,
+                                                       inv_dev));
+        LH_LAUNCH_CHECK("image_u8_warp_to_nhwc4 launch");
+        return LH_OK;
+    }
+    LH_REQUIRE(lh_dtype_size(dtype) > 0, "unsupported dtype %d", dtype);
+    hipLaunchKernelGGL(jitter_mean_warp_kernel, dim3(CJ_STRIPS, n), dim3(256), 0, (hipStream_t)stream, a, factors_dev, order_dev,
+                       (double*)workspace, inv_dev);
+    LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((image_u8_warp_jitter_to_nhwc4_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                                                   a, factors_dev, order_dev, (const double*)workspace, inv_dev));
+    LH_LAUNCH_CHECK("image_u8_warp_jitter_to_nhwc4 launch");
+    return LH_OK;
+}
+
+// keypoints through the forward matrix of the warp: p' = (a x + b y + c, d x + e y + f), joints that leave the frame are kept
+// (lh_gaussian_target renders them as the reference does: a zero map or a clipped patch)
+__global__ void affine_points_kernel(const float* pts, int pstride, const float* fwd, float* out, int ostride, int b, int j) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b * j) return;
+    const float* m = fwd + (i / j) * 6;
+    const float x = pts[(long)i * pstride], y = pts[(long)i * pstride + 1];
+    out[(long)i * ostride] = m[0] * x + m[1] * y + m[2];
+    out[(long)i * ostride + 1] = m[3] * x + m[4] * y + m[5];
+}
+
+extern "C" int lh_affine_points(const float* pts, int pstride, const float* fwd_dev, float* out, int ostride, int b, int j, void* stream) {
+    LH_REQUIRE(pts && fwd_dev && out && pstride >= 2 && ostride >= 2 && b > 0 && j > 0 && (long)b * j < (1L << 31),
+               "lh_affine_points: bad arguments");
+    hipLaunchKernelGGL(affine_points_kernel, dim3((b * j + 255) / 256), dim3(256), 0, (hipStream_t)stream, pts, pstride, fwd_dev, out, ostride,
+                       b, j);
+    LH_LAUNCH_CHECK("affine_points launch");
+    return LH_OK;
+}
+
 template <typename T>
 __global__ void nhwc_to_nchw_kernel(const T* src, float* dst, int n, int hw, int c, int cs, int vec) {
     const long total = (long)n * hw;

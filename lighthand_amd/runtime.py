@@ -36,6 +36,50 @@ def sample_color_jitter(n, brightness=0.5, contrast=0.5, saturation=0.5, hue=0.5
     return factors, order
 
 
+def sample_affine(n, rotation=0.0, scale=0.0, shift=0.0, prob=1.0, mask=None, generator=None, size=(256, 256)):
+    """Per-image random affine warp (host side, seeded like ``sample_color_jitter``): rotation ~ U[-rotation, rotation] degrees
+    about the frame centre ((w-1)/2, (h-1)/2) with cv2.getRotationMatrix2D's sign (the reference's offline augmentation,
+    src/tools/processing_aug.py), isotropic scale ~ U[1-scale, 1+scale], shift ~ U[-shift*w, shift*w] x U[-shift*h, shift*h].
+    Coordinates are output pixel indices of the h x w frame (``size``), the joints' convention.  A sample is drawn with
+    probability ``prob`` and only where ``mask`` (bool [n], optional) is set; the others -- and every sample when all three
+    factors are 0 -- get the exact identity.  The matrices are formed in float64 and rounded to fp32.
+    Returns (inv, fwd) CPU fp32 tensors [n][6] = [a b c d e f] for Plan.warp_inv / warp_fwd: ``fwd`` maps a joint into the
+    warped frame, ``inv`` maps an output pixel back to where it samples."""
+    h, w = size
+    u = torch.rand(n, 5, generator=generator, dtype=torch.float64)
+    theta = torch.deg2rad((2 * u[:, 0] - 1) * rotation)
+    s = 1 + (2 * u[:, 1] - 1) * scale
+    tx, ty = (2 * u[:, 2] - 1) * shift * w, (2 * u[:, 3] - 1) * shift * h
+    drawn = u[:, 4] < prob
+    if mask is not None:
+        drawn &= torch.as_tensor(mask, dtype=torch.bool).cpu()
+    if not (rotation or scale or shift):
+        drawn[:] = False
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    al, be = s * torch.cos(theta), s * torch.sin(theta)
+    # forward: p' = s R (p - c) + c + t, R = [[cos, sin], [-sin, cos]]
+    fwd = torch.stack([al, be, (1 - al) * cx - be * cy + tx, -be, al, be * cx + (1 - al) * cy + ty], 1)
+    # inverse: A^-1 = [[al, -be], [be, al]] / s^2, translation -A^-1 t
+    s2 = al * al + be * be
+    ia, ib, ic, idd = al / s2, -be / s2, be / s2, al / s2
+    inv = torch.stack([ia, ib, -(ia * fwd[:, 2] + ib * fwd[:, 5]), ic, idd, -(ic * fwd[:, 2] + idd * fwd[:, 5])], 1)
+    eye = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float64)
+    fwd[~drawn], inv[~drawn] = eye, eye
+    return (inv + 0.0).to(torch.float32), (fwd + 0.0).to(torch.float32)          # + 0.0: no signed zeros
+
+
+def _geometric_aug_spec(geometric_aug):
+    """TrainStep(geometric_aug=): (rotation, scale, shift) or a dict of rotation / scale / shift / prob / generator."""
+    keys = ("rotation", "scale", "shift", "prob", "generator")
+    spec = dict(geometric_aug) if isinstance(geometric_aug, dict) else dict(zip(keys[:3], geometric_aug))
+    unknown = set(spec) - set(keys)
+    if unknown:
+        raise LightHandError(f"geometric_aug: unknown keys {sorted(unknown)} (known: {', '.join(keys)})")
+    out = {"rotation": 0.0, "scale": 0.0, "shift": 0.0, "prob": 1.0, "generator": None}
+    out.update(spec)
+    return out
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -43,8 +87,16 @@ def _ptr(t):
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
-                 input_u8=None, color_jitter=None, loss_scale=None):
+                 input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None):
         self.lib = _lib.load()
+        # geometric_aug=(rotation, scale, shift) or a dict that may also carry prob / generator: a random affine warp of the
+        # uint8 input per image and step (sample_affine), the joints moved to match (joints_aug) before the target render
+        if geometric_aug is not None:
+            if not input_u8:
+                raise LightHandError("geometric_aug warps the uint8 input pipeline: it needs input_u8=(hs, ws)")
+            if not targets_from_joints:
+                raise LightHandError("geometric_aug needs targets_from_joints=True: the target is rendered from the warped joints")
+            geometric_aug = _geometric_aug_spec(geometric_aug)
         self.model = model
         self._model_generation = getattr(model, "_lh_generation", 0)
         model.train()
@@ -64,8 +116,12 @@ class TrainStep:
         # color_jitter=(brightness, contrast, saturation, hue): torchvision ColorJitter ranges (reference: 0.5 each,
         # src/tools/dataset.py:139-141) applied inside the fused input kernel; factors are drawn per batch on the host
         self.color_jitter = color_jitter
-        self.images_u8 = self.plan.use_uint8_input(*input_u8, jitter=color_jitter is not None) if input_u8 else None
+        self.geometric_aug = geometric_aug
+        self.images_u8 = self.plan.use_uint8_input(*input_u8, jitter=color_jitter is not None,
+                                                   warp=geometric_aug is not None) if input_u8 else None
         self.joints = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
+        # the joints through this step's forward matrices: what the model is asked to predict (self.joints keeps the caller's)
+        self.joints_aug = torch.zeros_like(self.joints) if geometric_aug is not None else None
         self.target = torch.zeros_like(out)
         self.targets_from_joints = targets_from_joints
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -121,7 +177,12 @@ class TrainStep:
     def _render_target(self, stream):
         out = self.plan.out_nchw
         b, j, hs = self.joints.shape[0], self.joints.shape[1], out.shape[2]
-        check(self.lib.lh_gaussian_target(self.joints.data_ptr(), 2, self._patch.data_ptr(), heatmap.RADIUS,
+        joints = self.joints
+        if self.joints_aug is not None:
+            check(self.lib.lh_affine_points(self.joints.data_ptr(), 2, self.plan.warp_fwd.data_ptr(), self.joints_aug.data_ptr(), 2, b, j,
+                                            stream), "lh_affine_points")
+            joints = self.joints_aug
+        check(self.lib.lh_gaussian_target(joints.data_ptr(), 2, self._patch.data_ptr(), heatmap.RADIUS,
                                           self.target.data_ptr(), b, j, hs, stream), "lh_gaussian_target")
 
     def _fwd_loss(self, stream):
@@ -300,6 +361,12 @@ class TrainStep:
             f, o = sample_color_jitter(self.joints.shape[0], *self.color_jitter, mask=aug)
             self.plan.jitter_factors.copy_(f, non_blocking=True)
             self.plan.jitter_order.copy_(o, non_blocking=True)
+        if self.geometric_aug is not None:
+            g = self.geometric_aug                 # read by the replay from the plan's buffers, never baked into the graph
+            inv, fwd = sample_affine(self.joints.shape[0], g["rotation"], g["scale"], g["shift"], prob=g["prob"],
+                                     generator=g["generator"], size=(self.plan.h, self.plan.w))
+            self.plan.warp_inv.copy_(inv, non_blocking=True)
+            self.plan.warp_fwd.copy_(fwd, non_blocking=True)
         if joints is not None:
             self.joints.copy_(joints[..., :2], non_blocking=True)
         if target is not None:

@@ -16,7 +16,13 @@ loaders with the default ``drop_last=False``), ``--lr_resume_fix`` (on resume, c
 left it; the reference builds a FRESH ``CosineAnnealingLR`` behind ``optimizer.load_state_dict``, src/tools/train.py:50-58, and
 that is the default here too), ``--loss_scale {auto,dynamic,<float>}`` (``auto``: the static default of ``TrainStep``, 1024 for
 fp16 and none otherwise; ``dynamic``: torch.amp.GradScaler-style dynamic scaling on the device -- the checkpoint then also holds
-``scaler_state_dict`` and a resume restores it, and the per-epoch line reports the scale and the skipped steps).
+``scaler_state_dict`` and a resume restores it, and the per-epoch line reports the scale and the skipped steps),
+``--rot_factor DEG`` / ``--scale_factor F`` / ``--shift_factor F`` (online geometric augmentation of raw uint8 frames: per sample
+and step a rotation ~ U[-DEG, DEG] degrees about the frame centre, a scale ~ U[1-F, 1+F] and a shift ~ U[-F, F] x the size,
+warped on the device in the fused input kernel with a black border, the joints moved to match before the target is rendered;
+the reference bakes one fixed +-20 degree rotation into a second copy of its dataset offline, src/tools/processing_aug.py.  All
+default to 0 = off, the same step as without them; with float-tensor datasets a factor is an error.  The reference's boolean
+``--rot`` is read nowhere there and stays a no-op here).
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -73,6 +79,9 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--lr_resume_fix", action="store_true", help="resume the cosine schedule at the saved epoch (reference: fresh schedule)")
     p.add_argument("--loss_scale", default="auto", type=_loss_scale_arg,
                    help="auto (static: 1024 for fp16, none otherwise), dynamic (GradScaler-style, on the device) or a static factor")
+    p.add_argument("--rot_factor", default=0.0, type=float, help="online rotation of raw uint8 frames: U[-DEG, DEG] degrees (0 = off)")
+    p.add_argument("--scale_factor", default=0.0, type=float, help="online scale of raw uint8 frames: U[1-F, 1+F] (0 = off)")
+    p.add_argument("--shift_factor", default=0.0, type=float, help="online shift of raw uint8 frames: U[-F, F] x the size (0 = off)")
     args = p.parse_args(argv)
     args.phase = phase
     args.model = args.root.split("/")[0]                  # src/tools/dataset.py:59 overwrites it from the name
@@ -137,6 +146,19 @@ def _sample_kind(ds):
     if img.dim() != 3 or img.shape[0] != 3:
         raise SystemExit(f"normalised images must be float [3, S, S], got {tuple(img.shape)}")
     return "f32", None
+
+
+def geometric_aug(args, kind):
+    """(rotation, scale, shift) for TrainStep(geometric_aug=) from --rot_factor / --scale_factor / --shift_factor, None when all are 0
+    (--rot is not read: the reference declares it and never uses it).  The warp runs in the uint8 input kernel: with a float-tensor
+    dataset ('f32') a factor is an error."""
+    factors = (args.rot_factor, args.scale_factor, args.shift_factor)
+    if not any(factors):
+        return None
+    if kind != "u8":
+        raise SystemExit("--rot_factor / --scale_factor / --shift_factor warp raw uint8 frames on the device; this dataset yields "
+                         "normalised float tensors -- pass uint8 [H, W, 3] frames or drop the factors")
+    return factors
 
 
 def _loss_scale_arg(v):
@@ -314,6 +336,8 @@ def main(args, train_set=None, val_set=None):
     from lighthand_amd.optim import Adam
     from lighthand_amd.runtime import InferStep, TrainStep
 
+    # a geometric factor with float samples is refused before any device work (synthetic samples are float tensors)
+    geo = geometric_aug(args, _sample_kind(train_set)[0] if train_set is not None else "f32")
     seed = 9001                                           # src/tools/train.py:15-22
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -352,7 +376,7 @@ def main(args, train_set=None, val_set=None):
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
-                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale)
+                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo)
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order
     steps = {args.batch_size: step}
 
@@ -366,7 +390,7 @@ def main(args, train_set=None, val_set=None):
             os.environ["LH_AUTOTUNE"] = "0"
             try:
                 st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
-                                          input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale)
+                                          input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo)
             finally:
                 if prev is None:
                     os.environ.pop("LH_AUTOTUNE", None)
