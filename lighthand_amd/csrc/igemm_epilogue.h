@@ -36,16 +36,10 @@ __device__ __forceinline__ void igemm_epilogue_consts(const IgemmArgs& p, float*
     }
 }
 
-// LDS bytes the K-split wave pairs (KZ = 2, igemm_ring_kernel.h) need BEHIND the tile and its constants: one fp32 partial tile per pair
-template <int BM, int BP, int WC, int WP> constexpr int lh_epi_ksplit_bytes() { return (BM / WC) * (BP / WP) * 4 * WC * WP; }
-
-// KZ = 2: the workgroup holds WC x WP PAIRS of waves; both waves of a pair accumulated the same (BM / WC) x (BP / WP) sub-tile over
-// alternate K slices.  Wave kz = 1 of a pair hands its partial sums to wave kz = 0 through LDS (fp32, one addition per element: the
-// sum order differs from the KZ = 1 kernels' by exactly that), wave 0 writes the tile, all 64 * WC * WP * KZ threads store its rows.
-template <typename T, int BM, int BP, int WC, int WP, int KZ = 1>
+template <typename T, int BM, int BP, int WC, int WP>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char* smem, f32x4 (&acc)[BM / WC / 16][BP / WP / 16],
                                                int pblk, int cblk, int tid, int lane, int wc, int wp, int hw,
-                                               int ooh, int oow, float* stats, int kz = 0) {
+                                               int ooh, int oow, float* stats) {
     constexpr int ES = sizeof(T);
     constexpr int EPC = 16 / ES;
     constexpr int TC = BM / WC, TP = BP / WP;
@@ -64,57 +58,39 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char
     __syncthreads();
     float* cst = reinterpret_cast<float*>(smem + BP * RS);
     const bool affine = p.bias || p.scale;              // wave-uniform: training-mode forward / gradient launches carry neither
-    if constexpr (KZ == 2) {
-        f32x4* part = reinterpret_cast<f32x4*>(smem + BP * RS + 3 * BM * 4) + (wc * WP + wp) * (CT * PT * 64) + lane;
-        if (kz == 1) {
-#pragma unroll
-            for (int i = 0; i < CT; ++i)
-#pragma unroll
-                for (int j = 0; j < PT; ++j) part[(i * PT + j) * 64] = acc[i][j];
-        }
-        if (affine) igemm_epilogue_consts<BM, 64 * WC * WP * KZ>(p, cst, cblk * BM, tid);
-        __syncthreads();
-        if (kz == 0) {
-#pragma unroll
-            for (int i = 0; i < CT; ++i)
-#pragma unroll
-                for (int j = 0; j < PT; ++j) acc[i][j] += part[(i * PT + j) * 64];
-        }
-    } else if (affine) {
+    if (affine) {
         igemm_epilogue_consts<BM, 64 * WC * WP>(p, cst, cblk * BM, tid);
         __syncthreads();
     }
-    if (KZ == 1 || kz == 0) {
-        const int q = lane >> 4, pl = lane & 15;
+    const int q = lane >> 4, pl = lane & 15;
 #pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            const int col = wc * TC + i * 16 + q * 4;
-            float4 s4 = float4{1.f, 1.f, 1.f, 1.f}, b4 = float4{0.f, 0.f, 0.f, 0.f};
-            if (affine) {
-                s4 = *reinterpret_cast<const float4*>(cst + col);
-                b4 = *reinterpret_cast<const float4*>(cst + BM + col);
-            }
-            const float sv[4] = {s4.x, s4.y, s4.z, s4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+    for (int i = 0; i < CT; ++i) {
+        const int col = wc * TC + i * 16 + q * 4;
+        float4 s4 = float4{1.f, 1.f, 1.f, 1.f}, b4 = float4{0.f, 0.f, 0.f, 0.f};
+        if (affine) {
+            s4 = *reinterpret_cast<const float4*>(cst + col);
+            b4 = *reinterpret_cast<const float4*>(cst + BM + col);
+        }
+        const float sv[4] = {s4.x, s4.y, s4.z, s4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-            for (int j = 0; j < PT; ++j) {
-                const int pr = wp * TP + j * 16 + pl;
-                T* dst = reinterpret_cast<T*>(smem + pr * RS + col * ES);
-                if constexpr (ES == 4) {
-                    reinterpret_cast<float2*>(dst)[0] = float2{acc[i][j][0] * sv[0] + bv[0], acc[i][j][1] * sv[1] + bv[1]};
-                    reinterpret_cast<float2*>(dst)[1] = float2{acc[i][j][2] * sv[2] + bv[2], acc[i][j][3] * sv[3] + bv[3]};
-                } else {
-                    union { uint2 u; T e[4]; } pk;
+        for (int j = 0; j < PT; ++j) {
+            const int pr = wp * TP + j * 16 + pl;
+            T* dst = reinterpret_cast<T*>(smem + pr * RS + col * ES);
+            if constexpr (ES == 4) {
+                reinterpret_cast<float2*>(dst)[0] = float2{acc[i][j][0] * sv[0] + bv[0], acc[i][j][1] * sv[1] + bv[1]};
+                reinterpret_cast<float2*>(dst)[1] = float2{acc[i][j][2] * sv[2] + bv[2], acc[i][j][3] * sv[3] + bv[3]};
+            } else {
+                union { uint2 u; T e[4]; } pk;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pk.e[r] = from_f<T>(acc[i][j][r] * sv[r] + bv[r]);
-                    *reinterpret_cast<uint2*>(dst) = pk.u;
-                }
+                for (int r = 0; r < 4; ++r) pk.e[r] = from_f<T>(acc[i][j][r] * sv[r] + bv[r]);
+                *reinterpret_cast<uint2*>(dst) = pk.u;
             }
         }
     }
     __syncthreads();
 
     constexpr int CH = BM * ES / 16;
-    constexpr int NT = 64 * WC * WP * KZ;             // threads of the workgroup
+    constexpr int NT = 64 * WC * WP;                  // threads of the workgroup
     constexpr int RPP = NT / CH;
     const int chunk = tid % CH, r0 = tid / CH;
     const int col0 = cblk * BM + chunk * EPC;

@@ -18,8 +18,6 @@ int lh_ring_launch_f16_mid(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_f16_small(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_bf16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_f16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
-int lh_ring_launch_bf16_ksplit(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
-int lh_ring_launch_f16_ksplit(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_f32(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_multi_launch_bf16(const LhMulti<IgemmArgs>& m, const RingCfg& c, hipStream_t s);
 int lh_ring_multi_launch_f16(const LhMulti<IgemmArgs>& m, const RingCfg& c, hipStream_t s);
@@ -36,9 +34,6 @@ static const RingCfg kCfg16[] = {
 #undef X
 #define X(BM, BP, WC, WP, D, KB) {BM, BP, D + LH_DENSE_DEPTH, KB},
     LH_RING_CFGS_DENSE(X)
-#undef X
-#define X(BM, BP, WC, WP, D, KB) {BM, BP, D + LH_KSPLIT_DEPTH, KB},
-    LH_RING_CFGS_KSPLIT(X)
 #undef X
 };
 static const RingCfg kCfg32[] = {
@@ -59,10 +54,9 @@ static void cfg_table(int dtype, const RingCfg** t, int* n) {
     else { *t = kCfg16; *n = (int)(sizeof(kCfg16) / sizeof(RingCfg)); }
 }
 
-// ring depth of a tiled configuration (the dense-wave forms carry it as depth + LH_DENSE_DEPTH, the K-split forms as depth + LH_KSPLIT_DEPTH)
+// ring depth of a tiled configuration (the dense-wave forms carry it as depth + LH_DENSE_DEPTH)
 static inline int ring_depth(const RingCfg& c) { return c.depth >= 100 ? c.depth : c.depth % 10 == 0 ? 10 : c.depth % 10; }
 static inline bool ring_dense(const RingCfg& c) { return c.depth >= LH_DENSE_DEPTH && c.depth < LH_DENSE_DEPTH + 10; }
-static inline bool ring_ksplit(const RingCfg& c) { return c.depth >= LH_KSPLIT_DEPTH && c.depth < LH_KSPLIT_DEPTH + 10; }
 
 static bool cfg_exists(int dtype, const RingCfg& c) {
     const RingCfg* t; int n;
@@ -123,14 +117,6 @@ static bool cfg_fits(const lh_igemm_desc* d, int dtype, const RingCfg& c) {
     if (ring_dense(c)) {
         const char* sw = getenv("LH_DENSE_TILES");
         if (sw && atoi(sw) == 0) return false;
-    }
-    // the K-split wave-pair forms: measured EQUAL to the dense-wave forms on every layer of the benchmark networks (round 6: stage-3 3x3 30.6-30.9
-    // vs 30.4-30.5 us, stage-4 3x3 48.8 vs 48.7, the step 8.94 vs 8.95 ms with fresh measurements) -- a third fewer LDS fragment reads buy
-    // nothing because the LDS is not what binds this loop (profiles/r06_ksplit_ablation.txt).  They change the accumulation order, so they are
-    // offered to the tuner only with LH_KSPLIT_TILES=1 (every default configuration then stays bit-equal to the others); an explicit cfg runs them.
-    if (ring_ksplit(c)) {
-        const char* sw = getenv("LH_KSPLIT_TILES");
-        if (!(sw && atoi(sw) != 0) || stages < 2) return false;
     }
     return true;
 }
@@ -381,14 +367,12 @@ int lh_igemm_ring_launch(const IgemmArgs& a0, const RingCfg& c, int dtype, hipSt
             if (rc == 1) rc = lh_ring_launch_bf16_mid(a, c, s);
             if (rc == 1) rc = lh_ring_launch_bf16_small(a, c, s);
             if (rc == 1) rc = lh_ring_launch_bf16_dense(a, c, s);
-            if (rc == 1) rc = lh_ring_launch_bf16_ksplit(a, c, s);
             break;
         case LH_F16:
             rc = lh_ring_launch_f16_big(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_mid(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_small(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_dense(a, c, s);
-            if (rc == 1) rc = lh_ring_launch_f16_ksplit(a, c, s);
             break;
         case LH_F32:
             rc = lh_ring_launch_f32(a, c, s);

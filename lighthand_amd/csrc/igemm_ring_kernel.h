@@ -63,12 +63,6 @@ template <> struct MmaR<float> {
 // Debug-only ablation builds (tools/ablate.sh): -DLH_ABL=<bits>  1 = drop the MFMAs, 2 = drop the fragment reads,
 // 4 = drop the LDS-DMA loads, 8 = drop the epilogue (the K loop is pruned with it), 16 = keep the epilogue but drop its
 // global stores, 32 = drop the epilogue but keep every accumulator live.  Results are garbage; only the timing is of interest.  Never set in the product build.
-#ifndef LH_PREREAD
-#define LH_PREREAD 0   // debug builds only: both K slices' fragment reads of a 128-byte stage issued up front (measured neutral)
-#endif
-#ifndef LH_PRIO
-#define LH_PRIO 0      // debug builds only (s_setprio around the MFMA block of a K slice; measured)
-#endif
 #ifndef LH_ABL
 #define LH_ABL 0
 #endif
@@ -97,13 +91,7 @@ template <int L, int MAXS> __device__ __forceinline__ void wait_stages(int stage
 
 // The kernel proper, for workgroup `bid` of `nblk` of ONE problem: the plain kernel passes its block index, the
 // multi-problem kernel (multi.h) the index inside the problem the workgroup belongs to.
-// KZ = 2, the K-SPLIT WAVE PAIR (round 6): WC x WP pairs of waves, each pair owning a (BM / WC) x (BP / WP) sub-tile -- 64 x 64 on the
-// 128 x 128 tile where the 8-wave form gives a wave 64 x 32 -- and the two waves of a pair taking ALTERNATE K slices of every 128-byte
-// stage.  Per stage a wave issues PT + CT = 8 fragment reads for 16 MFMAs instead of 2 x 6 reads for 2 x 8: two thirds of the LDS
-// fragment bytes per MFMA at the same occupancy (two waves per SIMD, one workgroup per CU for a 256-tile launch).  The partial sums of
-// a pair meet in the epilogue (one fp32 addition per element through LDS), so the accumulation ORDER differs from the KZ = 1 kernels:
-// results agree with them to fp32 rounding, not bit for bit.  RingCfg depth = depth + LH_KSPLIT_DEPTH.
-template <typename T, int BM, int BP, int WC, int WP, int D, int KB, int KZ = 1>
+template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
 __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned char* smem, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)      // the buffer builtins exist in the device pass only
     constexpr int ES = sizeof(T);
@@ -116,8 +104,7 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
     constexpr int SL = KB / 16;                       // 16-byte slots per row
     constexpr int RPI = 64 / SL;                      // rows one LDS-DMA instruction covers
     constexpr int GB = 16 * KB;                       // bytes of one 16-row group
-    constexpr int NWAVE = WC * WP * KZ;               // 4 waves, or 8 (the 256 x 256 tile, the dense-wave forms, the K-split pairs)
-    static_assert(KZ == 1 || (KZ == 2 && KB == 128 && sizeof(T) == 2), "K-split pairs: two K slices per stage, 16-bit types");
+    constexpr int NWAVE = WC * WP;                    // 4 waves, or 8 (the 256 x 256 tile, the dense-wave forms)
     constexpr int NW = BM / 16 * H / NWAVE, NX = BP / 16 * H / NWAVE;   // instructions per wave and stage
     constexpr int L = NW + NX;
     constexpr int KSUB = KB / 64;                     // logical steps (MFMA K slices) per stage
@@ -126,9 +113,7 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kz = KZ == 2 ? wave / (WC * WP) : 0;   // K-split pairs: which K slice of every stage this wave multiplies
-    const int wq = KZ == 2 ? wave % (WC * WP) : wave;
-    const int wc = wq / WP, wp = wq % WP;
+    const int wc = wave / WP, wp = wave % WP;
     // 1-D grid; work item w = (pixel tile, channel tile) with the channel tile fastest: the channel tiles of one pixel
     // tile and neighbouring pixel tiles (3x3 halos) run on one XCD at about the same time and share its L2.
     const int CB = (p.cout + BM - 1) / BM;
@@ -274,7 +259,6 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
     auto step_at = [&](const unsigned ca, const unsigned cb) {
         uint4 F[NR];
         static_for<0, NR>([&](auto r) { rd(r, F[decltype(r)::value], ca, cb); });
-        if (LH_PRIO) __builtin_amdgcn_s_setprio(LH_PRIO);      // experiment: the wave in its MFMA phase issues ahead of its SIMD partner
         static_for<0, CT>([&](auto Ic) {
             constexpr int i = decltype(Ic)::value;
             // the reads younger than weight fragment i may stay in flight (LDS returns in order); the scheduling barrier in
@@ -286,17 +270,10 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
             for (int j = 0; j < PT; ++j)
                 if (!(LH_ABL & 1)) MmaR<T>::run(F[PT + i], F[j], acc[i][j]);
         });
-        if (LH_PRIO) __builtin_amdgcn_s_setprio(0);
     };
     // K slice kk of the stage at byte offset `so`
     auto step = [&](auto KKc, unsigned so) { step_at(offA[decltype(KKc)::value] + so, offB[decltype(KKc)::value] + so); };
 
-    auto mfma_group = [&](auto Ic, uint4 (&F)[NR]) {
-        constexpr int i = decltype(Ic)::value;
-#pragma unroll
-        for (int j = 0; j < PT; ++j)
-            if (!(LH_ABL & 1)) MmaR<T>::run(F[PT + i], F[j], acc[i][j]);
-    };
     // waves 4-7 of the 8-wave tile share their SIMDs with waves 0-3: they refill the ring half a stage later
     const bool late = NWAVE == 8 && KSUB == 2 && wave >= NWAVE / 2;
     int cslot = 0;                                   // ring slot of the stage being consumed
@@ -308,32 +285,6 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
         if (++cslot == D) cslot = 0;
         // the refill goes into the slot of stage s - 1, whose reads every wave retired before the barrier
         if (!late && issued < S) issue();
-        if constexpr (KZ == 2) {                     // this wave's K slice of the stage only (its pair partner takes the other)
-            step_at(offA[KSUB - 1 < kz ? KSUB - 1 : kz] + so, offB[KSUB - 1 < kz ? KSUB - 1 : kz] + so);
-            if (late && issued < S) issue();
-            continue;
-        }
-        if constexpr (LH_PREREAD && KSUB == 2 && NR <= 8) {
-            // experiment: the fragment reads of BOTH K slices of the stage up front (a second fragment register set), the
-            // second slice's read latency under the first slice's MFMAs
-            uint4 F0[NR], F1[NR];
-            static_for<0, NR>([&](auto r) { rd(r, F0[decltype(r)::value], offA[0] + so, offB[0] + so); });
-            static_for<0, NR>([&](auto r) { rd(r, F1[decltype(r)::value], offA[1] + so, offB[1] + so); });
-            static_for<0, CT>([&](auto Ic) {
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NR + CT - 1 - decltype(Ic)::value) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_group(Ic, F0);
-            });
-            if (late && issued < S) issue();
-            static_for<0, CT>([&](auto Ic) {
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(CT - 1 - decltype(Ic)::value) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_group(Ic, F1);
-            });
-            continue;
-        }
         step(ic<0>{}, so);
         if constexpr (KSUB == 2) {
             if (late && issued < S) issue();
@@ -346,7 +297,7 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
             return;
         }
     }
-    igemm_epilogue<T, BM, BP, WC, WP, KZ>(p, smem, acc, pblk, cblk, tid, lane, wc, wp, hw, ooh, oow, stats, kz);
+    igemm_epilogue<T, BM, BP, WC, WP>(p, smem, acc, pblk, cblk, tid, lane, wc, wp, hw, ooh, oow, stats);
 #endif
 }
 
@@ -357,12 +308,6 @@ template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
 __global__ __launch_bounds__(64 * WC * WP, (ring_waves_per_simd<BM, BP, WC, WP>())) void igemm_ring_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     igemm_ring_body<T, BM, BP, WC, WP, D, KB>(p, smem, blockIdx.x, gridDim.x);
-}
-// the K-split wave-pair form (KZ = 2 above): 2 x WC x WP waves
-template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
-__global__ __launch_bounds__(128 * WC * WP, 1) void igemm_ring_ksplit_kernel(const IgemmArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    igemm_ring_body<T, BM, BP, WC, WP, D, KB, 2>(p, smem, blockIdx.x, gridDim.x);
 }
 
 // Up to LH_MULTI_MAX independent convolutions that share the kernel configuration as ONE grid (lh_igemm_multi).
@@ -397,30 +342,6 @@ static int launch_ring(const IgemmArgs& a, hipStream_t s) {
     return LH_OK;
 }
 
-
-template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
-static int launch_ring_ksplit(const IgemmArgs& a, hipStream_t s) {
-    constexpr int ring = D * (BM + BP) * KB;
-    constexpr int epi = lh_epi_lds_bytes<T, BM, BP, false>() + lh_epi_ksplit_bytes<BM, BP, WC, WP>();
-    constexpr int lds = ring > epi ? ring : epi;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    if (a.head_w) {
-        lh_set_error("igemm_ring: the K-split form carries no fused head");
-        return LH_ERR_UNSUPPORTED;
-    }
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_ring_ksplit_kernel<T, BM, BP, WC, WP, D, KB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            lh_set_error("igemm_ring (K-split): cannot raise dynamic LDS to %d bytes: %s", lds, hipGetErrorString(e));
-            return LH_ERR_HIP;
-        }
-    }
-    dim3 grid(ceil_div(a.M, BP) * ceil_div(a.cout, BM) * (a.nphase > 1 ? a.nphase : 1));
-    hipLaunchKernelGGL((igemm_ring_ksplit_kernel<T, BM, BP, WC, WP, D, KB>), grid, dim3(128 * WC * WP), lds, s, a);
-    LH_LAUNCH_CHECK("igemm_ring (K-split) launch");
-    return LH_OK;
-}
 
 template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
 static int launch_ring_multi(const LhMulti<IgemmArgs>& m, hipStream_t s) {

@@ -350,8 +350,6 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             if depth == 100:
                 return f"conv3x3_direct_kernel<{t}, {kb}, {'true' if stats else 'false'}>"
             wc, wp = {(256, 256): (2, 4), (128, 256): (2, 2), (256, 128): (4, 2), (128, 128): (2, 2), (128, 64): (4, 1), (64, 128): (1, 4), (64, 64): (2, 2)}[(bm, bp)]
-            if 30 <= depth < 40:                # the K-split wave-pair forms (igemm_ring_cfgs.h)
-                return f"igemm_ring_ksplit_kernel<{t}, {bm}, {bp}, {wc}, {wp}, {depth - 30}, {kb}>"
             if 20 <= depth < 30:                # the dense-wave forms (eight waves on the 4-wave tiles, igemm_ring_cfgs.h)
                 wc, wp = {(128, 128): (2, 4), (128, 64): (4, 2), (64, 128): (2, 4), (64, 64): (2, 4), (128, 256): (2, 4), (256, 128): (4, 2)}[(bm, bp)]
                 depth -= 20
@@ -591,31 +589,26 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         workgroup of such a convolution walks the same weight slab stage by stage, at once: each stage waits for lines no XCD has
         seen yet (profiles/r05_ingest_ladder.txt, sitting 6: the complete K loop of the stage-3 3x3 takes 21.3 us, 19.1 us with the
         pack in L2).  Only where the pack fits beside the pass's own stream in the 4 MB L2 of an XCD (LH_L2_TOUCH_MAX_MB, default 3;
-        LH_L2_TOUCH=0: off).  Members of HRNet's batch groups only with LH_L2_TOUCH_GROUPS=1 (measured slightly slower)."""
+        LH_L2_TOUCH=0: off).  Not for members of HRNet's batch groups (measured slightly slower)."""
         if os.environ.get("LH_L2_TOUCH", "1") == "0" or not self.training:
             return
         lim = float(os.environ.get("LH_L2_TOUCH_MAX_MB", "3")) * (1 << 20)
         touch_all = os.environ.get("LH_L2_TOUCH", "1") == "2"      # experiment: the persistent kernels' panels too
         lib, ig, n = self.lib, self._IG, 0
-        # members of HRNet's batch groups too (their descriptors travel into the merged calls)?  MEASURED (HRNet-W32 bs 32 fp16): 13.04-13.06
-        # ms with them, 13.01-13.02 without, 13.05-13.07 with no touch at all: off by default
-        grouped = os.environ.get("LH_L2_TOUCH_GROUPS", "0") == "1"
 
         def attach(lst, fuse_fn, look):
             nonlocal n
             for i, c in enumerate(lst):
-                if not isinstance(c, _Call) or c.fn is not fuse_fn or c.lane or (c.mtag is not None and not grouped):
+                if not isinstance(c, _Call) or c.fn is not fuse_fn or c.lane or c.mtag is not None:
                     continue
-                # the next convolution on this call's stream lane: right behind it (single launches), or the same member of the next
-                # position of a batch group (the other members' launches sit in between until _merge_groups merges them)
+                # the next convolution on this call's stream lane, right behind it
                 nxt = None
-                for d in lst[i + 1:i + 1 + (look if c.mtag is None else 4 * look)]:
+                for d in lst[i + 1:i + 1 + look]:
                     if not isinstance(d, _Call) or d.lane or d.fn is lib.lh_bn_finalize:
                         continue
-                    if c.mtag is None or d.slane == c.slane:
-                        nxt = d
-                        break
-                if nxt is None or nxt.fn is not lib.lh_igemm or nxt.slane != c.slane or (nxt.mtag is None) != (c.mtag is None):
+                    nxt = d
+                    break
+                if nxt is None or nxt.fn is not lib.lh_igemm or nxt.slane != c.slane or nxt.mtag is not None:
                     continue
                 d = nxt.keep
                 if (d.cfg[2] in (1, 100) and not touch_all) or not nxt.args[ig["pack"]]:    # pointwise / direct kernels fetch their panel once per workgroup
@@ -1200,20 +1193,16 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         self._pack_event = side.record_event()
         return side_work is not None
 
-    def _run_lanes(self, calls, stream, hooks=None):
+    def _run_lanes(self, calls, stream):
         """Launch `calls` with the independent branch chains (stream lane > 0) on side streams: a lane's first launch
         after a fork waits for the fork's event on the main stream, the join makes the main stream wait for every lane
         used since; outside fork/join regions (and at the end of the slice) everything is ordered on the main stream.
-        Works eagerly and under hipGraph capture (the side streams join the capture through the events).
-        hooks: {i: fn(events)} -- before calls[i] is launched, fn receives events that cover everything launched so far
-        (main stream + every side stream used): work that only needs calls[:i] hangs off them without stalling any lane."""
+        Works eagerly and under hipGraph capture (the side streams join the capture through the events)."""
         main = torch.cuda.current_stream()
         assert main.cuda_stream == stream, "lanes need the launch stream to be torch's current stream"
         ev, forked, used = None, set(), set()
         wev, wused = {}, set()                 # weight-gradient side streams: pending event per stream, streams used
-        for ci, c in enumerate(calls):
-            if hooks and ci in hooks:
-                hooks[ci]([main.record_event()] + [self._lane_streams[L].record_event() for L in sorted(used | wused)])
+        for c in calls:
             if isinstance(c, _Marker):
                 if c.kind == "packjoin":
                     if self._pack_event is not None:
@@ -1280,17 +1269,12 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                 self._pack_late(stream)              # no side streams in this plan: the late group runs in place
                 self._pack_late = None
 
-    def run_backward(self, stream, lo=0, hi=None, hooks=None):
-        """Run bwd[lo:hi] (a segment of the backward list: data-parallel plans replay it bucket by bucket).
-        hooks: {index in the backward list: fn(events)}, called when everything before that index has been launched, with
-        events that cover it (TrainStep: the Adam update of the parameters whose gradients are final by then)."""
+    def run_backward(self, stream, lo=0, hi=None):
+        """Run bwd[lo:hi] (a segment of the backward list: data-parallel plans replay it bucket by bucket)."""
         calls = self.bwd[lo:hi]
-        hooks = {i - lo: f for i, f in hooks.items() if lo <= i < (len(self.bwd) if hi is None else hi)} if hooks else None
         if self.use_lanes:
-            return self._run_lanes(calls, stream, hooks)
-        for ci, c in enumerate(calls):
-            if hooks and ci in hooks:
-                hooks[ci]([torch.cuda.current_stream().record_event()])
+            return self._run_lanes(calls, stream)
+        for c in calls:
             if not isinstance(c, _Marker):
                 c(stream)
 

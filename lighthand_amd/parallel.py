@@ -191,8 +191,7 @@ def plan_buckets(marks, offsets, total, bucket_bytes=32 << 20):
 
 
 class GradSync:
-    """Launches one all-reduce per gradient bucket on a side stream; the optimizer waits for all of them (or updates each
-    bucket's parameters right behind its all-reduce: launch(after=...))."""
+    """Launches one all-reduce per gradient bucket on a side stream; the optimizer waits for all of them."""
 
     def __init__(self, world_size=None, bucket_bytes=32 << 20, group=None, compress=None, comm=None, algo="allreduce"):
         """compress='bf16': every bucket travels as bfloat16 (half the bytes per xGMI link; the sum is formed in bf16 by
@@ -219,8 +218,8 @@ class GradSync:
         self.stream = torch.cuda.Stream() if self.cuda else None
         self._pending = []
         self._segments = None
-        # measurement only (bench.py allreduce_exposed_ms): with stub = True launch() keeps its stream hand-over, the bf16
-        # staging and the `after` work but skips the collective itself -- the step then costs what it would with a free wire
+        # measurement only (bench.py allreduce_exposed_ms): with stub = True launch() keeps its stream hand-over and the bf16
+        # staging but skips the collective itself -- the step then costs what it would with a free wire
         self.stub = False
 
     def _direct_sum_(self, t):
@@ -263,16 +262,11 @@ class GradSync:
             self._segments = plan_buckets(plan.bwd_marks, offsets, plan.arena_numel, self.bucket_bytes)
         return self._segments
 
-    def launch(self, flat_grad, bucket, after=None):
-        """All-reduce flat_grad[start:stop] on the side stream.  after(stream): work to enqueue on that stream right behind
-        the collective (TrainStep: the Adam update of the bucket's parameters); device tensors only."""
+    def launch(self, flat_grad, bucket):
+        """All-reduce flat_grad[start:stop] on the side stream."""
         start, stop = bucket
         view = flat_grad[start:stop]
-        if after is not None and not (self.cuda and view.is_cuda):
-            raise ValueError("GradSync.launch(after=...) needs device gradients")
         if self.world_size == 1:
-            if after is not None:
-                after(torch.cuda.current_stream().cuda_stream)
             return
         if self.cuda and view.is_cuda:
             ev = torch.cuda.Event()
@@ -294,8 +288,6 @@ class GradSync:
                     _lib.check(lib.lh_cast_f32_bf16(view.data_ptr(), half.data_ptr(), stop - start, 1, sp), "lh_cast_f32_bf16")
                 else:
                     reduce_(view)
-                if after is not None:
-                    after(self.stream.cuda_stream)
                 done = torch.cuda.Event()
                 done.record(self.stream)
             self._pending.append(done)

@@ -102,6 +102,8 @@ def test_explicit_conv_configuration_must_fit():
     assert lib.lh_igemm_config(C.byref(d), _lib.LH_BF16, cfg) == -1 and b"does not fit" in lib.lh_last_error()
     d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = 128, 128, 2, 128
     assert lib.lh_igemm_config(C.byref(d), _lib.LH_BF16, cfg) == 0 and tuple(cfg[:4]) == (128, 128, 2, 128)
+    d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = 128, 128, 32, 128        # no form carries ring depth codes 30..39
+    assert lib.lh_igemm_config(C.byref(d), _lib.LH_BF16, cfg) == -3 and b"not compiled in" in lib.lh_last_error()
     d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = 256, 16, 1, 512          # pointwise panel with the wrong K padding
     assert lib.lh_igemm_config(C.byref(d), _lib.LH_BF16, cfg) == -1
     d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = 128, 16, 1, 256

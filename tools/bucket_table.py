@@ -52,10 +52,9 @@ def main():
         for i, (g, bucket) in enumerate(segs):
             if bucket == "adam":
                 sync.wait_all()
-            if g is not None:
-                g.replay()
+            g.replay()
             if bucket is not None and bucket != "adam":
-                sync.launch(step.arena.flat_grad, bucket, after=step._update_after(bucket))
+                sync.launch(step.arena.flat_grad, bucket)
             evs[i + 1].record()
         torch.cuda.synchronize()
         t = [evs[i].elapsed_time(evs[i + 1]) for i in range(len(segs))]
