@@ -76,6 +76,10 @@ int lh_image_u8_warp_to_nhwc4(const unsigned char* hwc, void* out, int n, int hs
 /* points fp32 [b][j][pstride] -> out fp32 [b][j][ostride]: (x, y) through the forward matrix fwd_dev fp32 [b][6].  Points
  * that leave the frame are kept; out may alias pts when the strides agree. */
 int lh_affine_points(const float* pts, int pstride, const float* fwd_dev, float* out, int ostride, int b, int j, void* stream);
+/* Flip test: mirror the w interior pixels of every row of a padded NHWC4 image [n][h+2*pad][wp][4] (the layout
+ * lh_image_to_nhwc4 and the lh_image_u8_* entries write, run dtype) in place, img'[y][x] = img[y][w-1-x]; the padding is
+ * not touched.  A bit-exact copy: a second call restores the input. */
+int lh_nhwc4_mirror(void* img, int n, int h, int w, int pad, int wp, int dtype, void* stream);
 /* NHWC (run dtype) -> NCHW fp32 heatmaps (what model(images) returns, pose_resnet.py:246)
  * and the inverse for the incoming gradient. c_stride = channel stride of the NHWC side. */
 int lh_nhwc_to_nchw_f32(const void* nhwc, float* nchw, int n, int h, int w, int c, int c_stride,
@@ -494,6 +498,13 @@ int lh_heatmap_soft_argmax(const float* heatmaps, int bj, int h, int w, float be
                            void* stream);
 int lh_heatmap_refine(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w,
                       float scale, float* preds, void* stream);
+/* Flip test's flip-back and merge (SimpleBaseline's flip_back + SHIFT_HEATMAP + average, TEST.FLIP_TEST of the reference's
+ * configs) followed by lh_heatmap_argmax's decode, in one launch.  a = heat-maps of the plain input, m = those of the
+ * horizontally mirrored input, fp32 [b*j][h][w]; f[y][x] = m[y][w-x] for x >= 1 and f[y][0] = m[y][w-1] when `shift`,
+ * else f[y][x] = m[y][w-1-x]; merged = (a + f) * 0.5f.  preds / maxvals / idx (idx may be NULL) as lh_heatmap_argmax on
+ * merged.  merged may alias a (the same pointer); it must not overlap m. */
+int lh_heatmap_flip_merge(const float* a, const float* m, int bj, int h, int w, int shift, float scale, float* merged,
+                          float* preds, float* maxvals, int* idx, void* stream);
 
 /* Validation metrics of Runner.run (src/utils/method.py:243-250) on the device: per sample, wrong[b] = number of
  * joints with error / bbox-diagonal(gt) > T (PCK_2d_loss 'proportion', src/utils/loss.py:116-148) and epe[b] = sum of

@@ -113,6 +113,7 @@ SIGNATURES = {
     "lh_image_u8_jitter_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _I, _P]),
     "lh_image_u8_warp_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P, _I, _P]),
     "lh_affine_points": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "lh_nhwc4_mirror": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
     "lh_nhwc_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lh_nchw_f32_to_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lh_pack_weight": (_I, [_P, _P, C.POINTER(_SZ), _I, _I, _L, _L, _L, _L, _I, C.POINTER(_I), _I, _P]),
@@ -173,6 +174,7 @@ SIGNATURES = {
     "lh_pck_curve": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "lh_heatmap_soft_argmax": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
     "lh_heatmap_refine": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    "lh_heatmap_flip_merge": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "lh_keypoint_metrics": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "lh_comm_unique_id": (_I, [_P]),
     "lh_comm_init": (_I, [C.POINTER(_P), _I, _I, _P]),

@@ -419,6 +419,44 @@ extern "C" int lh_affine_points(const float* pts, int pstride, const float* fwd_
     return LH_OK;
 }
 
+// Flip test (TEST.FLIP_TEST of the reference's configs): the second forward of a flip-test step reads the stem's padded NHWC4
+// image mirrored in place, img'[y][x] = img[y][w-1-x] over the w interior pixels of every row.  The padding is not touched, so
+// the zero border stays where the stem expects it.  The launch takes the place of the image launch in that pass: one kernel
+// serves every input path (float, uint8, ColorJitter, warp), and what the stem reads is bit for bit the mirror of what the
+// first pass fed it.  A pixel record (4 channels) moves as one word R: 8 bytes for 16-bit dtypes, 16 for fp32.  Thread k of
+// a row swaps records k and w-1-k, so consecutive lanes read and write consecutive records on both sides of the row.
+template <typename R>
+__global__ void nhwc4_mirror_kernel(R* img, int h, int w, int pad, int hp, int wp, unsigned half, unsigned total) {
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned r = i / half;                          // interior row b * h + y
+        const int k = (int)(i - r * half);
+        const unsigned b = r / (unsigned)h, y = r - b * (unsigned)h;
+        R* row = img + ((long)(b * (unsigned)hp + y + (unsigned)pad) * wp + pad);
+        const R lo = row[k], hi = row[w - 1 - k];
+        row[k] = hi;
+        row[w - 1 - k] = lo;
+    }
+}
+
+extern "C" int lh_nhwc4_mirror(void* img, int n, int h, int w, int pad, int wp, int dtype, void* stream) {
+    LH_REQUIRE(img && n > 0 && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "lh_nhwc4_mirror: bad arguments");
+    const int es = lh_dtype_size(dtype);
+    LH_REQUIRE(es > 0, "lh_nhwc4_mirror: unsupported dtype %d", dtype);
+    const int hp = h + 2 * pad;
+    LH_REQUIRE((long)n * hp * wp < (1L << 31), "lh_nhwc4_mirror: image batch too large for 32-bit pixel indices");
+    const unsigned half = (unsigned)(w / 2), total = (unsigned)n * (unsigned)h * half;
+    if (total == 0) return LH_OK;                             // w == 1: the mirror is the identity
+    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    if (es == 2)
+        hipLaunchKernelGGL((nhwc4_mirror_kernel<uint2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (uint2*)img, h, w, pad, hp, wp,
+                           half, total);
+    else
+        hipLaunchKernelGGL((nhwc4_mirror_kernel<uint4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (uint4*)img, h, w, pad, hp, wp,
+                           half, total);
+    LH_LAUNCH_CHECK("nhwc4_mirror launch");
+    return LH_OK;
+}
+
 template <typename T>
 __global__ void nhwc_to_nchw_kernel(const T* src, float* dst, int n, int hw, int c, int cs, int vec) {
     const long total = (long)n * hw;
@@ -859,6 +897,94 @@ extern "C" int lh_heatmap_refine(const float* heatmaps, const int* idx, const fl
     hipLaunchKernelGGL(heatmap_refine_kernel, dim3((bj + 255) / 256), dim3(256), 0, (hipStream_t)stream, heatmaps, idx, maxvals,
                        bj, h, w, scale, preds);
     LH_LAUNCH_CHECK("heatmap_refine launch");
+    return LH_OK;
+}
+
+// Flip test (TEST.FLIP_TEST / TEST.SHIFT_HEATMAP of the reference's configs) after the two forwards, in one launch: a = the
+// plain pass's heat-maps, m = those of the pass on the horizontally mirrored input.  SimpleBaseline's flip_back, its
+// `output_flipped[..., 1:] = output_flipped.clone()[..., :-1]` and `(output + output_flipped) * 0.5`:
+//   shift:    f[y][x] = m[y][W-x] for x >= 1, f[y][0] = m[y][W-1];   no shift: f[y][x] = m[y][W-1-x]
+//   merged = (a + f) * 0.5f (two fp32 roundings: -ffp-contract=off), then heatmap_argmax_kernel's decode of merged.
+// No joint permutation: the 21 joints of one hand are their own mirror images.
+// Why the one-column shift is right for this project's coordinates: the target of a joint at input x is centred on column
+// int(x / 4 + 0.5) and the decode multiplies the peak column by 4, so a joint at x = 4k peaks at column k.  The mirrored input
+// (width 4W) holds it at 4W-1-4k, centred on int(W - k + 0.25) = W - k; flipped back that is column W-1-(W-k) = k-1, and the
+// shift brings it back to k.
+// One workgroup per map, the tie rule of heatmap_argmax_kernel.  A thread loads a chunk of U elements of a and of m into
+// registers before it stores any of them: merged may alias a (each element is read and written by the same thread only), and
+// the loads of a chunk stay independent of its stores.
+template <int U>
+__global__ __launch_bounds__(256) void heatmap_flip_merge_kernel(const float* a, const float* m, int hw, int w, int shift, float scale,
+                                                                 float* merged, float* preds, float* maxvals, int* idx) {
+    __shared__ Cand red[4];
+    const long base = (long)blockIdx.x * hw;
+    const float* am = a + base;
+    const float* mm = m + base;
+    float* om = merged + base;
+    const int dy = 256 / w, dx = 256 - dy * w;                // element i + 256 is dy rows and dx columns further
+    Cand best = {0.f, 0x7fffffff};
+    bool have = false;
+    int y = threadIdx.x / w, x = threadIdx.x - y * w;          // row and column of element i0
+    for (int i0 = threadIdx.x; i0 < hw; i0 += 256 * U) {
+        float va[U], vf[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            va[u] = vf[u] = 0.f;
+            if (i < hw) {
+                const int sx = shift ? (x ? w - x : w - 1) : w - 1 - x;
+                va[u] = am[i];
+                vf[u] = mm[y * w + sx];
+            }
+            x += dx;
+            y += dy;
+            if (x >= w) { x -= w; ++y; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            if (i < hw) {
+                const float v = (va[u] + vf[u]) * 0.5f;
+                om[i] = v;
+                const Cand c = {v, i};
+                if (!have || cand_before(c, best)) { best = c; have = true; }
+            }
+        }
+    }
+    // the reduction and store of heatmap_argmax_kernel, restated: that kernel keeps its code
+    if (!have) best = Cand{-INFINITY, 0x7fffffff};
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Cand other = {__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
+        if (other.i != 0x7fffffff && (best.i == 0x7fffffff || cand_before(other, best))) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Cand b = red[0];
+        for (int k = 1; k < 4; ++k)
+            if (red[k].i != 0x7fffffff && (b.i == 0x7fffffff || cand_before(red[k], b))) b = red[k];
+        const float keep = b.v > 0.f ? 1.f : 0.f;
+        preds[blockIdx.x * 2 + 0] = (float)(b.i % w) * keep * scale;
+        preds[blockIdx.x * 2 + 1] = (float)(b.i / w) * keep * scale;
+        maxvals[blockIdx.x] = b.v;
+        if (idx) idx[blockIdx.x] = b.i;
+    }
+}
+
+extern "C" int lh_heatmap_flip_merge(const float* a, const float* m, int bj, int h, int w, int shift, float scale, float* merged,
+                                     float* preds, float* maxvals, int* idx, void* stream) {
+    LH_REQUIRE(a && m && merged && preds && maxvals && bj > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31),
+               "lh_heatmap_flip_merge: bad arguments");
+    const size_t bytes = (size_t)bj * h * w * sizeof(float);
+    const auto apart = [bytes](const void* p, const void* q) {
+        return (const char*)p + bytes <= (const char*)q || (const char*)q + bytes <= (const char*)p;
+    };
+    LH_REQUIRE(apart(m, merged) && (a == merged || apart(a, merged)),
+               "lh_heatmap_flip_merge: merged may alias a exactly and must not overlap m");
+    hipLaunchKernelGGL((heatmap_flip_merge_kernel<4>), dim3(bj), dim3(256), 0, (hipStream_t)stream, a, m, h * w, w, shift ? 1 : 0,
+                       scale, merged, preds, maxvals, idx);
+    LH_LAUNCH_CHECK("heatmap_flip_merge launch");
     return LH_OK;
 }
 

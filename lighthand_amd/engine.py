@@ -789,6 +789,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         self.img_nhwc4, self.img_pad, self.img_wp = img, p, wp
         self.fwd.append(_Call(self.lib.lh_image_to_nhwc4, (self.img_nchw.data_ptr(), img.data_ptr(), x.n, x.h, x.w, p, wp, self.dt), "image transform"))
         self._image_call_index = len(self.fwd) - 1
+        # the flip test's second pass: the image launch of run_forward(mirrored=True), whichever input path wrote img
+        self._mirror_call = _Call(self.lib.lh_nhwc4_mirror, (img.data_ptr(), x.n, x.h, x.w, p, wp, self.dt), "image mirror")
         stage = self._alloc(cout, k, kr // 4, 4, dtype=torch.float32, zero=True)
         self.packs.append(self._copy4(stage[:, :, :k, :3], wt.detach().permute(0, 2, 3, 1), "stem weight staging"))
         rows = [(r, 0) for r in range(k)]
@@ -1256,10 +1258,22 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         for L in used | wused:
             main.wait_stream(self._lane_streams[L])
 
-    def run_forward(self, stream):
+    def _mirrored_forward(self):
+        """The forward list with the image launch replaced by lh_nhwc4_mirror on img_nhwc4: the pass reads the input of the
+        previous forward mirrored horizontally (flip test, runtime.InferStep(flip_test=True)); the rest of the list is the
+        plain pass's, so a training-mode plan normalises with this pass's batch statistics and updates the running ones again."""
+        i = self._image_call_index
+        img = self.fwd[i]
+        assert isinstance(img, _Call) and img.args[1] == self.img_nhwc4.data_ptr(), "the image launch moved in the forward list"
+        self._mirror_call.slane = img.slane
+        return self.fwd[:i] + [self._mirror_call] + self.fwd[i + 1:]
+
+    def run_forward(self, stream, mirrored=False):
+        """mirrored=True: the forward of the horizontal mirror of the image the previous forward read (_mirrored_forward)."""
+        calls = self._mirrored_forward() if mirrored else self.fwd
         if self.use_lanes:
-            return self._run_lanes(self.fwd, stream)
-        for c in self.fwd:
+            return self._run_lanes(calls, stream)
+        for c in calls:
             if not isinstance(c, _Marker):
                 c(stream)
             elif c.kind == "packjoin" and self._pack_event is not None:

@@ -158,6 +158,29 @@ def max_preds_device(heatmaps, scale=1.0, post_process=False):
     return preds, maxvals, idx
 
 
+def flip_merge_device(heatmaps, heatmaps_mirrored, shift=True, scale=1.0, out=None):
+    """Flip test for callers that run their own forwards: heatmaps float32 [B, J, H, W] of the plain batch and
+    ``heatmaps_mirrored`` of the same batch mirrored horizontally, on the device ->
+    (preds [B, J, 2], maxvals [B, J, 1], flat indices [B, J], merged [B, J, H, W]) device tensors.  merged = (heatmaps +
+    flipped-back mirrored maps, shifted one column when ``shift``) * 0.5 (SimpleBaseline's flip test; TEST.SHIFT_HEATMAP), decoded
+    like ``max_preds_device``.  ``out``: a float32 [B, J, H, W] buffer for merged (may be ``heatmaps`` itself)."""
+    if heatmaps.dim() != 4 or heatmaps_mirrored.shape != heatmaps.shape:
+        raise AssertionError("heatmaps and heatmaps_mirrored should be 4-ndim of one shape")
+    a = heatmaps.to(torch.float32).contiguous()
+    m = heatmaps_mirrored.to(torch.float32).contiguous()
+    b, j, h, w = a.shape
+    if out is None:
+        out = torch.empty_like(a)
+    if out.shape != a.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(a.shape)}")
+    preds = torch.empty(b, j, 2, dtype=torch.float32, device=a.device)
+    maxvals = torch.empty(b, j, 1, dtype=torch.float32, device=a.device)
+    idx = torch.empty(b, j, dtype=torch.int32, device=a.device)
+    check(_lib.load().lh_heatmap_flip_merge(a.data_ptr(), m.data_ptr(), b * j, h, w, int(bool(shift)), float(scale), out.data_ptr(),
+                                            preds.data_ptr(), maxvals.data_ptr(), idx.data_ptr(), _stream()), "lh_heatmap_flip_merge")
+    return preds, maxvals, idx, out
+
+
 def soft_argmax_device(heatmaps, beta=100.0, scale=1.0):
     """Opt-in differentiable-style decode (an extension: the reference only has the hard arg-max): heatmaps float32
     [B, J, H, W] on the device -> expected (x, y) under softmax(beta * heatmap), [B, J, 2] device tensor."""

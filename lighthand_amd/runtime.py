@@ -341,11 +341,22 @@ class TrainStep:
 class InferStep:
     """Eval-mode forward + arg-max decode as one captured graph (wearable_eval_2d / pred_store path,
     src/utils/argparser.py:246-281).  ``bn_train=True`` reproduces the reference quirk of running
-    ``pred_store`` without ``model.eval()`` (batch statistics at evaluation time)."""
+    ``pred_store`` without ``model.eval()`` (batch statistics at evaluation time).
+
+    The TEST block of the reference's configs, opt-in and inside the same graph:
+    ``flip_test`` (TEST.FLIP_TEST) runs the forward a second time on the batch mirrored horizontally (lh_nhwc4_mirror in place
+    of the image launch) and decodes the average of the plain heat-maps and the flipped-back mirrored ones
+    (lh_heatmap_flip_merge); ``heatmaps`` is then that merged buffer.  Both passes run the plan of ``batch``, so with
+    ``bn_train`` each pass normalises with its own batch statistics and updates the running ones, as two model() calls do.
+    ``shift_heatmap`` (TEST.SHIFT_HEATMAP) shifts the flipped-back maps by one column before the average; it only applies to
+    the flip test.  ``post_process`` (TEST.POST_PROCESS) adds the quarter-pixel refinement (lh_heatmap_refine) to the decode."""
 
     _serial = 0
 
-    def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0):
+    def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
+                 flip_test=False, shift_heatmap=True, post_process=False):
+        if not shift_heatmap and not flip_test:
+            raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
         self.lib = _lib.load()
         # a plan of its own (never the one model(x) runs): use_uint8_input rewires the plan's image launch, and a pipeline
         # slot replays asynchronously on its own stream -- neither may happen to the plan model.forward() uses
@@ -356,9 +367,12 @@ class InferStep:
         dev = out.device
         # input_u8=(hs, ws): raw uint8 HWC frames; ToTensor / Resize / Normalize run fused on the device (dataset.py:128-159)
         self.images = self.plan.use_uint8_input(*input_u8) if input_u8 else self.plan.img_nchw
-        self.heatmaps = out
+        self.flip_test, self.shift_heatmap, self.post_process = flip_test, shift_heatmap, post_process
+        # flip test: the plain pass's maps are copied here, and the merge writes over them in place
+        self.heatmaps = torch.zeros_like(out) if flip_test else out
         self.preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
         self.maxvals = torch.zeros(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
+        self.idx = torch.zeros(batch, out.shape[1], dtype=torch.int32, device=dev) if post_process else None
         self.scale = float(height // out.shape[2])
         self.use_graph = use_graph
         self.graph = None
@@ -367,9 +381,20 @@ class InferStep:
     def _enqueue(self):
         s = torch.cuda.current_stream().cuda_stream
         self.plan.run_forward(s)
-        out = self.heatmaps
-        check(self.lib.lh_heatmap_argmax(out.data_ptr(), out.shape[0] * out.shape[1], out.shape[2], out.shape[3], self.scale,
-                                         self.preds.data_ptr(), self.maxvals.data_ptr(), None, s), "lh_heatmap_argmax")
+        out, hm = self.plan.out_nchw, self.heatmaps
+        bj, h, w = out.shape[0] * out.shape[1], out.shape[2], out.shape[3]
+        if self.flip_test:
+            hm.copy_(out)
+            self.plan.run_forward(s, mirrored=True)
+            check(self.lib.lh_heatmap_flip_merge(hm.data_ptr(), out.data_ptr(), bj, h, w, int(self.shift_heatmap), self.scale,
+                                                 hm.data_ptr(), self.preds.data_ptr(), self.maxvals.data_ptr(), _ptr(self.idx), s),
+                  "lh_heatmap_flip_merge")
+        else:
+            check(self.lib.lh_heatmap_argmax(hm.data_ptr(), bj, h, w, self.scale, self.preds.data_ptr(), self.maxvals.data_ptr(),
+                                             _ptr(self.idx), s), "lh_heatmap_argmax")
+        if self.post_process:
+            check(self.lib.lh_heatmap_refine(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.scale,
+                                             self.preds.data_ptr(), s), "lh_heatmap_refine")
 
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
@@ -402,16 +427,18 @@ class InferPipeline:
     a stream of its own.  The stage 3-4 launches of one batch are latency-bound chains of one wave of tiles; a second batch
     fills the machine under them: R50 256x256 bs 64 bf16, 29.9 k img/s with one batch in flight, 33.3 k with two (MI355X).
     Eval-mode only (the batch-statistics quirk of ``pred_store`` updates the running statistics, which slots would race on).
+    ``flip_test`` / ``shift_heatmap`` / ``post_process``: as InferStep's, for every slot.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
         preds0, maxvals0 = pipe.result(t0)          # valid until `depth` more batches have been submitted
     """
 
-    def __init__(self, model, batch, height, width, depth=2, input_u8=None):
+    def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i) for i in range(depth)]
+        self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
+                                shift_heatmap=shift_heatmap, post_process=post_process) for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
         self.count = 0

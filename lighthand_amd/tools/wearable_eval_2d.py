@@ -11,6 +11,10 @@ Reference quirk kept behind a flag: ``pred_store`` never calls ``model.eval()``,
 BATCH statistics at evaluation time.  ``--bn_train`` (default, = reference behaviour) reproduces that;
 ``--bn_eval`` uses the running statistics (BN folded into the conv epilogues).
 
+The configs' TEST block, off by default (= reference behaviour): ``--flip_test`` (TEST.FLIP_TEST) averages the heat-maps of every
+image and of its mirror image, flipped back and shifted one column (``--no_shift_heatmap`` drops the shift, TEST.SHIFT_HEATMAP);
+``--post_process`` (TEST.POST_PROCESS) refines the arg-max by a quarter pixel.  Both run inside the captured InferStep.
+
 The reference's evaluation set (Armo_hand_dataset) is not redistributable: ``--synthetic N`` builds a seeded
 stand-in with the four occlusion categories and visibility flags.
 """
@@ -48,22 +52,23 @@ class _Steps:
     (argparser.py:258-262) -- padding it would put foreign samples into the BatchNorm batch statistics that
     ``pred_store``'s train-mode forward uses, and into the running-statistics update."""
 
-    def __init__(self, model, size, bn_train):
+    def __init__(self, model, size, bn_train, flip_test=False, shift_heatmap=True, post_process=False):
         self.model, self.size, self.bn_train, self.steps = model, size, bn_train, {}
+        self.options = dict(flip_test=flip_test, shift_heatmap=shift_heatmap, post_process=post_process)
 
     def __call__(self, images):
         from lighthand_amd.runtime import InferStep
         n = images.shape[0]
         step = self.steps.get(n)
         if step is None:
-            step = self.steps[n] = InferStep(self.model, n, self.size, self.size, bn_train=self.bn_train)
+            step = self.steps[n] = InferStep(self.model, n, self.size, self.size, bn_train=self.bn_train, **self.options)
         return step(images.cuda(non_blocking=True))
 
 
-def pred_store(model, loader, out_json, batch, size, bn_train=True):
+def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
     """src/utils/argparser.py:246-281 with the forward + arg-max decode on the device."""
     meta = {c: {"bb": [], "pred": [], "gt": []} for c in CATEGORIES}
-    step = _Steps(model, size, bn_train)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
     for images, joints_v, cats in loader:
         preds = step(images).cpu()                       # already x4 (method.py:157)
         gt = joints_v[:, :, :2]
@@ -80,12 +85,12 @@ def pred_store(model, loader, out_json, batch, size, bn_train=True):
     return meta
 
 
-def pred_store_test(model, loader, out_json, batch, size, bn_train=True):
+def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
     """src/utils/argparser.py:284-323 -- the category-less variant: one entry per BATCH of predictions (x4, 256-px frame),
     ground truth and bounding-box diagonals; read back by ``lighthand_amd.metrics.pred_test``.  The loader yields
     (images, gt_2d_joints[, ...])."""
     meta = {"pred": [], "gt": [], "bb": []}
-    step = _Steps(model, size, bn_train)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
     for item in loader:
         images, gt = item[0], item[1][:, :, :2]
         preds = step(images).cpu()
@@ -100,13 +105,13 @@ def pred_store_test(model, loader, out_json, batch, size, bn_train=True):
     return meta
 
 
-def device_eval(model, loader, batch, size, bn_train=True):
+def device_eval(model, loader, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
     """Same evaluation reduced ON THE DEVICE: per threshold set the PCK-curve counts of all visible
     joints are accumulated by lh_pck_curve, summed across data-parallel ranks with one small all-reduce, and read by
     the host once.  Returns {(type, T1): [auc, epe_mm, curve]}; the AUC equals pred_eval's 'mean_auc' AUC (whose EPE is
     diluted by the reference's zeros quirk; the EPE here is the plain mean)."""
     from lighthand_amd.metrics import auc_from_counts, device_pck_curve
-    step = _Steps(model, size, bn_train)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
     acc = {(t, tuple(T)): None for t, T in THRESHOLDS}
     for images, joints_v, _ in loader:
         preds = step(images)
@@ -139,9 +144,7 @@ def write_report(path, results):
                         f.write("\n")
 
 
-def main(argv=None):
-    from lighthand_amd.metrics import pred_eval
-    from lighthand_amd.tools.train import build_model
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root_path", default="output")
     ap.add_argument("--model_path", default="simplebaseline/frei", help="sub-tree of root_path searched for *.bin (reference: output/simplebaseline/frei)")
@@ -153,7 +156,21 @@ def main(argv=None):
     ap.add_argument("--synthetic", default=0, type=int)
     ap.add_argument("--bn_eval", action="store_true")
     ap.add_argument("--device_metrics", action="store_true", help="also reduce the PCK curves / AUC on the device and print them")
+    ap.add_argument("--flip_test", action="store_true", help="average with the flipped-back heat-maps of the mirrored image (TEST.FLIP_TEST)")
+    ap.add_argument("--no_shift_heatmap", dest="shift_heatmap", action="store_false",
+                    help="with --flip_test: no one-column shift of the flipped-back heat-maps (TEST.SHIFT_HEATMAP off)")
+    ap.add_argument("--post_process", action="store_true", help="quarter-pixel refinement of the arg-max (TEST.POST_PROCESS)")
+    return ap
+
+
+def main(argv=None):
+    from lighthand_amd.metrics import pred_eval
+    from lighthand_amd.tools.train import build_model
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if not args.shift_heatmap and not args.flip_test:
+        ap.error("--no_shift_heatmap applies to --flip_test")
+    test_opts = dict(flip_test=args.flip_test, shift_heatmap=args.shift_heatmap, post_process=args.post_process)
     if not args.synthetic:
         raise SystemExit("the Armo_hand evaluation set is not shipped: pass --synthetic N or plug your own Dataset")
     data = SyntheticEvalSet(args.synthetic, args.size)
@@ -172,10 +189,11 @@ def main(argv=None):
             model.load_state_dict(torch.load(path, map_location="cpu")["model_state_dict"], strict=False)
             model.train(not args.bn_eval)
             out_json = os.path.join(args.root_path, name, "evaluation.json")
-            meta = pred_store(model, loader, out_json, args.batch_size, args.size, bn_train=not args.bn_eval)
+            meta = pred_store(model, loader, out_json, args.batch_size, args.size, bn_train=not args.bn_eval, **test_opts)
             results.append([pred_eval({k: v for k, v in meta.items() if v["bb"]}, T_list, t_type), name])
             if args.device_metrics and t_type == THRESHOLDS[0][0] and T_list == THRESHOLDS[0][1]:
-                for (ty, t1), (auc, epe, _) in device_eval(model, loader, args.batch_size, args.size, bn_train=not args.bn_eval).items():
+                for (ty, t1), (auc, epe, _) in device_eval(model, loader, args.batch_size, args.size, bn_train=not args.bn_eval,
+                                                           **test_opts).items():
                     host = pred_eval({k: v for k, v in meta.items() if v["bb"]}, [t for n_, t in THRESHOLDS if n_ == ty and t[1] == t1][0], ty)
                     print(f"device metrics {name} {ty} {t1}: auc {auc:.4f} (host mean_auc {host['mean_auc'][0]:.4f}) epe {epe:.3f} mm")
         fn = os.path.join(args.root_path, f"pck_eval_{'_'.join(args.model_path.split('/'))}_{t_type}_{T_list[1]}.txt")
