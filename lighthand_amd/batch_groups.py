@@ -2,7 +2,6 @@
 compile order that puts the k-th node of every branch side by side, and the final pass that merges their launches into lh_*_multi calls.
 A mixin of ``engine.Plan`` (split out of engine.py in round 6)."""
 import ctypes as C
-import os
 
 import torch
 

@@ -9,7 +9,6 @@ of ctypes calls on the caller's HIP stream -- which is exactly what a hipGraph c
 (``lighthand_amd.runtime.TrainStep``).
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -18,6 +17,7 @@ from ._lib import FuseBwdDesc, FuseDesc, IgemmDesc, check
 from .batch_groups import BatchGroups
 from .graph import BN_EPS, BN_MOMENTUM, PRECISIONS, Act, GraphBuilder, _Call, _Marker, _desc, _ptr, _taps_array  # noqa: F401 (re-exported)
 from .infer_rewrites import InferRewrites
+from .options import PlanOptions
 from .tuner import Tuner
 from .wgrad_schedule import WgradSchedule
 
@@ -26,8 +26,9 @@ from .wgrad_schedule import WgradSchedule
 class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
     """Everything needed to run one model at one static shape."""
 
-    def __init__(self, model, n, h, w, precision="fp32", training=True, backward=None, device=None, wgrad_bucket_bytes=None):
+    def __init__(self, model, n, h, w, precision="fp32", training=True, backward=None, device=None, wgrad_bucket_bytes=None, options=None):
         self.lib = _lib.load()
+        self.opt = options if options is not None else PlanOptions.from_env()     # the LH_* planning switches, resolved once (options.py)
         self.precision = precision
         self.tdtype = PRECISIONS[precision]
         self.dt = _lib.dtype_code(self.tdtype)
@@ -62,11 +63,11 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         # Multi-problem launches: the nodes at the same position of the parallel chains of a fork .. join region (HRNet's
         # branches) are compiled as a GROUP whose launches merge into lh_*_multi calls (one grid for 2-4 problems) on the
         # main stream, instead of one launch per branch on stream lanes.  16-bit types; LH_BATCH=0 keeps the lanes.
-        self.batch = os.environ.get("LH_BATCH", "1") != "0" and self.es == 2 and self.n_lanes > 1
-        self.wgrad_batch = os.environ.get("LH_WGRAD_BATCH", "1") != "0" and self.es == 2
+        self.batch = self.opt.batch and self.es == 2 and self.n_lanes > 1
+        self.wgrad_batch = self.opt.wgrad_batch and self.es == 2
         # Table launches (round 6): ALL weight gradients of a deferred group that share a tile class run as ONE grid with a split count
         # per layer + at most one fold grid (lh_wgrad_table_run; _table_wgrads).  LH_WGRAD_TABLE=0: one launch (+ fold) per layer.
-        self.wgrad_table = os.environ.get("LH_WGRAD_TABLE", "1") != "0" and self.es == 2
+        self.wgrad_table = self.opt.wgrad_table and self.es == 2
         self.wgrad_tables = []             # (call, info, member names) of every table launch of the plan
         self._forced = None                # kernel choices of the group being compiled (see _tune_group)
         self._n_groups = 0
@@ -81,13 +82,13 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         auto_group = max(4, -(-n_convs * 62 // 100))         # 36 layers for R50 (re-measured in round 3: 24: 9.65 ms, 32-40: 9.59-9.61, 48: 9.77)
         if self.n_lanes > 1:
             auto_group = 16                                   # branch lanes hand over at every module end; 16 on the main lane
-        self.wgrad_group = int(os.environ.get("LH_WGRAD_GROUP", str(auto_group))) if self.with_bwd else 0
+        self.wgrad_group = (auto_group if self.opt.wgrad_group is None else self.opt.wgrad_group) if self.with_bwd else 0
         # data-parallel plans: a deferred group ALSO ends as soon as its layers hold one gradient bucket's worth of
         # parameters, so the first bucket's all-reduce starts early in the backward pass (parallel.wgrad_group_cuts)
         self.wgrad_bucket_bytes = wgrad_bucket_bytes
         if self.wgrad_group > 0:
             self.use_lanes = True
-            self._w_lanes = int(os.environ.get("LH_WGRAD_LANES", "2" if self.n_lanes == 1 else "4"))
+            self._w_lanes = (2 if self.n_lanes == 1 else 4) if self.opt.wgrad_lanes is None else self.opt.wgrad_lanes
             for i in range(self._w_lanes):
                 self._lane_streams[-1 - i] = torch.cuda.Stream(device=self.device)
         self._pend = {}                    # source lane -> dict(calls, names, layers, ws)
@@ -217,8 +218,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             #  Inside them the members of a batch group run merged tiled launches whose reduce passes are merged too: carrying the gates into
             #  lh_igemm_multi was measured +0.26 ms SLOWER, round 6; a plan computes the same sums whether its branches run as groups or lanes)
             in_branch = self._emit_group > 1 or self._cur_lane != 0 or getattr(self, "_in_branch", False)
-            gi = self._gate_info.get(id(x)) if (self.bn_gate and first and len(descs) == 1 and self.es == 2 and
-                                                (self.n_lanes == 1 or (self.bn_gate_branches and not in_branch))) else None
+            gi = self._gate_info.get(id(x)) if (self.opt.bn_gate and first and len(descs) == 1 and self.es == 2 and
+                                                (self.n_lanes == 1 or (self.opt.bn_gate_branches and not in_branch))) else None
             gkind, gbytes = self._gate_kind(gi, x, amask is not None), x.pixels * x.c * self.es
             self._tune([dd], addend=kind, role="dgrad", gate=(gkind, gbytes) if gkind else None)
             cfg = (C.c_int * 5)()
@@ -272,7 +273,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             return None
         uses = len(self._uses.get(id(x), []))
         if gi.get("mask") is not None:
-            ok = self.bn_gate_tail and (uses == 1 or (uses == 2 and masked_addend))
+            ok = self.opt.bn_gate_tail and (uses == 1 or (uses == 2 and masked_addend))
             return None if not ok else "mask2" if gi.get("raw2") is not None else "mask"
         return "x" if uses == 1 else None
 
@@ -282,13 +283,14 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         persistent kernels (pointwise, direct 3x3: streams of independent waves, the extra read rides with the others) up to
         LH_BN_GATE_PW_MAX_MB; tails up to LH_BN_GATE_TAIL_MAX_MB on either."""
         pw, tiled = cfg[2] in (1, 100), (2 <= cfg[2] < 10 or 20 <= cfg[2] < 40)
-        if not (tiled or (pw and self.bn_gate_pw)):
+        opt, mb = self.opt, nbytes / (1 << 20)
+        if not (tiled or (pw and opt.bn_gate_pw)):
             return False
         if kind == "mask2":                # two BatchNorm terms (a projection shortcut): the pointwise kernel only
-            return cfg[2] == 1 and self.bn_gate_tail2 and nbytes <= self.bn_gate_tail_bytes
+            return cfg[2] == 1 and opt.bn_gate_tail2 and mb <= opt.bn_gate_tail_max_mb
         if kind == "mask":
-            return nbytes <= (self.bn_gate_tail_bytes if pw else min(self.bn_gate_tail_bytes, self.bn_gate_tiled_tail_bytes))
-        return nbytes <= (self.bn_gate_pw_bytes if pw else self.bn_gate_bytes)
+            return mb <= (opt.bn_gate_tail_max_mb if pw else min(opt.bn_gate_tail_max_mb, opt.bn_gate_tiled_tail_max_mb))
+        return mb <= (opt.bn_gate_pw_max_mb if pw else opt.bn_gate_max_mb)
 
     def _patch(self, call, relu=None, **ptrs):
         a = list(call.args)
@@ -395,18 +397,9 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         self._masked_addend = {}           # id(activation) -> (dout, relu mask bits) a later data-gradient launch adds
         # BatchNorm-backward gate (lh_igemm_gated): id(activation a = relu(BN(x))) -> what the data gradient that writes a.grad
         # needs (recorded by _c_fuse), and id(a) -> (partial sums, rows) once such a launch has been planned (read by the node's
-        # backward, which then skips its reduce pass).  LH_BN_GATE=0: off.
+        # backward, which then skips its reduce pass).  LH_BN_GATE=0: off; the LH_BN_GATE_* switches and caps: options.py.
         self._gate_info, self._gated = {}, {}
         self._bnrelu_info = {}             # id(a = relu(BN(x))) -> its lh_fuse_fwd call and BN state (training plans; _c_maxpool)
-        self.bn_gate = os.environ.get("LH_BN_GATE", "1") != "0"
-        self.bn_gate_bytes = float(os.environ.get("LH_BN_GATE_MAX_MB", "9")) * (1 << 20)
-        self.bn_gate_pw = os.environ.get("LH_BN_GATE_PW", "1") != "0"               # round 6: the pointwise kernel's epilogue takes the gate too
-        self.bn_gate_pw_bytes = float(os.environ.get("LH_BN_GATE_PW_MAX_MB", "1024")) * (1 << 20)
-        self.bn_gate_tail = os.environ.get("LH_BN_GATE_TAIL", "1") != "0"           # round 6: residual tails (sign from the stored mask bits)
-        self.bn_gate_tail_bytes = float(os.environ.get("LH_BN_GATE_TAIL_MAX_MB", "1024")) * (1 << 20)
-        self.bn_gate_tiled_tail_bytes = float(os.environ.get("LH_BN_GATE_TILED_TAIL_MAX_MB", "1024")) * (1 << 20)
-        self.bn_gate_tail2 = os.environ.get("LH_BN_GATE_TAIL2", "1") != "0"         # ... tails with a projection shortcut (two BatchNorm terms)
-        self.bn_gate_branches = os.environ.get("LH_BN_GATE_BRANCHES", "1") != "0"   # ... in networks with parallel branches (HRNet), outside the branch regions
         # consumers of every activation in forward order: (kind, node) -- backward visits them in reverse
         self._uses = {}
         for kind, nd in self.nodes:
@@ -465,7 +458,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             # (R50: stage 4 + the head's transposed convolutions, 75 % of the parameters) are packed by a second launch that
             # runs under the latency-bound middle of the forward pass instead of beside the HBM-bound stem and stage 1.
             groups = [convs]
-            if self.with_bwd and len(convs) >= 16 and os.environ.get("LH_LATE_PACK", "1") != "0":
+            if self.with_bwd and len(convs) >= 16 and self.opt.late_pack:
                 size = [cv.d0 * cv.d1 * cv.rs for cv in convs]
                 total, acc, cut = sum(size), 0, len(convs)
                 while cut > 0 and acc + size[cut - 1] <= 0.8 * total:
@@ -546,7 +539,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                     self._cur_lane = lane
                     self._flush_wgrads(lane)
             for src in sorted(self._pend):
-                self._flush_wgrads(src, spread=os.environ.get("LH_TAIL_SPREAD", "1") != "0")
+                self._flush_wgrads(src, spread=self.opt.tail_spread)
             self.bwd_marks.sort(key=lambda m: m[0])
             # two workspaces: the weight-gradient chain may run concurrently with the BN-backward chain
             # (stream lanes run concurrently: each lane has its own pair)
@@ -590,10 +583,10 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         seen yet (profiles/r05_ingest_ladder.txt, sitting 6: the complete K loop of the stage-3 3x3 takes 21.3 us, 19.1 us with the
         pack in L2).  Only where the pack fits beside the pass's own stream in the 4 MB L2 of an XCD (LH_L2_TOUCH_MAX_MB, default 3;
         LH_L2_TOUCH=0: off).  Not for members of HRNet's batch groups (measured slightly slower)."""
-        if os.environ.get("LH_L2_TOUCH", "1") == "0" or not self.training:
+        if not self.opt.l2_touch or not self.training:
             return
-        lim = float(os.environ.get("LH_L2_TOUCH_MAX_MB", "3")) * (1 << 20)
-        touch_all = os.environ.get("LH_L2_TOUCH", "1") == "2"      # experiment: the persistent kernels' panels too
+        lim = self.opt.l2_touch_max_mb * (1 << 20)
+        touch_all = self.opt.l2_touch == 2      # experiment: the persistent kernels' panels too
         lib, ig, n = self.lib, self._IG, 0
 
         def attach(lst, fuse_fn, look):
@@ -800,7 +793,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         stats_ptr = None
         flops = 2.0 * y.pixels * cout * 3 * k * k
         direct = (self.training and id(y) in self._bn_inputs and self.es == 2 and (k, s, p, cout, y.c) == (7, 2, 3, 64, 64) and bias is None
-                  and os.environ.get("LH_STEM_DIRECT", "1") != "0")
+                  and self.opt.stem_direct)
         if direct:
             # training stem (pose_resnet.py:151-152) on the direct kernel: weights in registers, a tile's input patch in LDS,
             # raw convolution output + one statistics row per workgroup (stem_pool.hip, lh_stem_conv)
@@ -1080,7 +1073,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             return
         xbuf, ybuf = self._act_buf(x), self._act_buf(y)
         idx = self._alloc(y.n, y.h, y.w, y.c, dtype=torch.uint8) if self.with_bwd else None     # window positions: only the backward pass reads them
-        bi = self._bnrelu_info.get(id(x)) if os.environ.get("LH_BN_POOL", "1") != "0" else None
+        bi = self._bnrelu_info.get(id(x)) if self.opt.bn_pool else None
         nchunk = x.c * self.es // 16
         if bi is not None and len(self._uses.get(id(x), [])) == 1 and self.fwd and self.fwd[-1] is bi["call"] and x.c == x.c_valid \
                 and nchunk & (nchunk - 1) == 0 and nchunk <= 256:            # (the flat BN-backward kernels: they take the mask from raw)
@@ -1106,7 +1099,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         def emit():
             dy, dx = self._act_grad(y), self._act_grad(x)
             assert self._first_write(x), "maxpool input gradient must be produced by the pool alone"
-            gi = self._gate_info.get(id(x)) if (self.bn_gate and self.n_lanes == 1 and self.es == 2 and os.environ.get("LH_POOL_GATE", "1") != "0") else None
+            gi = self._gate_info.get(id(x)) if (self.opt.bn_gate and self.n_lanes == 1 and self.es == 2 and self.opt.pool_gate) else None
             nch = x.c * self.es // 16
             if gi is not None and gi.get("mask") is None and len(self._uses.get(id(x), [])) == 1 and x.c == x.c_valid and nch & (nch - 1) == 0 and nch <= 256:
                 # x = relu(BN(raw)) with the pool as its only reader: the pool's backward stores the ReLU-gated gradient and the

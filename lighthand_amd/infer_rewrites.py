@@ -2,7 +2,6 @@
 launch, the stage-1 bottlenecks as one launch each, the 1x1 head inside the last transposed convolution's epilogue.  A mixin of
 ``engine.Plan`` (split out of engine.py in round 6).  Reference: PoseResNet.forward, src/modeling/simplebaseline/pose_resnet.py:234-248."""
 import ctypes as C
-import os
 
 import torch
 
@@ -16,7 +15,7 @@ class InferRewrites:
 
     fuse_stem = True             # test hook: False keeps the inference stem as convolution + max-pool launches (A/B against _fuse_stem_pool)
 
-    fuse_bottleneck = os.environ.get("LH_FUSE_BOTTLENECK", "1") != "0"    # False keeps the stage-1 bottlenecks of inference plans as three launches (A/B against _fuse_bottleneck)
+    fuse_bottleneck = True    # test hook: False keeps the stage-1 bottlenecks of inference plans as three launches, as LH_FUSE_BOTTLENECK=0 does (A/B against _fuse_bottleneck)
 
     def _fuse_head(self, nd, pack, bias):
         """Inference plans: `final_layer(relu(bn(deconv(x))))` (pose_resnet.py:245-246) as ONE launch.  When this 1x1
@@ -111,7 +110,7 @@ class InferRewrites:
         node has just been folded into conv3's epilogue (_fold_eval_bn); walks back conv3 <- conv2 <- conv1 and replaces the
         three launches when every link is what the kernel implements.  The projection shortcut of the stage's first block
         stays a launch of its own (its output is the residual)."""
-        if not type(self).fuse_bottleneck or self.with_bwd or self.training or self.es != 2:
+        if not (type(self).fuse_bottleneck and self.opt.fuse_bottleneck) or self.with_bwd or self.training or self.es != 2:
             return False
         conv_of = lambda act: next((n for kind, n in self.nodes if kind == "conv" and n["y"] is act), None)
         users = lambda act: sum(1 for kind, n in self.nodes

@@ -7,6 +7,7 @@ import torch.nn as nn
 
 from . import _lib
 from .engine import PRECISIONS, Plan
+from .options import PlanOptions
 
 
 class ParamArena:
@@ -132,26 +133,29 @@ class HipModule(nn.Module):
             self._lh_arena = ParamArena(self)
         return self._lh_arena
 
-    def plan(self, n, h, w, training=None, backward=None, wgrad_bucket_bytes=None, slot=0, owner=None):
+    def plan(self, n, h, w, training=None, backward=None, wgrad_bucket_bytes=None, slot=0, owner=None, options=None):
         """slot: plans of the same shape with different slots own separate activation buffers and weight packs (several
         batches in flight on different streams: runtime.InferPipeline).
         owner: a step object that REWIRES or replays its plan on its own (runtime.InferStep with uint8 input or on a
         pipeline stream, runtime.TrainStep) names itself here and gets a plan of its own, which the module does NOT keep
         (it lives and dies with the step): ``model(x)`` keeps the (shape, mode) plan without an owner, whose input is
-        always the float NCHW image and whose buffers no asynchronous replay touches."""
+        always the float NCHW image and whose buffers no asynchronous replay touches.
+        options: the planning switches (options.PlanOptions; default: what the environment asks for now).  They are part of the
+        cache key: a plan built under other switches is not handed back for the same shape."""
         training = self.training if training is None else training
+        options = options if options is not None else PlanOptions.from_env()
         backward = training if backward is None else backward
         self.arena()
         if owner is not None:
             # never cached: the step holds the only reference, so dropping the step frees the plan's activation buffers,
             # weight packs and workspaces (a cached owner plan per InferStep made device memory grow without bound)
-            p = Plan(self, n, h, w, self._lh_precision, training=training, backward=backward, wgrad_bucket_bytes=wgrad_bucket_bytes)
+            p = Plan(self, n, h, w, self._lh_precision, training=training, backward=backward, wgrad_bucket_bytes=wgrad_bucket_bytes, options=options)
             p.generation = 0
             return p
-        key = (n, h, w, self._lh_precision, training, backward, wgrad_bucket_bytes) + ((slot,) if slot else ())
+        key = (n, h, w, self._lh_precision, training, backward, wgrad_bucket_bytes, options) + ((slot,) if slot else ())
         p = self._lh_plans.get(key)
         if p is None:
-            p = Plan(self, n, h, w, self._lh_precision, training=training, backward=backward, wgrad_bucket_bytes=wgrad_bucket_bytes)
+            p = Plan(self, n, h, w, self._lh_precision, training=training, backward=backward, wgrad_bucket_bytes=wgrad_bucket_bytes, options=options)
             p.generation = 0
             self._lh_plans[key] = p
         return p

@@ -85,7 +85,7 @@ def _ptr(t):
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
-                 input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None):
+                 input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None):
         self.lib = _lib.load()
         # geometric_aug=(rotation, scale, shift) or a dict that may also carry prob / generator: a random affine warp of the
         # uint8 input per image and step (sample_affine), the joints moved to match (joints_aug) before the target render
@@ -103,9 +103,10 @@ class TrainStep:
         if grad_sync is not None:               # data parallel: one set of measured kernel choices for all ranks
             from . import parallel
             self.plan = parallel.plan_with_shared_tuning(
-                lambda: model.plan(batch, height, width, training=True, backward=True, wgrad_bucket_bytes=grad_sync.bucket_bytes, owner=owner))
+                lambda: model.plan(batch, height, width, training=True, backward=True, wgrad_bucket_bytes=grad_sync.bucket_bytes, owner=owner,
+                                   options=plan_options))
         else:
-            self.plan = model.plan(batch, height, width, training=True, backward=True, owner=owner)
+            self.plan = model.plan(batch, height, width, training=True, backward=True, owner=owner, options=plan_options)
         self.arena = model.arena()
         dev = self.arena.device
         out = self.plan.out_nchw
@@ -354,7 +355,7 @@ class InferStep:
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
-                 flip_test=False, shift_heatmap=True, post_process=False):
+                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
         self.lib = _lib.load()
@@ -362,7 +363,7 @@ class InferStep:
         # slot replays asynchronously on its own stream -- neither may happen to the plan model.forward() uses
         InferStep._serial += 1
         self.plan = model.plan(batch, height, width, training=bn_train, backward=False, slot=slot,
-                               owner=("infer", "u8" if input_u8 else "f32", InferStep._serial))
+                               owner=("infer", "u8" if input_u8 else "f32", InferStep._serial), options=plan_options)
         out = self.plan.out_nchw
         dev = out.device
         # input_u8=(hs, ws): raw uint8 HWC frames; ToTensor / Resize / Normalize run fused on the device (dataset.py:128-159)

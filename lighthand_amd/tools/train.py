@@ -334,6 +334,7 @@ def main(args, train_set=None, val_set=None):
     from lighthand_amd import parallel
     from lighthand_amd.amp import DynamicLossScale
     from lighthand_amd.optim import Adam
+    from lighthand_amd.options import PlanOptions
     from lighthand_amd.runtime import InferStep, TrainStep
 
     # a geometric factor with float samples is refused before any device work (synthetic samples are float tensors)
@@ -386,16 +387,9 @@ def main(args, train_set=None, val_set=None):
         count live in the optimizer, so full and short batches update one Adam state, as in the reference loop."""
         st = steps.get(b)
         if st is None:
-            prev = os.environ.get("LH_AUTOTUNE")
-            os.environ["LH_AUTOTUNE"] = "0"
-            try:
-                st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
-                                          input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo)
-            finally:
-                if prev is None:
-                    os.environ.pop("LH_AUTOTUNE", None)
-                else:
-                    os.environ["LH_AUTOTUNE"] = prev
+            st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
+                                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo,
+                                      plan_options=PlanOptions.from_env().replace(autotune=False))
         return st
 
     val_steps = {}

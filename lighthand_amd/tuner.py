@@ -119,12 +119,6 @@ class Tuner:
         return (d.n, d.hi, d.wi, d.in_pix_stride, d.k_run, d.ho, d.wo, d.sh, d.sw, d.cout, d.OH, d.OW, d.osh, d.osw,
                 d.ooh, d.oow, d.out_pix_stride, d.ntaps, bytes(d.dh)[:d.ntaps], bytes(d.dw)[:d.ntaps])
 
-    @staticmethod
-    def tune_iters():
-        """Timed launches per candidate configuration: 4 at plan build (tuning must stay cheap), more when the shipped
-        database is generated (LH_TUNE_ITERS, tools/make_tune_db.sh: a 20-launch average ranks near-ties reliably)."""
-        return max(1, int(os.environ.get("LH_TUNE_ITERS", "4")))
-
     _flush_buf = {}
 
     def _timed_cold(self, run, warm, iters):
@@ -183,20 +177,61 @@ class Tuner:
             raise _lib.LightHandError(f"lh_igemm_candidates returned {n} entries for a buffer of {type(self)._MAX_CANDS}")
         return buf, n
 
+    def _wgrad_candidates(self, desc, n_out, n_in):
+        """The weight-gradient plans compiled in for this launch: (tile o, tile i, stage rows | depth | splits encoded, workgroups, slab MiB)."""
+        buf = (C.c_int * (5 * type(self)._MAX_CANDS))()
+        n = self.lib.lh_wgrad_candidates(C.byref(desc), n_out, n_in, self.dt, buf, type(self)._MAX_CANDS)
+        if not 0 <= n < type(self)._MAX_CANDS:
+            raise _lib.LightHandError(f"lh_wgrad_candidates returned {n} entries for a buffer of {type(self)._MAX_CANDS}")
+        return [tuple(buf[5 * i:5 * i + 5]) for i in range(n)]
+
+    def _fastest(self, key, cands, apply, run, warm, cold=True, note="", surcharge=None, log=None):
+        """The measurement all tuning sites share.  Every candidate of `cands` (any iterable: _tune_table builds its tables while it is
+        walked) is written into the descriptors by apply(cand) and launched once untimed, then opt.tune_iters launches of run() -- or of
+        the launch apply returned for this candidate -- are timed: one at a time in the cache state of a step (_timed_cold; `warm` = what
+        the preceding kernel wrote), or back to back when `cold` is false.  surcharge(cand) adds milliseconds per launch (work the
+        candidate leaves to another kernel).  Every time goes to LH_TUNE_TIMES and, with LH_TUNE_LOG (`log` overrides), into a line headed
+        by `note` (a string, or note(cand)).  Returns the fastest candidate, the first of equals."""
+        iters, best = self.opt.tune_iters, None
+        for cand in cands:
+            go = apply(cand) or run
+            go()
+            if cold:
+                t = self._timed_cold(go, warm, iters)
+            else:
+                stream = torch.cuda.current_stream()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(stream)
+                for _ in range(iters):
+                    go()
+                b.record(stream)
+                b.synchronize()
+                t = a.elapsed_time(b)
+            if surcharge is not None:
+                t += surcharge(cand) * iters
+            _record_time(key, cand, t)
+            if self.opt.tune_log if log is None else log:
+                print(f"[tune {note(cand) if callable(note) else note}] {cand}: {t / iters * 1e3:7.1f} us", flush=True)
+            if best is None or t < best[0]:
+                best = (t, cand)
+        return best[1]
+
+    def _remember(self, key, choice):
+        """A choice this process made (measured, or the default of a launch with nothing to choose from): what a save writes."""
+        type(self)._TUNE_CACHE[key] = choice
+        type(self)._tune_measured.add(key)
+        return choice
+
     def _tune(self, descs, with_stats=False, addend=None, role=None, gate=None):
         """Measured kernel choice (cdna guide: measure, don't guess): time every compiled-in configuration that fits
         this launch (lh_igemm_candidates) on scratch operands of the real size and write the fastest into the
         descriptors' cfg.  One descriptor = lh_igemm; several = the phases of lh_igemm_phases (one shared choice).
         Results do not depend on the choice (the K-loop order is the same for every tile).  LH_AUTOTUNE=0 keeps the
         library's static default."""
-        if os.environ.get("LH_AUTOTUNE", "1") == "0":
+        if not self.opt.autotune:
             return
         if self._forced is not None and role in self._forced and len(descs) == 1:     # member of a batch group: the group's choice
-            choice = self._forced[role]
-            if isinstance(choice, list):              # mixed launch: a configuration per member (direct 3x3 | the shared tile)
-                choice = choice[self._forced["member"]]
-            for d in descs:
-                d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = choice
+            descs[0].cfg[0], descs[0].cfg[1], descs[0].cfg[2], descs[0].cfg[3] = self._forced[role]
             return
         lead = max(descs, key=lambda d: d.ntaps)
         if lead.ntaps == 0:
@@ -231,8 +266,7 @@ class Tuner:
                 dense = lead.out_pix_stride == lead.cout
                 add = self._scratch("addend", lead.n * lead.OH * lead.OW * lead.out_pix_stride * es + 256) if addend else None
                 amask = self._scratch("amask", lead.n * lead.OH * lead.OW * lead.out_pix_stride * es // 16 + 256) if addend == "masked" and dense else None
-                stream = torch.cuda.current_stream()
-                sp = stream.cuda_stream
+                sp = torch.cuda.current_stream().cuda_stream
                 if len(descs) > 1:
                     arr = (C.POINTER(IgemmDesc) * len(descs))(*[C.pointer(d) for d in descs])
                     parr = (C.c_void_p * len(descs))(*[pk.data_ptr() for pk in packs])
@@ -244,7 +278,7 @@ class Tuner:
                     def run():
                         check(self.lib.lh_igemm(C.byref(lead), src.data_ptr(), packs[0].data_ptr(), dst.data_ptr(), _ptr(add), _ptr(amask), None, None, None,
                                                 _ptr(stats), self.dt, sp), "autotune lh_igemm")
-                run_plain, run_gated, penalty = run, None, 0.0
+                run_gated, penalty = None, 0.0
                 if gate is not None and len(descs) == 1:
                     nout = lead.n * lead.OH * lead.OW * lead.out_pix_stride
                     gx = self._scratch("gate_x", nout * es + 256)
@@ -264,35 +298,20 @@ class Tuner:
                                                       C.byref(gt), self.dt, sp), "autotune lh_igemm_gated")
                     # ms per launch: the reduce pass lh_fuse_bwd keeps (per BatchNorm term: dout and that term's x)
                     penalty = (4.0 if gate[0] == "mask2" else 2.0) * gate[1] / 4.5e12 * 1e3 + 2e-3
-                best = None
-                cold = os.environ.get("LH_TUNE_COLD", "1") != "0"
-                for cfg in cands:
+
+                def gated(cfg):                   # does this candidate take the gate (else the reduce pass stays: the surcharge)?
+                    return run_gated is not None and self._cfg_gateable(cfg, gate[0], gate[1])
+
+                def apply(cfg):
                     for d in descs:
                         d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = cfg
-                    gated = run_gated is not None and self._cfg_gateable(cfg, gate[0], gate[1])
-                    run = run_gated if gated else run_plain
-                    run()
-                    if cold:                  # input = the previous kernel's output (warm), everything else cold
-                        t = self._timed_cold(run, [src[:lead.n * lead.hi * lead.wi * lead.in_pix_stride * es]], type(self).tune_iters())
-                    else:
-                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        a.record(stream)
-                        for _ in range(type(self).tune_iters()):
-                            run()
-                        b.record(stream)
-                        b.synchronize()
-                        t = a.elapsed_time(b)
-                    if run_gated is not None and not gated:
-                        t += penalty * type(self).tune_iters()
-                    _record_time(key, cfg, t)
-                    if os.environ.get("LH_TUNE_LOG"):
-                        print(f"[tune {role or ''} {lead.k_run}x{lead.ntaps}->{lead.cout} M={lead.n * lead.ho * lead.wo} addend={addend} gate={gate and gate[0]}{'' if gate is None else ('+' if gated else '-')}] cfg {cfg}: "
-                              f"{t / type(self).tune_iters() * 1e3:7.1f} us", flush=True)
-                    if best is None or t < best[0]:
-                        best = (t, cfg)
-                hit = best[1]
-            type(self)._TUNE_CACHE[key] = hit
-            type(self)._tune_measured.add(key)
+                    return run_gated if gated(cfg) else None
+                shape = f"{role or ''} {lead.k_run}x{lead.ntaps}->{lead.cout} M={lead.n * lead.ho * lead.wo} addend={addend} gate={gate and gate[0]}"
+                # input = the previous kernel's output (warm), everything else cold
+                hit = self._fastest(key, cands, apply, run, [src[:lead.n * lead.hi * lead.wi * lead.in_pix_stride * es]], cold=self.opt.tune_cold,
+                                    note=lambda cfg: shape + ("" if run_gated is None else "+" if gated(cfg) else "-"),
+                                    surcharge=None if run_gated is None else lambda cfg: 0.0 if gated(cfg) else penalty)
+            self._remember(key, hit)
         for d in descs:
             d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = hit
 
@@ -301,16 +320,14 @@ class Tuner:
         lh_wgrad_candidates, timed on scratch operands; the winner goes into d.cfg[5..7].  The split count changes the
         fp32 summation order (deterministically): the choice is cached per launch signature for the whole process so
         that every plan of a process computes the same sums."""
-        if os.environ.get("LH_AUTOTUNE", "1") == "0":
+        if not self.opt.autotune:
             return
         if self._forced is not None and "wgrad" in self._forced and not tag:
             d.cfg[5], d.cfg[6], d.cfg[7] = self._forced["wgrad"][self._forced["member"]]
             return
         key = ("w", self.dt, self._desc_key(d), n_out, n_in, dy_stride) + tuple(tag)
         hit = type(self)._TUNE_CACHE.get(key) if type(self).force_wgrad is None else None
-        buf = (C.c_int * (5 * 320))()
-        n = self.lib.lh_wgrad_candidates(C.byref(d), n_out, n_in, self.dt, buf, 320)
-        cands = [tuple(buf[5 * i:5 * i + 5]) for i in range(n)]
+        cands = self._wgrad_candidates(d, n_out, n_in)
         if hit is not None and hit != (0, 0, 0) and hit not in [c[:3] for c in cands]:
             hit = None
         if hit is None:
@@ -324,29 +341,15 @@ class Tuner:
                 dys = self._scratch("dy", d.n * d.ho * d.wo * dy_stride * es + 256)
                 slab = self._scratch("wws", (max(c[4] for c in cands) + 1) << 20)
                 grad = self._scratch("stats", grad_floats * 4 + 256)
-                stream = torch.cuda.current_stream()
-                sp = stream.cuda_stream
-                best = None
-                cold = os.environ.get("LH_TUNE_COLD", "1") != "0"
-                for bo, bi, enc, _, _ in cands:
-                    d.cfg[5], d.cfg[6], d.cfg[7] = bo, bi, enc
-                    launch(xs.data_ptr(), dys.data_ptr(), slab.data_ptr(), grad.data_ptr(), sp)
-                    if cold:                  # dy comes from the preceding backward kernel (warm); x was written in the forward pass
-                        t = self._timed_cold(lambda: launch(xs.data_ptr(), dys.data_ptr(), slab.data_ptr(), grad.data_ptr(), sp), [dys[:d.n * d.ho * d.wo * dy_stride * es]], type(self).tune_iters())
-                    else:
-                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        a.record(stream)
-                        for _ in range(type(self).tune_iters()):
-                            launch(xs.data_ptr(), dys.data_ptr(), slab.data_ptr(), grad.data_ptr(), sp)
-                        b.record(stream)
-                        b.synchronize()
-                        t = a.elapsed_time(b)
-                    _record_time(key, (bo, bi, enc), t)
-                    if best is None or t < best[0]:
-                        best = (t, (bo, bi, enc))
-                hit = best[1]
-            type(self)._TUNE_CACHE[key] = hit
-            type(self)._tune_measured.add(key)
+                sp = torch.cuda.current_stream().cuda_stream
+
+                def apply(c):
+                    d.cfg[5], d.cfg[6], d.cfg[7] = c
+                # dy comes from the preceding backward kernel (warm); x was written in the forward pass
+                hit = self._fastest(key, [c[:3] for c in cands], apply, lambda: launch(xs.data_ptr(), dys.data_ptr(), slab.data_ptr(), grad.data_ptr(), sp),
+                                    [dys[:d.n * d.ho * d.wo * dy_stride * es]], cold=self.opt.tune_cold,
+                                    note=f"wgrad {n_in}x{d.ntaps}->{n_out} M={d.n * d.ho * d.wo}")
+            self._remember(key, hit)
         d.cfg[5], d.cfg[6], d.cfg[7] = hit
 
     def _tune_table(self, arr, members, cands):
@@ -355,23 +358,21 @@ class Tuner:
         members' REAL operand buffers filled with random bits for the measurement (cold caches: a deferred group runs long after its
         operands were written).  The choice fixes every member's split count, i.e. the fp32 summation order: cached per table signature."""
         n = len(members)
-        if os.environ.get("LH_AUTOTUNE", "1") == "0":
+        if not self.opt.autotune:
             return cands[0], 0
-        forced = os.environ.get("LH_WGRAD_TABLE_FORCE")       # experiments: "bo,bi,kps,depth,target"
+        forced = self.opt.wgrad_table_force                   # experiments: (bo, bi, kps, depth, target)
         if forced:
-            v = [int(t) for t in forced.split(",")]
-            return tuple(v[:4]), v[4]
+            return forced[:4], forced[4]
         # a table whose whole work is a few tens of microseconds (test-sized models) is not worth a measurement: the library's automatic choice
         work = sum(-(-c.wargs[0]._obj.n * c.wargs[0]._obj.ho * c.wargs[0]._obj.wo // 64) * -(-c.wargs[5] // cands[0][0]) * -(-c.wargs[6] // cands[0][1])
                    * c.wargs[0]._obj.ntaps for c in members)
-        if work < int(os.environ.get("LH_WGRAD_TABLE_TUNE_MIN", "20000")):
+        if work < self.opt.wgrad_table_tune_min:
             return cands[0], 0
         key = ("wt", self.dt, tuple((self._desc_key(c.wargs[0]._obj), c.wargs[4], c.wargs[5], c.wargs[6]) for c in members))
         hit = type(self)._TUNE_CACHE.get(key)
         if hit is not None and tuple(hit[:4]) in cands:
             return tuple(hit[:4]), hit[4]
-        stream = torch.cuda.current_stream()
-        sp = stream.cuda_stream
+        sp = torch.cuda.current_stream().cuda_stream
         bufs, saved = {}, []
         for c in members:
             for t in c.wbufs:
@@ -379,35 +380,35 @@ class Tuner:
         for t in bufs.values():
             saved.append((t, t.clone()))
             t.view(torch.int16).random_(-16000, 16000)
-        best = None
-        try:
+        built = []                           # (info, blob, workspace) of the table being timed
+
+        def tables():
             for cfg in cands:
                 kps = cfg[2]
                 smax = max((c.wargs[0]._obj.n * c.wargs[0]._obj.ho * c.wargs[0]._obj.wo + kps - 1) // kps for c in members)
                 ladder = [0] + sorted({max(256 // kps, -(-smax // q)) for q in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)}, reverse=True)
                 seen = set()
                 for target in ladder:
-                    info, blob, ws = self._build_table(arr, n, cfg, target)
+                    built.clear()
+                    built.extend(self._build_table(arr, n, cfg, target))
+                    info = built[0]
                     sig = (info.n_items, info.n_fold_items, info.workspace_bytes)
-                    if sig in seen:
-                        continue
-                    seen.add(sig)
-                    run = lambda: check(self.lib.lh_wgrad_table_run(blob.data_ptr(), C.byref(info), self.dt, sp), "autotune lh_wgrad_table_run")
-                    run()
-                    t = self._timed_cold(run, [], type(self).tune_iters())
-                    _record_time(key, tuple(cfg) + (info.target_stages if target else 0,), t)
-                    if os.environ.get("LH_WGRAD_TABLE_LOG"):
-                        print(f"[table {n} x wgrad] cfg {cfg} target {target:5d} items {info.n_items:5d} fold {info.n_fold_items:5d} "
-                              f"slab {info.workspace_bytes >> 20:4d} MiB nsplit<= {info.nsplit_max:3d}: {t / type(self).tune_iters() * 1e3:8.1f} us", flush=True)
-                    if best is None or t < best[0]:
-                        best = (t, cfg, info.target_stages if target else 0)
-                    del blob, ws
+                    if sig not in seen:       # another rung of the ladder, the same table
+                        seen.add(sig)
+                        yield tuple(cfg) + (info.target_stages if target else 0,)
+
+        def note(cand):
+            info = built[0]
+            return (f"table {n} x wgrad: items {info.n_items:5d} fold {info.n_fold_items:5d} slab {info.workspace_bytes >> 20:4d} MiB "
+                    f"nsplit<= {info.nsplit_max:3d}")
+        try:
+            hit = self._remember(key, self._fastest(key, tables(), lambda cand: None, lambda: check(
+                self.lib.lh_wgrad_table_run(built[1].data_ptr(), C.byref(built[0]), self.dt, sp), "autotune lh_wgrad_table_run"), [],
+                note=note, log=self.opt.wgrad_table_log))
         finally:
+            built.clear()
             for t, keep in saved:
                 t.copy_(keep)
-        hit = tuple(best[1]) + (best[2],)
-        type(self)._TUNE_CACHE[key] = hit
-        type(self)._tune_measured.add(key)
         return tuple(hit[:4]), hit[4]
 
     def _tune_group(self, nds):
@@ -415,7 +416,7 @@ class Tuner:
         gradient, weight gradient): the merged launch needs a common tile, so the members are not tuned one by one --
         every configuration that fits all of them is timed on the merged launch (scratch operands, cold caches).
         Returns the forced choices _tune / _tune_wgrad pick up while the members compile."""
-        if os.environ.get("LH_AUTOTUNE", "1") == "0" or type(self).force_cfg is not None or type(self).force_wgrad is not None:
+        if not self.opt.autotune or type(self).force_cfg is not None or type(self).force_wgrad is not None:
             return None
         if any(nd["x"].is_image for nd in nds):
             return None
@@ -433,18 +434,14 @@ class Tuner:
                 buf, n = self._igemm_candidates(d)
                 c = {tuple(buf[5 * i:5 * i + 4]) for i in range(n)}
                 common = c if common is None else common & c
-            cands = sorted(c + (0,) for c in (common or ()) if 2 <= c[2] < 10 and (c[0], c[1]) in self._MULTI_TILES)      # 4-wave tiled forms (the multi-problem kernels)
-            # (a 5th element of a candidate marked round 4's MIXED launch -- direct 3x3 bodies inside the merged grid; measured slower, removed in
-            #  round 6: it is always 0 now and stays in the tuple so that the shipped database's entries keep their form)
-            direct = [None] * len(ds)
+            cands = sorted(c for c in (common or ()) if 2 <= c[2] < 10 and (c[0], c[1]) in self._MULTI_TILES)      # 4-wave tiled forms (the multi-problem kernels)
             hit = type(self)._TUNE_CACHE.get(key)
-            if hit is not None and len(hit) == 4:
-                hit = tuple(hit) + (0,)               # entries of earlier rounds: one tiled configuration for all members
+            if hit is not None:
+                # (a 5th element of an entry marked round 4's MIXED launch -- direct 3x3 bodies inside the merged grid; measured slower, removed
+                #  in round 6: the shipped database's entries carry a 0 there, anything else is stale)
+                hit = tuple(hit[:4]) if not any(hit[4:]) else None
             if hit is not None and hit not in cands:
                 hit = None
-
-            def per_member(cfg):
-                return [dc if (cfg[4] and dc is not None) else cfg[:4] for dc in direct]
             if hit is None and cands:
                 arr = (_lib.IgemmCall * len(ds))()
                 warm = []
@@ -462,32 +459,20 @@ class Tuner:
 
                 def run():
                     check(self.lib.lh_igemm_multi(arr, len(ds), self.dt, sp), "group autotune lh_igemm_multi")
-                best = None
-                for cfg in cands:
-                    for d, mc in zip(ds, per_member(cfg)):
-                        d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = mc
-                    run()
-                    t = self._timed_cold(run, warm, type(self).tune_iters())
-                    _record_time(key, cfg, t)
-                    if os.environ.get("LH_TUNE_LOG"):
-                        print(f"[tune {role or ''} {lead.k_run}x{lead.ntaps}->{lead.cout} M={lead.n * lead.ho * lead.wo} addend={addend}] cfg {cfg}: "
-                              f"{t / type(self).tune_iters() * 1e3:7.1f} us", flush=True)
-                    if best is None or t < best[0]:
-                        best = (t, cfg)
-                hit = best[1]
-                type(self)._TUNE_CACHE[key] = hit
-                type(self)._tune_measured.add(key)
+
+                def apply(cfg):
+                    for d in ds:
+                        d.cfg[0], d.cfg[1], d.cfg[2], d.cfg[3] = cfg
+                hit = self._remember(key, self._fastest(key, cands, apply, run, warm, note=f"group {role} x {len(ds)}"))
             if hit is not None:
-                forced[role] = per_member(hit) if hit[4] else hit[:4]
+                forced[role] = hit
         # weight gradient: common (tile, stage rows, ring depth); per member the plan with the fewest workgroups -- the batch
         # fills the machine, a member need not
         if self.with_bwd:
             per, common = [], None
             for (d, _), nd in zip(descs, nds):
                 y, wt = nd["y"], self.params[nd["w"] + ".weight"]
-                buf = (C.c_int * (5 * 320))()
-                n = self.lib.lh_wgrad_candidates(C.byref(d), y.c, wt.shape[1], self.dt, buf, 320)
-                cs = [tuple(buf[5 * i:5 * i + 5]) for i in range(n)]
+                cs = self._wgrad_candidates(d, y.c, wt.shape[1])
                 per.append(cs)
                 keys = {(c[0], c[1], (c[2] >> 16) & 255, (c[2] >> 24) & 255) for c in cs if c[0] <= 128 and c[1] <= 128}
                 common = keys if common is None else common & keys
@@ -518,22 +503,19 @@ class Tuner:
 
                 def runw():
                     check(self.lib.lh_wgrad_fused_multi(arr, len(nds), self.dt, sp), "group autotune lh_wgrad_fused_multi")
-                best = None
-                for tk in sorted(common):
-                    for policy in (0, 1):                 # fewest workgroups per member / next larger split count
-                        encs = []
-                        for cs in per:
-                            opts = sorted((c for c in cs if (c[0], c[1], (c[2] >> 16) & 255, (c[2] >> 24) & 255) == tk), key=lambda c: c[3])
-                            encs.append(opts[min(policy, len(opts) - 1)][2])
-                        for (d, _), enc in zip(descs, encs):
-                            d.cfg[5], d.cfg[6], d.cfg[7] = tk[0], tk[1], enc
-                        runw()
-                        t = self._timed_cold(runw, warm, type(self).tune_iters())
-                        if best is None or t < best[0]:
-                            best = (t, tk + (tuple(encs),))
-                hit = best[1]
-                type(self)._TUNE_CACHE[key] = hit
-                type(self)._tune_measured.add(key)
+
+                def member_encs(tk, policy):              # per member: the plan of this tile with the fewest workgroups / the next larger split count
+                    encs = []
+                    for cs in per:
+                        opts = sorted((c for c in cs if (c[0], c[1], (c[2] >> 16) & 255, (c[2] >> 24) & 255) == tk), key=lambda c: c[3])
+                        encs.append(opts[min(policy, len(opts) - 1)][2])
+                    return tuple(encs)
+
+                def apply(cand):
+                    for (d, _), enc in zip(descs, cand[4]):
+                        d.cfg[5], d.cfg[6], d.cfg[7] = cand[0], cand[1], enc
+                hit = self._remember(key, self._fastest(key, [tk + (member_encs(tk, policy),) for tk in sorted(common) for policy in (0, 1)], apply, runw, warm,
+                                                        note=f"group wgrad x {len(nds)}"))
             if hit is not None:
                 forced["wgrad"] = [(hit[0], hit[1], enc) for enc in hit[4]]
         return forced

@@ -2,7 +2,6 @@
 a group, a split count per layer: lh_wgrad_table_run) and same-shape merging of what is left.  A mixin of ``engine.Plan`` (split out of
 engine.py in round 6).  Reference: loss.backward(), src/utils/method.py:182."""
 import ctypes as C
-import os
 
 import torch
 
@@ -100,7 +99,7 @@ class WgradSchedule:
                 units[-1].append(c)
             else:
                 units.append([c])
-        big = os.environ.get("LH_WGRAD_TABLE_BIG", "1") != "0"
+        big = self.opt.wgrad_table_big
 
         def cls(u):
             c = u[0]
@@ -119,7 +118,7 @@ class WgradSchedule:
         # layer some operand re-reads; a larger tile multiplies padding for the small layer, which streams its operands anyway) -- one
         # launch + fold less per straggler (R50: the head's 1x1, the projection of stage 2)
         order = [(256, 256), (128, 128), (64, 64)]
-        for k in order if os.environ.get("LH_WGRAD_TABLE_STRAGGLERS", "1") != "0" else ():
+        for k in order if self.opt.wgrad_table_stragglers else ():
             if k in groups and len(groups[k]) == 1:
                 i = order.index(k)
                 hosts = [h for h in order[i + 1:] + order[:i][::-1] if h in groups and len(groups[h]) >= 2]

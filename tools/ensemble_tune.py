@@ -2,7 +2,7 @@
 """Ensemble of several tuning sessions: LH_TUNE_TIMES files (one line per timed candidate: key, choice, ms) of N sessions -- normally N boxes
 of the pool, which favour different candidates among near-ties -- are added per (key, choice); the database entry of a key becomes the choice
 with the smallest SUM over the sessions that timed it in all of them.
-usage: ensemble_tune.py out_db times1.txt times2.txt ...   (keys of _tune / _tune_wgrad / _tune_table; group keys of HRNet are not logged)"""
+usage: ensemble_tune.py out_db times1.txt times2.txt ...   (every key Tuner._fastest times: _tune / _tune_wgrad / _tune_table / _tune_group)"""
 import ast
 import collections
 import sys
