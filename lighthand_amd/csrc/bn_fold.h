@@ -1,4 +1,4 @@
-// The BatchNorm statistics fold and finalize arithmetic of the finalize kernels (bn.hip).
+// The BatchNorm statistics fold and finalize arithmetic of the finalize kernels (bn_stats.hip).
 #pragma once
 #include "common.h"
 

@@ -578,7 +578,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
 
     def _attach_l2_touch(self):
         """Training plans: an elementwise BatchNorm / ReLU pass (lh_fuse_fwd) that is followed on its stream by a tiled
-        convolution warms that convolution's weight pack in L2 at its tail (lh_fuse_desc.l2_touch; bn.hip lh_l2_touch).  Every
+        convolution warms that convolution's weight pack in L2 at its tail (lh_fuse_desc.l2_touch; bn_common.h lh_l2_touch).  Every
         workgroup of such a convolution walks the same weight slab stage by stage, at once: each stage waits for lines no XCD has
         seen yet (profiles/r05_ingest_ladder.txt, sitting 6: the complete K loop of the stage-3 3x3 takes 21.3 us, 19.1 us with the
         pack in L2).  Only where the pack fits beside the pass's own stream in the 4 MB L2 of an XCD (LH_L2_TOUCH_MAX_MB, default 3;

@@ -15,10 +15,10 @@ NOT plan options -- process-level names, read where they are used, once per proc
   LH_DIST_BACKEND      parallel.py: the torch.distributed backend (default nccl on a HIP device, else gloo).
   RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT    parallel.py, tools/train.py: the torchrun rendezvous.
 and the switches the C library reads with getenv() itself:
-  LH_POOL_STRIP        bn.hip: rows per strip of the BatchNorm + ReLU + max-pool forward (0: the window-per-thread kernel).
-  LH_POOL_BLOCK        bn.hip: 0 runs the gated max-pool backward on the pixel-per-thread kernel.
-  LH_BN_EXP            bn.hip: bit flags of the cache-policy / traversal experiments of the streaming BatchNorm passes.
-  LH_FOLD_IN_APPLY     bn.hip: set (to anything), the backward apply pass no longer folds the partial sums itself.
+  LH_POOL_STRIP        pool.hip: rows per strip of the BatchNorm + ReLU + max-pool forward (0: the window-per-thread kernel).
+  LH_POOL_BLOCK        pool.hip: 0 runs the gated max-pool backward on the pixel-per-thread kernel.
+  LH_BN_EXP            bn_common.h: bit flags of the cache-policy / traversal experiments of the streaming BatchNorm passes.
+  LH_FOLD_IN_APPLY     fuse_bwd.hip: set (to anything), the backward apply pass no longer folds the partial sums itself.
   LH_DENSE_TILES       igemm_ring.hip: 0 withdraws the dense tile configurations from the candidates.
   LH_PW_OCC            igemm_pw_kernel.h: cap on the pointwise kernel's workgroups per compute unit (default 4).
   LH_WGRAD_TABLE_XCD   wgrad.hip: 0 orders a table's work items longest first without dealing them over the XCDs.

@@ -354,7 +354,7 @@ def test_bn_fuse_fwd_bwd_fp32(mode):
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("mode", ["plain", "residual", "two_bn", "up"])
 def test_bn_backward_fold_in_apply_equals_fold_launch(mode, precision, monkeypatch):
-    """Small tensors: the BN-backward apply pass folds the reduce pass's partial sums itself (bn.hip fold_coef_block, no
+    """Small tensors: the BN-backward apply pass folds the reduce pass's partial sums itself (fuse_bwd.hip fold_coef_block, no
     coefficient launch); LH_FOLD_IN_APPLY=0 forces the separate fold launch.  Both paths sum the same partial sums in fp64,
     in two fixed orders: input gradients and d(gamma) / d(beta) agree to the last fp32 digits (pose_resnet.py:45-47,
     pose_hrnet.py:247-265 are the nodes this serves)."""
