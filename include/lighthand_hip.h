@@ -483,6 +483,28 @@ int lh_gaussian_target_alt(const float* points, int pstride, const float* patch,
 size_t lh_mse_workspace_bytes(long numel);
 int lh_mse_heatmap(const float* pred, const float* target, long numel, float* loss, float* grad,
                    const float* grad_scale, void* workspace, void* stream);
+/* Opt-in extensions without a reference oracle (the reference computes target_weight, src/tools/dataset.py:171-186, and
+ * never applies it; it has no hard-keypoint mining): the formulas are those of the SimpleBaseline / HRNet code line.
+ *
+ * lh_gaussian_target with upstream's target_weight: vis = optional fp32 visibility per joint, read at vis[i * vstride] for
+ * joint i of b*j (NULL = 1); weight fp32 [b][j] = (vis > 0.5 ? vis : 0) * in_frame, in_frame = some part of the patch lies
+ * inside the map (the negation of lh_gaussian_target's skip test).  target = lh_gaussian_target's, bit for bit, where
+ * weight > 0 and a zero map otherwise (upstream's `if v > 0.5:`); with vis == NULL it is lh_gaussian_target's everywhere. */
+int lh_gaussian_target_w(const float* joints, int jstride, const float* vis, int vstride, const float* patch, int radius,
+                         float* target, float* weight, int b, int j, int size, void* stream);
+/* JointsMSELoss(use_target_weight=True) (topk == 0) and JointsOHKMMSELoss (1 <= topk <= j).  pred / target / grad fp32
+ * [b][j][hw], weight fp32 [b][j] or NULL (ones), joint_loss optional fp32 [b][j], grad optional, grad_scale an optional
+ * device scalar read on the device like lh_mse_heatmap's.  Per plane, fp64 in a fixed order (no atomics: every call gives the
+ * same bits): S = w^2 * sum (float)(d * d), d = p - g in fp32; joint_loss = 0.5 * S / hw.
+ * topk == 0: loss = 0.5 * sum S / (b*j*hw), grad = d * (w * w * gs), gs = (grad_scale ? *grad_scale : 1) / (float)(b*j*hw):
+ *   one pass over pred / target plus one small launch; with weight == NULL grad is lh_mse_heatmap's bit for bit.
+ * topk >= 1: per sample the topk largest joint_loss values are selected (fp32 values, the lower joint index among equals,
+ *   a NaN first); loss = (1/b) sum_b (1/topk) sum_selected joint_loss; grad = d * (w * w * gs_k) on the selected planes,
+ *   gs_k = scale / (float)(b*topk*hw), and exactly 0.f on the others.  Three launches: plane sums, select + loss, gradient.
+ * Buffers 16-byte aligned, hw % 4 == 0 (LH_ERR_ARG otherwise); workspace >= lh_joints_mse_workspace_bytes(b, j). */
+size_t lh_joints_mse_workspace_bytes(int b, int j);
+int lh_joints_mse(const float* pred, const float* target, const float* weight, int b, int j, int hw, int topk, float* loss,
+                  float* joint_loss, float* grad, const float* grad_scale, void* workspace, void* stream);
 /* get_max_preds: src/utils/loss.py:327-355 (+ the x4 of src/utils/method.py:157,176-178 via
  * `scale`).  heatmaps fp32 NCHW [b*j][h*w] -> preds fp32 [b*j][2], maxvals fp32 [b*j],
  * idx int32 [b*j] (first-occurrence arg-max, NaN counts as maximum). */

@@ -166,6 +166,9 @@ SIGNATURES = {
     "lh_gaussian_target_alt": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "lh_mse_workspace_bytes": (_SZ, [_L]),
     "lh_mse_heatmap": (_I, [_P, _P, _L, _P, _P, _P, _P, _P]),
+    "lh_gaussian_target_w": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "lh_joints_mse_workspace_bytes": (_SZ, [_I, _I]),
+    "lh_joints_mse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "lh_heatmap_argmax": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _P]),
     "lh_channel_sum_workspace_bytes": (C.c_size_t, [_I]),
     "lh_channel_sum_nchw": (_I, [_P, _I, _I, _I, _P, _P, _P]),

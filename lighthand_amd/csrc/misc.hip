@@ -763,6 +763,43 @@ extern "C" int lh_gaussian_target(const float* joints, int jstride, const float*
     return LH_OK;
 }
 
+// The same render with upstream's target_weight (src/tools/dataset.py:171-186, `if v > 0.5:`): weight = visibility x "some part
+// of the patch lies inside the map", and a joint of weight 0 gets a zero map.  A sibling of gaussian_target_kernel, which keeps
+// its ISA; the thread that owns pixel (0, 0) of a plane writes that plane's weight.
+__global__ void gaussian_target_w_kernel(const float* joints, int jstride, const float* vis, int vstride, const float* patch,
+                                         int radius, float* target, float* weight, int bj, int size) {
+    const long total = (long)bj * size * size;
+    const int pw = 2 * radius + 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % size);
+        const long t = i / size;
+        const int y = (int)(t % size);
+        const long j = t / size;
+        const float jx = joints[j * jstride], jy = joints[j * jstride + 1];
+        const int mx = (int)(jx * 0.25f + 0.5f), my = (int)(jy * 0.25f + 0.5f);
+        const int x0 = mx - radius, y0 = my - radius, x1 = mx + radius + 1, y1 = my + radius + 1;
+        const bool skip = x0 >= size || y0 >= size || x1 < 0 || y1 < 0;
+        const float v = vis ? vis[j * vstride] : 1.f;
+        const float w = (v > 0.5f ? v : 0.f) * (skip ? 0.f : 1.f);
+        float out = 0.f;
+        if (w > 0.f && x >= x0 && x < x1 && y >= y0 && y < y1) out = patch[(y - y0) * pw + (x - x0)];
+        target[i] = out;
+        if (x == 0 && y == 0) weight[j] = w;
+    }
+}
+
+extern "C" int lh_gaussian_target_w(const float* joints, int jstride, const float* vis, int vstride, const float* patch, int radius,
+                                    float* target, float* weight, int b, int j, int size, void* stream) {
+    LH_REQUIRE(joints && patch && target && weight && jstride >= 2 && (!vis || vstride >= 1) && b > 0 && j > 0 && size > 0 && radius >= 0,
+               "lh_gaussian_target_w: bad arguments");
+    const long total = (long)b * j * size * size;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(gaussian_target_w_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, joints, jstride, vis, vstride, patch,
+                       radius, target, weight, b * j, size);
+    LH_LAUNCH_CHECK("gaussian_target_w launch");
+    return LH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ MSE loss
 constexpr int MSE_BLOCKS = 512;
 
@@ -818,6 +855,150 @@ extern "C" int lh_mse_heatmap(const float* pred, const float* target, long numel
                        (double*)workspace);
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, blocks, numel, loss);
     LH_LAUNCH_CHECK("mse launch");
+    return LH_OK;
+}
+
+// ---- JointsMSELoss(use_target_weight=True) and JointsOHKMMSELoss of the SimpleBaseline / HRNet code line (lh_joints_mse).
+// One workgroup per joint plane: the plane's sum S = w^2 * sum (float)(d * d) in fp64, in a fixed order (the reduction of
+// mse_partial_kernel: per-thread fp64 accumulator, wave-64 shuffle, four LDS slots; no atomics, so every replay gives the same
+// bits).  Without mining the gradient coefficient w * w * gs is known before any sum, so the same pass writes the gradient
+// (GRAD); with mining the pass only sums, joints_ohkm_select_kernel picks the planes and joints_ohkm_grad_kernel writes them.
+__device__ __forceinline__ double plane_reduce(double acc, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(256) void joints_mse_plane_kernel(const float* pred, const float* target, const float* weight, int hw,
+                                                              long numel, float* grad, const float* grad_scale, double* plane_sum,
+                                                              float* joint_loss) {
+    __shared__ double red[4];
+    const long base = (long)blockIdx.x * hw;
+    const float w = weight ? weight[blockIdx.x] : 1.f;
+    float coef = 0.f;
+    if (GRAD) {
+        const float gs = (grad_scale ? *grad_scale : 1.f) / (float)numel;
+        coef = w * w * gs;
+    }
+    const float4* p4 = reinterpret_cast<const float4*>(pred + base);
+    const float4* t4 = reinterpret_cast<const float4*>(target + base);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < hw / 4; i += 256) {
+        const float4 p = p4[i], t = t4[i];
+        const float4 d = {p.x - t.x, p.y - t.y, p.z - t.z, p.w - t.w};
+        acc += (double)(d.x * d.x) + (double)(d.y * d.y) + (double)(d.z * d.z) + (double)(d.w * d.w);
+        if (GRAD) reinterpret_cast<float4*>(grad + base)[i] = float4{d.x * coef, d.y * coef, d.z * coef, d.w * coef};
+    }
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) {
+        const double s = (double)w * (double)w * sum;
+        plane_sum[blockIdx.x] = s;
+        if (joint_loss) joint_loss[blockIdx.x] = (float)(0.5 * s / (double)hw);
+    }
+}
+
+__global__ __launch_bounds__(256) void joints_mse_final_kernel(const double* plane_sum, int bj, long numel, float* loss) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < bj; i += 256) acc += plane_sum[i];
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) *loss = (float)(0.5 * sum / (double)numel);
+}
+
+// true when joint k (loss a) is picked before joint i (loss b): larger loss first, the lower joint index among equals; a NaN
+// loss ranks first (lh_heatmap_argmax's rule), so it reaches the loss value instead of hiding behind the selection
+__device__ __forceinline__ bool ohkm_before(float a, int k, float b, int i) {
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return an && (!bn || k < i);
+    return a > b || (a == b && k < i);
+}
+
+// One workgroup, thread t owns planes t, t + 256, ...: the rank of the plane's joint among its sample's fp32 per-joint losses
+// (j comparisons), the coefficient w * w * gs_k and the selection flag for the gradient pass, and
+// loss = (1/b) sum_b (1/topk) sum_selected 0.5 * S / hw accumulated in fp64 in a fixed order.
+__global__ __launch_bounds__(256) void joints_ohkm_select_kernel(const double* plane_sum, const float* weight, int b, int j, int hw,
+                                                                int topk, const float* grad_scale, float* coef, int* selected,
+                                                                float* loss) {
+    __shared__ double red[4];
+    const float gs = (grad_scale ? *grad_scale : 1.f) / (float)((long)b * topk * hw);
+    double acc = 0.0;
+    for (int idx = threadIdx.x; idx < b * j; idx += 256) {
+        const int i = idx % j;
+        const double* ps = plane_sum + (idx - i);
+        const double li = 0.5 * ps[i] / (double)hw;
+        const float fi = (float)li;
+        int rank = 0;
+        for (int k = 0; k < j; ++k)
+            if (k != i && ohkm_before((float)(0.5 * ps[k] / (double)hw), k, fi, i)) ++rank;
+        const bool sel = rank < topk;
+        const float w = weight ? weight[idx] : 1.f;
+        coef[idx] = sel ? w * w * gs : 0.f;
+        selected[idx] = sel ? 1 : 0;
+        if (sel) acc += li;
+    }
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) *loss = (float)(sum / ((double)b * (double)topk));
+}
+
+// planes that were not selected are not read: their gradient is exactly 0.f
+__global__ __launch_bounds__(256) void joints_ohkm_grad_kernel(const float* pred, const float* target, int hw, const float* coef,
+                                                              const int* selected, float* grad) {
+    const long base = (long)blockIdx.x * hw;
+    float4* g4 = reinterpret_cast<float4*>(grad + base);
+    if (!selected[blockIdx.x]) {
+        for (int i = threadIdx.x; i < hw / 4; i += 256) g4[i] = float4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const float c = coef[blockIdx.x];
+    const float4* p4 = reinterpret_cast<const float4*>(pred + base);
+    const float4* t4 = reinterpret_cast<const float4*>(target + base);
+    for (int i = threadIdx.x; i < hw / 4; i += 256) {
+        const float4 p = p4[i], t = t4[i];
+        g4[i] = float4{(p.x - t.x) * c, (p.y - t.y) * c, (p.z - t.z) * c, (p.w - t.w) * c};
+    }
+}
+
+// workspace: fp64 plane sums [b][j], then the fp32 coefficient table and the int32 selection flags of the mining pass
+extern "C" size_t lh_joints_mse_workspace_bytes(int b, int j) {
+    return b > 0 && j > 0 ? (size_t)b * j * (sizeof(double) + sizeof(float) + sizeof(int)) : 0;
+}
+
+extern "C" int lh_joints_mse(const float* pred, const float* target, const float* weight, int b, int j, int hw, int topk, float* loss,
+                             float* joint_loss, float* grad, const float* grad_scale, void* workspace, void* stream) {
+    LH_REQUIRE(pred && target && loss && workspace && b > 0 && j > 0 && hw > 0, "lh_joints_mse: bad arguments");
+    LH_REQUIRE(topk >= 0 && topk <= j, "lh_joints_mse: topk %d outside 0..%d (the joints of a sample)", topk, j);
+    LH_REQUIRE(hw % 4 == 0, "lh_joints_mse: the plane size %d must be a multiple of 4", hw);
+    LH_REQUIRE((long)b * j < (1L << 31), "lh_joints_mse: too many planes");
+    LH_REQUIRE(((uintptr_t)pred % 16 == 0) && ((uintptr_t)target % 16 == 0) && (!grad || (uintptr_t)grad % 16 == 0) &&
+               ((uintptr_t)workspace % 16 == 0), "lh_joints_mse: buffers must be 16-byte aligned");
+    const int bj = b * j;
+    const long numel = (long)bj * hw;
+    double* plane_sum = (double*)workspace;
+    float* coef = (float*)(plane_sum + bj);
+    int* selected = (int*)(coef + bj);
+    hipStream_t s = (hipStream_t)stream;
+    if (topk == 0) {
+        if (grad)
+            hipLaunchKernelGGL((joints_mse_plane_kernel<true>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel, grad,
+                               grad_scale, plane_sum, joint_loss);
+        else
+            hipLaunchKernelGGL((joints_mse_plane_kernel<false>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel,
+                               (float*)nullptr, grad_scale, plane_sum, joint_loss);
+        hipLaunchKernelGGL(joints_mse_final_kernel, dim3(1), dim3(256), 0, s, (const double*)plane_sum, bj, numel, loss);
+        LH_LAUNCH_CHECK("joints_mse launch");
+        return LH_OK;
+    }
+    hipLaunchKernelGGL((joints_mse_plane_kernel<false>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel, (float*)nullptr,
+                       grad_scale, plane_sum, joint_loss);
+    hipLaunchKernelGGL(joints_ohkm_select_kernel, dim3(1), dim3(256), 0, s, (const double*)plane_sum, weight, b, j, hw, topk, grad_scale,
+                       coef, selected, loss);
+    if (grad)
+        hipLaunchKernelGGL(joints_ohkm_grad_kernel, dim3(bj), dim3(256), 0, s, pred, target, hw, (const float*)coef, (const int*)selected,
+                           grad);
+    LH_LAUNCH_CHECK("joints_ohkm launch");
     return LH_OK;
 }
 

@@ -3,7 +3,8 @@
 Mirrors the three free functions the reference's training loop uses
 (``CustomDataset.generate_target`` src/tools/dataset.py:165-212, ``JointsMSELoss``
 src/utils/loss.py:306-325, ``get_max_preds`` src/utils/loss.py:327-355) with the same
-names, arguments and error behaviour; the arithmetic runs in liblighthand_hip.
+names, arguments and error behaviour; the arithmetic runs in liblighthand_hip.  ``WeightedJointsMSELoss`` and the
+``return_weight`` option of the renderers are opt-in extensions (upstream's target_weight and OHKM loss).
 """
 import numpy as np
 import torch
@@ -41,9 +42,12 @@ def _patch_on(device):
     return _patch_cache[key]
 
 
-def render_targets(joints, size=HEATMAP_SIZE, out=None):
+def render_targets(joints, size=HEATMAP_SIZE, out=None, return_weight=False):
     """joints: device tensor [B, J, >=2] (pixel coordinates in the 256x256 frame) ->
-    float32 [B, J, size, size] Gaussian targets (sigma 2, 13x13 patch, clipped assignment)."""
+    float32 [B, J, size, size] Gaussian targets (sigma 2, 13x13 patch, clipped assignment).
+    ``return_weight=True`` (an extension: the reference computes this weight and never uses it) returns
+    ``(target, target_weight [B, J, 1])``: column 2 of ``joints``, when present, is the visibility, weight = (vis > 0.5 ? vis : 0)
+    x (some part of the patch lies inside the map), and a joint of weight 0 gets a zero map."""
     if not joints.is_cuda:
         raise _lib.LightHandError("render_targets needs a HIP device tensor")
     j = joints.to(torch.float32).contiguous()
@@ -51,14 +55,25 @@ def render_targets(joints, size=HEATMAP_SIZE, out=None):
     if out is None:
         out = torch.empty(b, nj, size, size, dtype=torch.float32, device=j.device)
     patch = _patch_on(j.device)
+    if return_weight:
+        weight = torch.empty(b, nj, 1, dtype=torch.float32, device=j.device)
+        vis = j.data_ptr() + 8 if stride >= 3 else None
+        check(_lib.load().lh_gaussian_target_w(j.data_ptr(), stride, vis, stride, patch.data_ptr(), RADIUS, out.data_ptr(),
+                                               weight.data_ptr(), b, nj, size, _stream()), "lh_gaussian_target_w")
+        return out, weight
     check(_lib.load().lh_gaussian_target(j.data_ptr(), stride, patch.data_ptr(), RADIUS, out.data_ptr(), b, nj, size, _stream()),
           "lh_gaussian_target")
     return out
 
 
-def generate_target(joints, device="cuda"):
+def generate_target(joints, device="cuda", return_weight=False):
     """Per-sample form with the reference's signature: joints [21, >=2] (array-like) ->
-    torch.float32 [21, 64, 64] (returned on the CPU like the reference's dataset method)."""
+    torch.float32 [21, 64, 64] (returned on the CPU like the reference's dataset method).  ``return_weight=True`` returns
+    ``(target, target_weight [21, 1])`` as upstream's generate_target does (column 2 = visibility when present)."""
+    if return_weight:
+        j = torch.as_tensor(np.asarray(joints, dtype=np.float32)[:, :3].copy()).to(device)
+        target, weight = render_targets(j[None], return_weight=True)
+        return target[0].cpu(), weight[0].cpu()
     j = torch.as_tensor(np.asarray(joints, dtype=np.float32)[:, :2].copy()).to(device)
     return render_targets(j[None])[0].cpu()
 
@@ -137,6 +152,58 @@ class JointsMSELoss(nn.Module):
         if not output.is_cuda:
             raise _lib.LightHandError("JointsMSELoss runs on the HIP device only")
         return _MseFn.apply(output, target)
+
+
+class _WeightedMseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target, target_weight, topk):
+        lib = _lib.load()
+        p = output.detach().to(torch.float32).contiguous()
+        g = target.detach().to(torch.float32).contiguous()
+        if p.shape != g.shape or p.dim() < 3:
+            raise ValueError(f"prediction {tuple(p.shape)} and target {tuple(g.shape)} must be one [B, J, ...] shape")
+        b, j = p.shape[:2]
+        hw = p[0, 0].numel()
+        w = None
+        if target_weight is not None:
+            w = target_weight.detach().to(torch.float32).contiguous()
+            if w.numel() != b * j:
+                raise ValueError(f"target_weight {tuple(w.shape)} does not hold one weight per joint plane ({b} x {j})")
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        joint_loss = torch.empty(b, j, dtype=torch.float32, device=p.device)
+        grad = torch.empty_like(p)
+        ws = torch.empty(lib.lh_joints_mse_workspace_bytes(b, j), dtype=torch.uint8, device=p.device)
+        check(lib.lh_joints_mse(p.data_ptr(), g.data_ptr(), None if w is None else w.data_ptr(), b, j, hw, int(topk), loss.data_ptr(),
+                                joint_loss.data_ptr(), grad.data_ptr(), None, ws.data_ptr(), _stream()), "lh_joints_mse")
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(joint_loss)
+        return loss, joint_loss
+
+    @staticmethod
+    def backward(ctx, gout, _gjoint):
+        (grad,) = ctx.saved_tensors
+        return grad * gout, None, None, None
+
+
+class WeightedJointsMSELoss(nn.Module):
+    """An extension without a reference oracle (the reference computes ``target_weight`` and drops it; ``JointsMSELoss`` above
+    stays its drop-in): the SimpleBaseline / HRNet code line's ``JointsMSELoss(use_target_weight=True)`` -- every joint plane's
+    prediction and target are multiplied by its weight, loss = 0.5 * mean over all elements -- and, with ``topk`` >= 1, its
+    ``JointsOHKMMSELoss``: per sample only the ``topk`` joints with the largest loss count, loss = mean over samples of their mean.
+    ``target_weight``: [B, J, 1] / [B, J] or None (ones).  ``joint_loss`` holds the per-joint losses [B, J] of the last call."""
+
+    def __init__(self, topk=0):
+        super().__init__()
+        if topk < 0:
+            raise ValueError("topk must be >= 0 (0 = no hard-keypoint mining)")
+        self.topk = int(topk)
+        self.joint_loss = None
+
+    def forward(self, output, target, target_weight=None):
+        if not output.is_cuda:
+            raise _lib.LightHandError("WeightedJointsMSELoss runs on the HIP device only")
+        loss, self.joint_loss = _WeightedMseFn.apply(output, target, target_weight, self.topk)
+        return loss
 
 
 def max_preds_device(heatmaps, scale=1.0, post_process=False):

@@ -85,7 +85,8 @@ def _ptr(t):
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
-                 input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None):
+                 input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
+                 use_target_weight=False, ohkm_topk=0):
         self.lib = _lib.load()
         # geometric_aug=(rotation, scale, shift) or a dict that may also carry prob / generator: a random affine warp of the
         # uint8 input per image and step (sample_affine), the joints moved to match (joints_aug) before the target render
@@ -123,6 +124,24 @@ class TrainStep:
         self.joints_aug = torch.zeros_like(self.joints) if geometric_aug is not None else None
         self.target = torch.zeros_like(out)
         self.targets_from_joints = targets_from_joints
+        # use_target_weight / ohkm_topk (opt-in extensions, off = the step as it was: the same launches and buffers): the loss is
+        # lh_joints_mse in place of lh_mse_heatmap.  use_target_weight renders the target with lh_gaussian_target_w: a joint
+        # that is invisible (column 2 of the caller's joints, kept in `vis`; ones when the caller passes two columns) or whose
+        # patch left the map -- tested on the WARPED joints under geometric_aug -- gets weight 0 and a zero map, so it
+        # contributes neither loss nor gradient.  ohkm_topk = K keeps, per sample, the K joints with the largest loss (weights
+        # of 1 without use_target_weight).  Data parallel needs no new collective: the loss normaliser (b*j*hw, or b*K*hw
+        # with mining) is a constant every rank shares, so averaging the ranks' gradients stays the gradient of the mean loss.
+        self.use_target_weight, self.ohkm_topk = bool(use_target_weight), int(ohkm_topk)
+        if self.use_target_weight and not targets_from_joints:
+            raise LightHandError("use_target_weight needs targets_from_joints=True: the weight is computed where the target is rendered")
+        if not 0 <= self.ohkm_topk <= out.shape[1]:
+            raise LightHandError(f"ohkm_topk={ohkm_topk} must lie in 0..{out.shape[1]} (the joints of a sample)")
+        self.vis = self.target_weight = self.joint_loss = self._jmse_ws = None
+        if self.use_target_weight or self.ohkm_topk:
+            self.vis = torch.ones(batch, out.shape[1], dtype=torch.float32, device=dev)
+            self.target_weight = torch.ones(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
+            self.joint_loss = torch.zeros(batch, out.shape[1], dtype=torch.float32, device=dev)
+            self._jmse_ws = torch.empty(self.lib.lh_joints_mse_workspace_bytes(batch, out.shape[1]), dtype=torch.uint8, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
         self.maxvals = torch.zeros(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
@@ -171,6 +190,11 @@ class TrainStep:
             check(self.lib.lh_affine_points(self.joints.data_ptr(), 2, self.plan.warp_fwd.data_ptr(), self.joints_aug.data_ptr(), 2, b, j,
                                             stream), "lh_affine_points")
             joints = self.joints_aug
+        if self.use_target_weight:
+            check(self.lib.lh_gaussian_target_w(joints.data_ptr(), 2, self.vis.data_ptr(), 1, self._patch.data_ptr(), heatmap.RADIUS,
+                                                self.target.data_ptr(), self.target_weight.data_ptr(), b, j, hs, stream),
+                  "lh_gaussian_target_w")
+            return
         check(self.lib.lh_gaussian_target(joints.data_ptr(), 2, self._patch.data_ptr(), heatmap.RADIUS,
                                           self.target.data_ptr(), b, j, hs, stream), "lh_gaussian_target")
 
@@ -189,8 +213,14 @@ class TrainStep:
             # the arg-max decode only reads the heat-maps: on a side stream under the loss kernels
             aux = self._aux_stream = getattr(self, "_aux_stream", None) or torch.cuda.Stream()
             aux.wait_event(torch.cuda.current_stream().record_event())
-        check(self.lib.lh_mse_heatmap(out.data_ptr(), self.target.data_ptr(), out.numel(), self.loss.data_ptr(),
-                                      p.dout_nchw.data_ptr(), _ptr(self._loss_scale_dev), self._mse_ws.data_ptr(), stream), "lh_mse_heatmap")
+        if self._jmse_ws is not None:
+            check(self.lib.lh_joints_mse(out.data_ptr(), self.target.data_ptr(), self.target_weight.data_ptr() if self.use_target_weight else None,
+                                         out.shape[0], out.shape[1], out.shape[2] * out.shape[3], self.ohkm_topk, self.loss.data_ptr(),
+                                         self.joint_loss.data_ptr(), p.dout_nchw.data_ptr(), _ptr(self._loss_scale_dev),
+                                         self._jmse_ws.data_ptr(), stream), "lh_joints_mse")
+        else:
+            check(self.lib.lh_mse_heatmap(out.data_ptr(), self.target.data_ptr(), out.numel(), self.loss.data_ptr(),
+                                          p.dout_nchw.data_ptr(), _ptr(self._loss_scale_dev), self._mse_ws.data_ptr(), stream), "lh_mse_heatmap")
         if self.decode:
             check(self.lib.lh_heatmap_argmax(out.data_ptr(), out.shape[0] * out.shape[1], out.shape[2], out.shape[3],
                                              self.heat_scale, self.preds.data_ptr(), self.maxvals.data_ptr(), None,
@@ -294,7 +324,8 @@ class TrainStep:
                 self.optimizer._sync_hyper(st, group)
 
     def __call__(self, images=None, joints=None, target=None, aug=None):
-        """``aug`` (bool [batch], optional; uint8 input with color_jitter only): which samples are jittered this step
+        """``joints``: [batch, J, >=2]; under ``use_target_weight`` a third column is the visibility (two columns = all visible).
+        ``aug`` (bool [batch], optional; uint8 input with color_jitter only): which samples are jittered this step
         (the reference's fixed --ratio_of_aug subset, src/tools/dataset.py:133); None = all of them."""
         if getattr(self.model, "_lh_generation", 0) != self._model_generation:
             raise LightHandError("the model's parameter storages were re-created (.to() / .cuda() / .float()) after this TrainStep "
@@ -315,6 +346,8 @@ class TrainStep:
             self.plan.warp_fwd.copy_(fwd, non_blocking=True)
         if joints is not None:
             self.joints.copy_(joints[..., :2], non_blocking=True)
+            if self.use_target_weight:             # column 2 = visibility; two columns = every joint visible
+                self.vis.copy_(joints[..., 2], non_blocking=True) if joints.shape[-1] >= 3 else self.vis.fill_(1.0)
         if target is not None:
             self.target.copy_(target, non_blocking=True)
         if not self.use_graph:

@@ -22,7 +22,12 @@ and step a rotation ~ U[-DEG, DEG] degrees about the frame centre, a scale ~ U[1
 warped on the device in the fused input kernel with a black border, the joints moved to match before the target is rendered;
 the reference bakes one fixed +-20 degree rotation into a second copy of its dataset offline, src/tools/processing_aug.py.  All
 default to 0 = off, the same step as without them; with float-tensor datasets a factor is an error.  The reference's boolean
-``--rot`` is read nowhere there and stays a no-op here).
+``--rot`` is read nowhere there and stays a no-op here), ``--use_target_weight`` (the loss weights every joint plane by upstream's
+``target_weight``: 0 for a joint that is invisible -- a third column of ``joint_2d`` -- or whose Gaussian patch left the map, e.g.
+after the online warp; the reference computes this weight, src/tools/dataset.py:171-186, and never applies it) and ``--ohkm_topk K``
+(online hard-keypoint mining, upstream's JointsOHKMMSELoss: per sample only the K joints with the largest loss count).  Both default
+to off = the reference's objective; validation then scores the loss with the same criterion, PCK / EPE stay as they are.
+``--synthetic_invisible F``: the fraction of synthetic joints marked invisible under ``--use_target_weight`` (default 0.1).
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -82,6 +87,11 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--rot_factor", default=0.0, type=float, help="online rotation of raw uint8 frames: U[-DEG, DEG] degrees (0 = off)")
     p.add_argument("--scale_factor", default=0.0, type=float, help="online scale of raw uint8 frames: U[1-F, 1+F] (0 = off)")
     p.add_argument("--shift_factor", default=0.0, type=float, help="online shift of raw uint8 frames: U[-F, F] x the size (0 = off)")
+    p.add_argument("--use_target_weight", action="store_true",
+                   help="weight the loss by joint visibility (joint_2d column 2) x patch-inside-the-map (default: off, the reference's loss)")
+    p.add_argument("--ohkm_topk", default=0, type=int, help="online hard-keypoint mining: the K hardest joints per sample (0 = off)")
+    p.add_argument("--synthetic_invisible", default=0.1, type=float,
+                   help="fraction of --synthetic joints marked invisible (read under --use_target_weight only)")
     args = p.parse_args(argv)
     args.phase = phase
     args.model = args.root.split("/")[0]                  # src/tools/dataset.py:59 overwrites it from the name
@@ -104,12 +114,16 @@ def build_model(args):
 
 class SyntheticHands(torch.utils.data.Dataset):
     """Seeded stand-in for CustomDataset (src/tools/dataset.py:103-163): returns (image[3,S,S] ~ N(0,1) like
-    a normalised crop, joint_2d[21,2] uniform in [20, S-20]).  Heatmaps are rendered on the device."""
+    a normalised crop, joint_2d[21,2] uniform in [20, S-20]).  Heatmaps are rendered on the device.  ``invisible=F`` appends a
+    visibility column (joint_2d[21,3]): 0 for a seeded fraction F of the joints, 1 for the others."""
 
-    def __init__(self, n, size, seed):
+    def __init__(self, n, size, seed, invisible=None):
         rng = np.random.RandomState(seed)
         self.images = torch.from_numpy(rng.randn(n, 3, size, size).astype(np.float32))
         self.joints = torch.from_numpy(rng.uniform(20, size - 20, size=(n, 21, 2)).astype(np.float32))
+        if invisible is not None:                    # drawn after the images and joints: those stay what they are without it
+            vis = torch.from_numpy((rng.uniform(size=(n, 21, 1)) >= invisible).astype(np.float32))
+            self.joints = torch.cat([self.joints, vis], 2)
 
     def __len__(self):
         return len(self.images)
@@ -120,7 +134,8 @@ class SyntheticHands(torch.utils.data.Dataset):
 
 class _WithAugFlag(torch.utils.data.Dataset):
     """(image, joint_2d, ...) -> (image, joint_2d, jitter?) with the reference's rule for the colour augmentation: the
-    FIXED subset idx < len(dataset) * ratio_of_aug is jittered (src/tools/dataset.py:133)."""
+    FIXED subset idx < len(dataset) * ratio_of_aug is jittered (src/tools/dataset.py:133).  joint_2d keeps a third column
+    (visibility, read by --use_target_weight) when the dataset has one."""
 
     def __init__(self, base, ratio_of_aug):
         # the reference compares the sample index with len(self.meta) * ratio_of_aug (dataset.py:133), and len(meta) can
@@ -133,7 +148,7 @@ class _WithAugFlag(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         s = self.base[i]
-        return s[0], torch.as_tensor(s[1], dtype=torch.float32)[:, :2], i < self.limit
+        return s[0], torch.as_tensor(s[1], dtype=torch.float32)[:, :3], i < self.limit
 
 
 def _sample_kind(ds):
@@ -278,14 +293,17 @@ def validate(model, loader, args, u8_step=None):
     """Runner.run validation branch (src/utils/method.py:218-287): loss, PCK@0.2 (bbox-normalised), EPE.
     ``u8_step``: an InferStep(input_u8=...) of the model for loaders that yield raw uint8 frames, or a callable
     batch size -> InferStep (the short last batch of the loader needs a step of its own shape)."""
-    from lighthand_amd.heatmap import JointsMSELoss, max_preds_device, render_targets
+    from lighthand_amd.heatmap import JointsMSELoss, WeightedJointsMSELoss, max_preds_device, render_targets
     from lighthand_amd.metrics import device_pck_epe
     model.eval()
-    crit = JointsMSELoss(False)
+    # the loss the step trains with (--use_target_weight / --ohkm_topk), so the best-checkpoint decision follows the objective
+    use_weight, topk = getattr(args, "use_target_weight", False), getattr(args, "ohkm_topk", 0)
+    crit = WeightedJointsMSELoss(topk) if use_weight or topk else JointsMSELoss(False)
     acc = torch.zeros(5, device="cuda")          # loss*b, b, pck*b, epe sum, epe count -- reduced on the device
     with torch.no_grad():
         for batch in loader:
-            images, joints = batch[0].cuda(non_blocking=True), batch[1][..., :2].float().cuda(non_blocking=True)
+            images, joints3 = batch[0].cuda(non_blocking=True), batch[1][..., :3].float().cuda(non_blocking=True)
+            joints = joints3[..., :2].contiguous()
             if images.dtype == torch.uint8:
                 st = u8_step(images.shape[0]) if callable(u8_step) and not hasattr(u8_step, "heatmaps") else u8_step
                 st.refresh_weights()
@@ -294,8 +312,11 @@ def validate(model, loader, args, u8_step=None):
             else:
                 pred = model(images)
             hs = pred.shape[-1]
-            target = render_targets(joints, size=hs)
-            loss = crit(pred, target, None)
+            if use_weight:
+                target, weight = render_targets(joints3, size=hs, return_weight=True)
+            else:
+                target, weight = render_targets(joints, size=hs), None
+            loss = crit(pred, target, weight)
             kp, _, _ = max_preds_device(pred, scale=float(args.size // hs))
             b = images.shape[0]
             pck, esum, ecnt = device_pck_epe(kp, joints, T=0.2)
@@ -345,13 +366,16 @@ def main(args, train_set=None, val_set=None):
     random.seed(seed)
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
+    # synthetic samples carry a visibility column only where it is read: their default shape stays [21, 2]
+    invisible = args.synthetic_invisible if args.use_target_weight else None
     if train_set is None:
         if not args.synthetic:
             raise SystemExit("the reference's datasets (LightHand99K / FreiHAND / ...) are not shipped: pass --synthetic N, or call "
                              "lighthand_amd.tools.train.main(args, train_set=, val_set=) with Datasets of (image, joint_2d) samples")
-        train_set = SyntheticHands(args.synthetic, args.size, seed + rank)
+        train_set = SyntheticHands(args.synthetic, args.size, seed + rank, invisible=invisible)
     if val_set is None:
-        val_set = SyntheticHands(args.val_synthetic or max(args.batch_size, max(args.synthetic, args.batch_size * 8) // 8), args.size, seed + 1000)
+        val_set = SyntheticHands(args.val_synthetic or max(args.batch_size, max(args.synthetic, args.batch_size * 8) // 8), args.size, seed + 1000,
+                                 invisible=invisible)
     kind, raw_hw = _sample_kind(train_set)
     val_kind, val_hw = _sample_kind(val_set)
     train_set = _WithAugFlag(train_set, args.ratio_of_aug)
@@ -376,8 +400,9 @@ def main(args, train_set=None, val_set=None):
     sync = parallel.GradSync(world) if world > 1 else None
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
+    loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk)
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
-                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo)
+                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw)
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order
     steps = {args.batch_size: step}
 
@@ -388,7 +413,7 @@ def main(args, train_set=None, val_set=None):
         st = steps.get(b)
         if st is None:
             st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
-                                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo,
+                                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw,
                                       plan_options=PlanOptions.from_env().replace(autotune=False))
         return st
 

@@ -1,0 +1,50 @@
+#!/usr/bin/env python3
+"""What the visibility-weighted loss and hard-keypoint mining cost per training step: the plain TrainStep
+(lh_gaussian_target + lh_mse_heatmap) against use_target_weight (lh_gaussian_target_w + lh_joints_mse: the same passes), ohkm_topk=8
+(plane sums, select, gradient: one more read of the selected planes) and both, alternated in ONE process on R50 64 x 256^2 bf16.
+Every joint is visible and in frame, so all forms train on the same planes.  Device events around `steps` replays, after a warm-up;
+median over the rounds.
+usage (GPU box): python tools/loss_step_cost.py [steps] [rounds]"""
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from lighthand_amd.runtime import TrainStep  # noqa: E402
+
+steps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+dev = torch.device("cuda", 0)
+batch = 64
+
+
+def timed(step, n):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        step()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+images, joints = bench.synthetic_batch(batch, 256, dev)
+forms = {}
+for tag, kw in (("plain", {}), ("weighted", dict(use_target_weight=True)), ("ohkm-8", dict(ohkm_topk=8)),
+                ("weighted+ohkm-8", dict(use_target_weight=True, ohkm_topk=8))):
+    step = TrainStep(bench.build_model(depth=50, precision="bf16"), batch, 256, 256, lr=1e-3, **kw)
+    step(images, joints)
+    timed(step, 10)                                                   # warm-up (capture happened in the first call)
+    forms[tag] = step
+ms = {tag: [] for tag in forms}
+for _ in range(rounds):
+    for tag, step in forms.items():
+        ms[tag].append(timed(step, steps))
+med = {tag: statistics.median(v) for tag, v in ms.items()}
+print(f"r50 bs{batch} 256^2 bf16, heat-maps {forms['plain'].plan.out_nchw.numel() * 4 / 1e6:.0f} MB:", flush=True)
+for tag, v in ms.items():
+    print(f"  {tag:16s} {med[tag]:7.3f} ms/step median ({med[tag] - med['plain']:+.3f} vs plain; rounds: {', '.join(f'{x:.3f}' for x in v)})",
+          flush=True)
