@@ -73,6 +73,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride launch with 256 threads per workgroup: one thread per item, at most `cap` workgroups
+static inline int lh_grid(long total, int cap) { return (int)((total + 255) / 256 > cap ? cap : (total + 255) / 256); }
 
 // XCD-aware work-item index (speed only, never correctness).  Workgroup ids are dealt round-robin over the 8 XCDs,
 // each with a private L2, so ids b and b+8 share an L2 while neighbours b, b+1 do not.  The remap gives every XCD a

@@ -1,0 +1,591 @@
+// Heat-maps: Gaussian target renderers, MSE / weighted / hard-keypoint-mining losses, arg-max family decode, PCK / EPE metrics.
+#include "common.h"
+
+// ------------------------------------------------------------------------------------------------ Gaussian target
+// generate_target (src/tools/dataset.py:171-186).  WEIGHTED renders upstream's target_weight with it (`if v > 0.5:`): weight =
+// visibility x "some part of the patch lies inside the map", a joint of weight 0 gets a zero map, and the thread that owns pixel
+// (0, 0) of a plane writes that plane's weight.  A compile-time switch: the unweighted instantiation never reads vis / weight
+// (passed as null) and keeps the resource table it had as a kernel of its own (tools/kres.py).
+template <bool WEIGHTED>
+__global__ void gaussian_target_kernel(const float* joints, int jstride, const float* vis, int vstride, const float* patch,
+                                       int radius, float* target, float* weight, int bj, int size) {
+    const long total = (long)bj * size * size;
+    const int pw = 2 * radius + 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % size);
+        const long t = i / size;
+        const int y = (int)(t % size);
+        const long j = t / size;
+        const float jx = joints[j * jstride], jy = joints[j * jstride + 1];
+        // int(v / 4 + 0.5): truncation toward zero, like Python's int()
+        const int mx = (int)(jx * 0.25f + 0.5f), my = (int)(jy * 0.25f + 0.5f);
+        const int x0 = mx - radius, y0 = my - radius, x1 = mx + radius + 1, y1 = my + radius + 1;
+        const bool skip = x0 >= size || y0 >= size || x1 < 0 || y1 < 0;
+        bool draw = !skip;
+        float w = 0.f;
+        if constexpr (WEIGHTED) {
+            const float v = vis ? vis[j * vstride] : 1.f;
+            w = (v > 0.5f ? v : 0.f) * (skip ? 0.f : 1.f);
+            draw = w > 0.f;
+        }
+        float out = 0.f;
+        if (draw && x >= x0 && x < x1 && y >= y0 && y < y1) out = patch[(y - y0) * pw + (x - x0)];
+        target[i] = out;
+        if constexpr (WEIGHTED)
+            if (x == 0 && y == 0) weight[j] = w;
+    }
+}
+
+// GenerateHeatmap (src/utils/dataset_loader.py:22-53), the alternate renderer: points are ALREADY in heat-map coordinates,
+// sigma = res / 64 (an integer here), patch of (6 * sigma + 3)^2 centred on int(point), np.maximum blend with the zero
+// map (= plain placement: every joint owns its plane); a joint is skipped when x <= 0 or int(point) lies outside the map.
+__global__ void gaussian_target_alt_kernel(const float* points, int pstride, const float* patch, int sigma, float* target,
+                                           int bj, int res) {
+    const long total = (long)bj * res * res;
+    const int pw = 6 * sigma + 3;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % res);
+        const long t = i / res;
+        const int y = (int)(t % res);
+        const long j = t / res;
+        const float fx = points[j * pstride], fy = points[j * pstride + 1];
+        float v = 0.f;
+        if (fx > 0.f) {
+            const int px = (int)fx, py = (int)fy;                    // Python int(): truncation toward zero
+            if (px >= 0 && py >= 0 && px < res && py < res) {
+                const int ulx = px - 3 * sigma - 1, uly = py - 3 * sigma - 1;
+                const int gx = x - ulx, gy = y - uly;                // hms[aa:bb, cc:dd] <- g[a:b, c:d]: same offset on both axes
+                if (gx >= 0 && gx < pw && gy >= 0 && gy < pw) v = patch[gy * pw + gx];
+            }
+        }
+        target[i] = v;
+    }
+}
+
+extern "C" int lh_gaussian_target_alt(const float* points, int pstride, const float* patch, int sigma, float* target,
+                                      int b, int j, int res, void* stream) {
+    LH_REQUIRE(points && patch && target && pstride >= 2 && b > 0 && j > 0 && res > 0 && sigma >= 1 && res == 64 * sigma,
+               "lh_gaussian_target_alt: bad arguments (res must be 64 * sigma, sigma a positive integer)");
+    const long total = (long)b * j * res * res;
+    const int grid = lh_grid(total, 4096);
+    hipLaunchKernelGGL(gaussian_target_alt_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, points, pstride, patch, sigma,
+                       target, b * j, res);
+    LH_LAUNCH_CHECK("gaussian_target_alt launch");
+    return LH_OK;
+}
+
+extern "C" int lh_gaussian_target(const float* joints, int jstride, const float* patch, int radius, float* target,
+                                  int b, int j, int size, void* stream) {
+    LH_REQUIRE(joints && patch && target && jstride >= 2 && b > 0 && j > 0 && size > 0 && radius >= 0,
+               "lh_gaussian_target: bad arguments");
+    hipLaunchKernelGGL(gaussian_target_kernel<false>, dim3(lh_grid((long)b * j * size * size, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       joints, jstride, (const float*)nullptr, 0, patch, radius, target, (float*)nullptr, b * j, size);
+    LH_LAUNCH_CHECK("gaussian_target launch");
+    return LH_OK;
+}
+
+extern "C" int lh_gaussian_target_w(const float* joints, int jstride, const float* vis, int vstride, const float* patch, int radius,
+                                    float* target, float* weight, int b, int j, int size, void* stream) {
+    LH_REQUIRE(joints && patch && target && weight && jstride >= 2 && (!vis || vstride >= 1) && b > 0 && j > 0 && size > 0 && radius >= 0,
+               "lh_gaussian_target_w: bad arguments");
+    hipLaunchKernelGGL(gaussian_target_kernel<true>, dim3(lh_grid((long)b * j * size * size, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       joints, jstride, vis, vstride, patch, radius, target, weight, b * j, size);
+    LH_LAUNCH_CHECK("gaussian_target_w launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ MSE loss
+constexpr int MSE_BLOCKS = 512;
+
+__global__ __launch_bounds__(256) void mse_partial_kernel(const float* pred, const float* target, long numel, float* grad,
+                                                         const float* grad_scale, double* partial) {
+    __shared__ double red[4];
+    const float gs = (grad_scale ? *grad_scale : 1.f) / (float)numel;
+    double acc = 0.0;
+    const long nvec = numel / 4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
+        const float4 p = reinterpret_cast<const float4*>(pred)[i];
+        const float4 t = reinterpret_cast<const float4*>(target)[i];
+        const float4 d = {p.x - t.x, p.y - t.y, p.z - t.z, p.w - t.w};
+        acc += (double)(d.x * d.x) + (double)(d.y * d.y) + (double)(d.z * d.z) + (double)(d.w * d.w);
+        if (grad) reinterpret_cast<float4*>(grad)[i] = float4{d.x * gs, d.y * gs, d.z * gs, d.w * gs};
+    }
+    if (blockIdx.x == 0)
+        for (long i = nvec * 4 + threadIdx.x; i < numel; i += 256) {
+            const float d = pred[i] - target[i];
+            acc += (double)(d * d);
+            if (grad) grad[i] = d * gs;
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ void mse_final_kernel(const double* partial, int nblocks, long numel, float* loss) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) acc += partial[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss = (float)(0.5 * (red[0] + red[1] + red[2] + red[3]) / (double)numel);
+}
+
+extern "C" size_t lh_mse_workspace_bytes(long numel) { (void)numel; return MSE_BLOCKS * sizeof(double); }
+
+extern "C" int lh_mse_heatmap(const float* pred, const float* target, long numel, float* loss, float* grad,
+                              const float* grad_scale, void* workspace, void* stream) {
+    LH_REQUIRE(pred && target && loss && workspace && numel > 0, "lh_mse_heatmap: bad arguments");
+    LH_REQUIRE(((uintptr_t)pred % 16 == 0) && ((uintptr_t)target % 16 == 0) && (!grad || (uintptr_t)grad % 16 == 0),
+               "lh_mse_heatmap: buffers must be 16-byte aligned");
+    int blocks = (int)((numel / 4 + 255) / 256);
+    if (blocks > MSE_BLOCKS) blocks = MSE_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mse_partial_kernel, dim3(blocks), dim3(256), 0, s, pred, target, numel, grad, grad_scale,
+                       (double*)workspace);
+    hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, blocks, numel, loss);
+    LH_LAUNCH_CHECK("mse launch");
+    return LH_OK;
+}
+
+// ---- JointsMSELoss(use_target_weight=True) and JointsOHKMMSELoss of the SimpleBaseline / HRNet code line (lh_joints_mse).
+// One workgroup per joint plane: the plane's sum S = w^2 * sum (float)(d * d) in fp64, in a fixed order (the reduction of
+// mse_partial_kernel: per-thread fp64 accumulator, wave-64 shuffle, four LDS slots; no atomics, so every replay gives the same
+// bits).  Without mining the gradient coefficient w * w * gs is known before any sum, so the same pass writes the gradient
+// (GRAD); with mining the pass only sums, joints_ohkm_select_kernel picks the planes and joints_ohkm_grad_kernel writes them.
+__device__ __forceinline__ double plane_reduce(double acc, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(256) void joints_mse_plane_kernel(const float* pred, const float* target, const float* weight, int hw,
+                                                              long numel, float* grad, const float* grad_scale, double* plane_sum,
+                                                              float* joint_loss) {
+    __shared__ double red[4];
+    const long base = (long)blockIdx.x * hw;
+    const float w = weight ? weight[blockIdx.x] : 1.f;
+    float coef = 0.f;
+    if (GRAD) {
+        const float gs = (grad_scale ? *grad_scale : 1.f) / (float)numel;
+        coef = w * w * gs;
+    }
+    const float4* p4 = reinterpret_cast<const float4*>(pred + base);
+    const float4* t4 = reinterpret_cast<const float4*>(target + base);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < hw / 4; i += 256) {
+        const float4 p = p4[i], t = t4[i];
+        const float4 d = {p.x - t.x, p.y - t.y, p.z - t.z, p.w - t.w};
+        acc += (double)(d.x * d.x) + (double)(d.y * d.y) + (double)(d.z * d.z) + (double)(d.w * d.w);
+        if (GRAD) reinterpret_cast<float4*>(grad + base)[i] = float4{d.x * coef, d.y * coef, d.z * coef, d.w * coef};
+    }
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) {
+        const double s = (double)w * (double)w * sum;
+        plane_sum[blockIdx.x] = s;
+        if (joint_loss) joint_loss[blockIdx.x] = (float)(0.5 * s / (double)hw);
+    }
+}
+
+__global__ __launch_bounds__(256) void joints_mse_final_kernel(const double* plane_sum, int bj, long numel, float* loss) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < bj; i += 256) acc += plane_sum[i];
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) *loss = (float)(0.5 * sum / (double)numel);
+}
+
+// true when joint k (loss a) is picked before joint i (loss b): larger loss first, the lower joint index among equals; a NaN
+// loss ranks first (lh_heatmap_argmax's rule), so it reaches the loss value instead of hiding behind the selection
+__device__ __forceinline__ bool ohkm_before(float a, int k, float b, int i) {
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return an && (!bn || k < i);
+    return a > b || (a == b && k < i);
+}
+
+// One workgroup, thread t owns planes t, t + 256, ...: the rank of the plane's joint among its sample's fp32 per-joint losses
+// (j comparisons), the coefficient w * w * gs_k and the selection flag for the gradient pass, and
+// loss = (1/b) sum_b (1/topk) sum_selected 0.5 * S / hw accumulated in fp64 in a fixed order.
+__global__ __launch_bounds__(256) void joints_ohkm_select_kernel(const double* plane_sum, const float* weight, int b, int j, int hw,
+                                                                int topk, const float* grad_scale, float* coef, int* selected,
+                                                                float* loss) {
+    __shared__ double red[4];
+    const float gs = (grad_scale ? *grad_scale : 1.f) / (float)((long)b * topk * hw);
+    double acc = 0.0;
+    for (int idx = threadIdx.x; idx < b * j; idx += 256) {
+        const int i = idx % j;
+        const double* ps = plane_sum + (idx - i);
+        const double li = 0.5 * ps[i] / (double)hw;
+        const float fi = (float)li;
+        int rank = 0;
+        for (int k = 0; k < j; ++k)
+            if (k != i && ohkm_before((float)(0.5 * ps[k] / (double)hw), k, fi, i)) ++rank;
+        const bool sel = rank < topk;
+        const float w = weight ? weight[idx] : 1.f;
+        coef[idx] = sel ? w * w * gs : 0.f;
+        selected[idx] = sel ? 1 : 0;
+        if (sel) acc += li;
+    }
+    const double sum = plane_reduce(acc, red);
+    if (threadIdx.x == 0) *loss = (float)(sum / ((double)b * (double)topk));
+}
+
+// planes that were not selected are not read: their gradient is exactly 0.f
+__global__ __launch_bounds__(256) void joints_ohkm_grad_kernel(const float* pred, const float* target, int hw, const float* coef,
+                                                              const int* selected, float* grad) {
+    const long base = (long)blockIdx.x * hw;
+    float4* g4 = reinterpret_cast<float4*>(grad + base);
+    if (!selected[blockIdx.x]) {
+        for (int i = threadIdx.x; i < hw / 4; i += 256) g4[i] = float4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const float c = coef[blockIdx.x];
+    const float4* p4 = reinterpret_cast<const float4*>(pred + base);
+    const float4* t4 = reinterpret_cast<const float4*>(target + base);
+    for (int i = threadIdx.x; i < hw / 4; i += 256) {
+        const float4 p = p4[i], t = t4[i];
+        g4[i] = float4{(p.x - t.x) * c, (p.y - t.y) * c, (p.z - t.z) * c, (p.w - t.w) * c};
+    }
+}
+
+// workspace: fp64 plane sums [b][j], then the fp32 coefficient table and the int32 selection flags of the mining pass
+extern "C" size_t lh_joints_mse_workspace_bytes(int b, int j) {
+    return b > 0 && j > 0 ? (size_t)b * j * (sizeof(double) + sizeof(float) + sizeof(int)) : 0;
+}
+
+extern "C" int lh_joints_mse(const float* pred, const float* target, const float* weight, int b, int j, int hw, int topk, float* loss,
+                             float* joint_loss, float* grad, const float* grad_scale, void* workspace, void* stream) {
+    LH_REQUIRE(pred && target && loss && workspace && b > 0 && j > 0 && hw > 0, "lh_joints_mse: bad arguments");
+    LH_REQUIRE(topk >= 0 && topk <= j, "lh_joints_mse: topk %d outside 0..%d (the joints of a sample)", topk, j);
+    LH_REQUIRE(hw % 4 == 0, "lh_joints_mse: the plane size %d must be a multiple of 4", hw);
+    LH_REQUIRE((long)b * j < (1L << 31), "lh_joints_mse: too many planes");
+    LH_REQUIRE(((uintptr_t)pred % 16 == 0) && ((uintptr_t)target % 16 == 0) && (!grad || (uintptr_t)grad % 16 == 0) &&
+               ((uintptr_t)workspace % 16 == 0), "lh_joints_mse: buffers must be 16-byte aligned");
+    const int bj = b * j;
+    const long numel = (long)bj * hw;
+    double* plane_sum = (double*)workspace;
+    float* coef = (float*)(plane_sum + bj);
+    int* selected = (int*)(coef + bj);
+    hipStream_t s = (hipStream_t)stream;
+    if (topk == 0) {
+        if (grad)
+            hipLaunchKernelGGL((joints_mse_plane_kernel<true>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel, grad,
+                               grad_scale, plane_sum, joint_loss);
+        else
+            hipLaunchKernelGGL((joints_mse_plane_kernel<false>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel,
+                               (float*)nullptr, grad_scale, plane_sum, joint_loss);
+        hipLaunchKernelGGL(joints_mse_final_kernel, dim3(1), dim3(256), 0, s, (const double*)plane_sum, bj, numel, loss);
+        LH_LAUNCH_CHECK("joints_mse launch");
+        return LH_OK;
+    }
+    hipLaunchKernelGGL((joints_mse_plane_kernel<false>), dim3(bj), dim3(256), 0, s, pred, target, weight, hw, numel, (float*)nullptr,
+                       grad_scale, plane_sum, joint_loss);
+    hipLaunchKernelGGL(joints_ohkm_select_kernel, dim3(1), dim3(256), 0, s, (const double*)plane_sum, weight, b, j, hw, topk, grad_scale,
+                       coef, selected, loss);
+    if (grad)
+        hipLaunchKernelGGL(joints_ohkm_grad_kernel, dim3(bj), dim3(256), 0, s, pred, target, hw, (const float*)coef, (const int*)selected,
+                           grad);
+    LH_LAUNCH_CHECK("joints_ohkm launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ arg-max decode
+struct Cand { float v; int i; };
+// true when a precedes b under numpy.argmax's rule: NaN beats everything, then larger value,
+// ties (and NaN vs NaN) broken by the lower flat index.
+__device__ __forceinline__ bool cand_before(const Cand& a, const Cand& b) {
+    const bool an = a.v != a.v, bn = b.v != b.v;
+    if (an || bn) return an && (!bn || a.i < b.i);
+    return a.v > b.v || (a.v == b.v && a.i < b.i);
+}
+
+__global__ __launch_bounds__(256) void heatmap_argmax_kernel(const float* hm, int hw, int w, float scale, float* preds,
+                                                            float* maxvals, int* idx) {
+    __shared__ Cand red[4];
+    const float* m = hm + (long)blockIdx.x * hw;
+    Cand best = {0.f, 0x7fffffff};
+    bool have = false;
+    for (int i = threadIdx.x; i < hw; i += 256) {
+        const Cand c = {m[i], i};
+        if (!have || cand_before(c, best)) { best = c; have = true; }
+    }
+    if (!have) best = Cand{-INFINITY, 0x7fffffff};
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Cand other = {__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
+        if (other.i != 0x7fffffff && (best.i == 0x7fffffff || cand_before(other, best))) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Cand b = red[0];
+        for (int k = 1; k < 4; ++k)
+            if (red[k].i != 0x7fffffff && (b.i == 0x7fffffff || cand_before(red[k], b))) b = red[k];
+        const float keep = b.v > 0.f ? 1.f : 0.f;
+        preds[blockIdx.x * 2 + 0] = (float)(b.i % w) * keep * scale;
+        preds[blockIdx.x * 2 + 1] = (float)(b.i / w) * keep * scale;
+        maxvals[blockIdx.x] = b.v;
+        if (idx) idx[blockIdx.x] = b.i;
+    }
+}
+
+extern "C" int lh_heatmap_argmax(const float* heatmaps, int bj, int h, int w, float scale, float* preds, float* maxvals,
+                                 int* idx, void* stream) {
+    LH_REQUIRE(heatmaps && preds && maxvals && bj > 0 && h > 0 && w > 0, "lh_heatmap_argmax: bad arguments");
+    hipLaunchKernelGGL(heatmap_argmax_kernel, dim3(bj), dim3(256), 0, (hipStream_t)stream, heatmaps, h * w, w, scale, preds,
+                       maxvals, idx);
+    LH_LAUNCH_CHECK("heatmap_argmax launch");
+    return LH_OK;
+}
+
+// Opt-in quarter-pixel refinement of the hard arg-max (the reference carries the switch
+// TEST.POST_PROCESS, src/modeling/simplebaseline/config.py:109, but never uses it): the published SimpleBaseline
+// `get_final_preds` rule -- when the peak (px, py) is strictly inside the map (1 < px < W-1, 1 < py < H-1) move it a
+// quarter pixel toward the higher neighbour on each axis: coord += 0.25 * sign(hm[..+1] - hm[..-1]).  Works on the
+// UNSCALED peak; `scale` is the factor lh_heatmap_argmax already applied to `preds`.
+__global__ void heatmap_refine_kernel(const float* hm, const int* idx, const float* maxvals, int bj, int h, int w,
+                                      float scale, float* preds) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= bj) return;
+    if (!(maxvals[t] > 0.f)) return;                      // get_max_preds zeroed the coordinate: px = py = 0, never interior
+    const int k = idx[t];
+    const int px = k % w, py = k / w;
+    if (!(1 < px && px < w - 1 && 1 < py && py < h - 1)) return;
+    const float* m = hm + (long)t * h * w;
+    const float dx = m[py * w + px + 1] - m[py * w + px - 1];
+    const float dy = m[(py + 1) * w + px] - m[(py - 1) * w + px];
+    const float sx = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f), sy = dy > 0.f ? 1.f : (dy < 0.f ? -1.f : 0.f);
+    preds[t * 2 + 0] = ((float)px + 0.25f * sx) * scale;
+    preds[t * 2 + 1] = ((float)py + 0.25f * sy) * scale;
+}
+
+extern "C" int lh_heatmap_refine(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w,
+                                 float scale, float* preds, void* stream) {
+    LH_REQUIRE(heatmaps && idx && maxvals && preds && bj > 0 && h > 0 && w > 0, "lh_heatmap_refine: bad arguments");
+    hipLaunchKernelGGL(heatmap_refine_kernel, dim3((bj + 255) / 256), dim3(256), 0, (hipStream_t)stream, heatmaps, idx, maxvals,
+                       bj, h, w, scale, preds);
+    LH_LAUNCH_CHECK("heatmap_refine launch");
+    return LH_OK;
+}
+
+// Flip test (TEST.FLIP_TEST / TEST.SHIFT_HEATMAP of the reference's configs) after the two forwards, in one launch: a = the
+// plain pass's heat-maps, m = those of the pass on the horizontally mirrored input.  SimpleBaseline's flip_back, its
+// `output_flipped[..., 1:] = output_flipped.clone()[..., :-1]` and `(output + output_flipped) * 0.5`:
+//   shift:    f[y][x] = m[y][W-x] for x >= 1, f[y][0] = m[y][W-1];   no shift: f[y][x] = m[y][W-1-x]
+//   merged = (a + f) * 0.5f (two fp32 roundings: -ffp-contract=off), then heatmap_argmax_kernel's decode of merged.
+// No joint permutation: the 21 joints of one hand are their own mirror images.
+// Why the one-column shift is right for this project's coordinates: the target of a joint at input x is centred on column
+// int(x / 4 + 0.5) and the decode multiplies the peak column by 4, so a joint at x = 4k peaks at column k.  The mirrored input
+// (width 4W) holds it at 4W-1-4k, centred on int(W - k + 0.25) = W - k; flipped back that is column W-1-(W-k) = k-1, and the
+// shift brings it back to k.
+// One workgroup per map, the tie rule of heatmap_argmax_kernel.  A thread loads a chunk of U elements of a and of m into
+// registers before it stores any of them: merged may alias a (each element is read and written by the same thread only), and
+// the loads of a chunk stay independent of its stores.
+template <int U>
+__global__ __launch_bounds__(256) void heatmap_flip_merge_kernel(const float* a, const float* m, int hw, int w, int shift, float scale,
+                                                                 float* merged, float* preds, float* maxvals, int* idx) {
+    __shared__ Cand red[4];
+    const long base = (long)blockIdx.x * hw;
+    const float* am = a + base;
+    const float* mm = m + base;
+    float* om = merged + base;
+    const int dy = 256 / w, dx = 256 - dy * w;                // element i + 256 is dy rows and dx columns further
+    Cand best = {0.f, 0x7fffffff};
+    bool have = false;
+    int y = threadIdx.x / w, x = threadIdx.x - y * w;          // row and column of element i0
+    for (int i0 = threadIdx.x; i0 < hw; i0 += 256 * U) {
+        float va[U], vf[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            va[u] = vf[u] = 0.f;
+            if (i < hw) {
+                const int sx = shift ? (x ? w - x : w - 1) : w - 1 - x;
+                va[u] = am[i];
+                vf[u] = mm[y * w + sx];
+            }
+            x += dx;
+            y += dy;
+            if (x >= w) { x -= w; ++y; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 256;
+            if (i < hw) {
+                const float v = (va[u] + vf[u]) * 0.5f;
+                om[i] = v;
+                const Cand c = {v, i};
+                if (!have || cand_before(c, best)) { best = c; have = true; }
+            }
+        }
+    }
+    // the reduction and store of heatmap_argmax_kernel, restated: that kernel keeps its code
+    if (!have) best = Cand{-INFINITY, 0x7fffffff};
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Cand other = {__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
+        if (other.i != 0x7fffffff && (best.i == 0x7fffffff || cand_before(other, best))) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Cand b = red[0];
+        for (int k = 1; k < 4; ++k)
+            if (red[k].i != 0x7fffffff && (b.i == 0x7fffffff || cand_before(red[k], b))) b = red[k];
+        const float keep = b.v > 0.f ? 1.f : 0.f;
+        preds[blockIdx.x * 2 + 0] = (float)(b.i % w) * keep * scale;
+        preds[blockIdx.x * 2 + 1] = (float)(b.i / w) * keep * scale;
+        maxvals[blockIdx.x] = b.v;
+        if (idx) idx[blockIdx.x] = b.i;
+    }
+}
+
+extern "C" int lh_heatmap_flip_merge(const float* a, const float* m, int bj, int h, int w, int shift, float scale, float* merged,
+                                     float* preds, float* maxvals, int* idx, void* stream) {
+    LH_REQUIRE(a && m && merged && preds && maxvals && bj > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31),
+               "lh_heatmap_flip_merge: bad arguments");
+    const size_t bytes = (size_t)bj * h * w * sizeof(float);
+    const auto apart = [bytes](const void* p, const void* q) {
+        return (const char*)p + bytes <= (const char*)q || (const char*)q + bytes <= (const char*)p;
+    };
+    LH_REQUIRE(apart(m, merged) && (a == merged || apart(a, merged)),
+               "lh_heatmap_flip_merge: merged may alias a exactly and must not overlap m");
+    hipLaunchKernelGGL((heatmap_flip_merge_kernel<4>), dim3(bj), dim3(256), 0, (hipStream_t)stream, a, m, h * w, w, shift ? 1 : 0,
+                       scale, merged, preds, maxvals, idx);
+    LH_LAUNCH_CHECK("heatmap_flip_merge launch");
+    return LH_OK;
+}
+
+// Opt-in soft-arg-max decode (named in the project's north star; NOT in the reference, which decodes with the hard arg-max
+// of get_max_preds): preds = sum_p softmax(beta * hm)[p] * (x_p, y_p), computed per map with the usual max subtraction,
+// fp32 exponentials and fp64 sums.  One workgroup per (sample, joint).
+__global__ __launch_bounds__(256) void heatmap_soft_argmax_kernel(const float* hm, int hw, int w, float beta, float scale, float* preds) {
+    __shared__ float rmax[4];
+    __shared__ double rs[4][3];
+    const float* m = hm + (long)blockIdx.x * hw;
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < hw; i += 256) mx = fmaxf(mx, m[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) rmax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+    double s0 = 0.0, sx = 0.0, sy = 0.0;
+    for (int i = threadIdx.x; i < hw; i += 256) {
+        const double e = (double)expf(beta * (m[i] - mx));
+        s0 += e; sx += e * (double)(i % w); sy += e * (double)(i / w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); }
+    if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6][0] = s0; rs[threadIdx.x >> 6][1] = sx; rs[threadIdx.x >> 6][2] = sy; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double t0 = rs[0][0] + rs[1][0] + rs[2][0] + rs[3][0];
+        const double tx = rs[0][1] + rs[1][1] + rs[2][1] + rs[3][1];
+        const double ty = rs[0][2] + rs[1][2] + rs[2][2] + rs[3][2];
+        preds[blockIdx.x * 2 + 0] = (float)(tx / t0) * scale;
+        preds[blockIdx.x * 2 + 1] = (float)(ty / t0) * scale;
+    }
+}
+
+extern "C" int lh_heatmap_soft_argmax(const float* heatmaps, int bj, int h, int w, float beta, float scale, float* preds,
+                                      void* stream) {
+    LH_REQUIRE(heatmaps && preds && bj > 0 && h > 0 && w > 0, "lh_heatmap_soft_argmax: bad arguments");
+    hipLaunchKernelGGL(heatmap_soft_argmax_kernel, dim3(bj), dim3(256), 0, (hipStream_t)stream, heatmaps, h * w, w, beta, scale, preds);
+    LH_LAUNCH_CHECK("heatmap_soft_argmax launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ validation metrics
+// PCK_2d_loss(T, 'proportion') + EPE_train on the device (src/utils/loss.py:50-67,116-148): one wave per
+// sample.  wrong[b] = #joints whose error / bbox-diagonal(gt) > T; epe[b] = sum of errors of joints 1..J-2 (the
+// reference's joint range quirk).  Sums over the batch are left to the caller (device tensors, no host sync).
+__global__ __launch_bounds__(64) void keypoint_metrics_kernel(const float* pred, const float* gt, int gt_stride, int j, float T,
+                                                              int* wrong, float* epe) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* g = gt + (long)b * j * gt_stride;
+    const float* p = pred + (long)b * j * 2;
+    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    for (int k = lane; k < j; k += 64) {
+        const float x = g[k * gt_stride], y = g[k * gt_stride + 1];
+        xmin = fminf(xmin, x); xmax = fmaxf(xmax, x); ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        xmin = fminf(xmin, __shfl_xor(xmin, o)); xmax = fmaxf(xmax, __shfl_xor(xmax, o));
+        ymin = fminf(ymin, __shfl_xor(ymin, o)); ymax = fmaxf(ymax, __shfl_xor(ymax, o));
+    }
+    const float diag = sqrtf((xmax - xmin) * (xmax - xmin) + (ymax - ymin) * (ymax - ymin));
+    int w = 0;
+    float e = 0.f;
+    for (int k = lane; k < j; k += 64) {
+        const float dx = g[k * gt_stride] - p[k * 2], dy = g[k * gt_stride + 1] - p[k * 2 + 1];
+        const float dist = sqrtf(dx * dx + dy * dy);
+        if (dist / diag > T) ++w;
+        if (k >= 1 && k <= j - 2) e += dist;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { w += __shfl_xor(w, o); e += __shfl_xor(e, o); }
+    if (lane == 0) { wrong[b] = w; epe[b] = e; }
+}
+
+extern "C" int lh_keypoint_metrics(const float* pred, const float* gt, int gt_stride, int b, int j, float T, int* wrong,
+                                   float* epe, void* stream) {
+    LH_REQUIRE(pred && gt && wrong && epe && b > 0 && j > 2 && gt_stride >= 2, "lh_keypoint_metrics: bad arguments");
+    hipLaunchKernelGGL(keypoint_metrics_kernel, dim3(b), dim3(64), 0, (hipStream_t)stream, pred, gt, gt_stride, j, T, wrong, epe);
+    LH_LAUNCH_CHECK("keypoint_metrics launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ PCK curve / AUC
+// pred_eval (src/utils/argparser.py:326-388) on the device: for every threshold, the number of VISIBLE
+// joints (gt[..][2] == 1) whose error -- pixel distance, divided by the sample's bbox size when bb is given ('pckb') --
+// is < thr[t].  float64 like the NumPy original, integer atomics (exact, order independent: ranks add their counts with one
+// small all-reduce).  diff_row[s] = sum of the pixel errors of ALL joints of sample s (the EPE numerator).
+__global__ void pck_curve_kernel(const float* pred, const float* gt, int gt_stride, const float* bb, int n, int j,
+                                 const double* thr, int nthr, unsigned long long* counts, unsigned long long* nvis,
+                                 double* diff_row) {
+    const int sidx = blockIdx.x;
+    if (sidx >= n) return;
+    __shared__ double err[64];
+    __shared__ int vis[64];
+    for (int k = threadIdx.x; k < j; k += blockDim.x) {
+        const float* g = gt + ((long)sidx * j + k) * gt_stride;
+        const float* q = pred + ((long)sidx * j + k) * 2;
+        const double dx = (double)g[0] - (double)q[0], dy = (double)g[1] - (double)q[1];
+        err[k] = sqrt(dx * dx + dy * dy);
+        vis[k] = g[2] == 1.f ? 1 : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        int nv = 0;
+        for (int k = 0; k < j; ++k) { sum += err[k]; nv += vis[k]; }
+        diff_row[sidx] = sum;
+        if (nv) atomicAdd(nvis, (unsigned long long)nv);
+    }
+    const double scale = bb ? (double)bb[sidx] : 1.0;
+    for (int t = threadIdx.x; t < nthr; t += blockDim.x) {
+        int c = 0;
+        for (int k = 0; k < j; ++k)
+            if (vis[k] && err[k] / scale < thr[t]) ++c;
+        if (c) atomicAdd(counts + t, (unsigned long long)c);
+    }
+}
+
+extern "C" int lh_pck_curve(const float* pred, const float* gt, int gt_stride, const float* bb, int n, int j, const double* thr,
+                            int nthr, unsigned long long* counts, unsigned long long* nvis, double* diff_row, void* stream) {
+    LH_REQUIRE(pred && gt && thr && counts && nvis && diff_row && n > 0 && j > 0 && j <= 64 && gt_stride >= 3 && nthr > 0,
+               "lh_pck_curve: bad arguments (j <= 64, gt rows of >= 3 values: x, y, visibility)");
+    hipLaunchKernelGGL(pck_curve_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, pred, gt, gt_stride, bb, n, j, thr, nthr,
+                       counts, nvis, diff_row);
+    LH_LAUNCH_CHECK("pck_curve launch");
+    return LH_OK;
+}
