@@ -15,15 +15,18 @@ import torch
 from . import _lib
 from ._lib import FuseBwdDesc, FuseDesc, IgemmDesc, check
 from .batch_groups import BatchGroups
+from .bn_gate import BnGate
 from .graph import BN_EPS, BN_MOMENTUM, PRECISIONS, Act, GraphBuilder, _Call, _Marker, _desc, _ptr, _taps_array  # noqa: F401 (re-exported)
 from .infer_rewrites import InferRewrites
 from .options import PlanOptions
+from .runner import Runner
 from .tuner import Tuner
+from .weight_packs import WeightPacks
 from .wgrad_schedule import WgradSchedule
 
 
 # --------------------------------------------------------------------------------------- plan
-class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
+class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate, Runner):
     """Everything needed to run one model at one static shape."""
 
     def __init__(self, model, n, h, w, precision="fp32", training=True, backward=None, device=None, wgrad_bucket_bytes=None, options=None):
@@ -42,11 +45,10 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         if self.device.type != "cuda":
             raise _lib.LightHandError("lighthand_amd runs on a HIP device only; move the model with .to('cuda')")
         self.grads = {}
-        arena0 = getattr(model, "_lh_arena", None)
-        self.arena_offsets = arena0.offsets if arena0 is not None else {}
-        self.arena_numel = arena0.numel if arena0 is not None else 0
+        arena = getattr(model, "_lh_arena", None)
+        self.arena_offsets = arena.offsets if arena is not None else {}
+        self.arena_numel = arena.numel if arena is not None else 0
         if self.with_bwd:
-            arena = getattr(model, "_lh_arena", None)
             for k, p in self.params.items():
                 if isinstance(p, torch.nn.Parameter):
                     self.grads[k] = arena.grad_view(k) if arena is not None else torch.zeros_like(p)
@@ -98,6 +100,13 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         self.fwd, self.bwd, self.packs = [], [], []
         self._pack_items = []
         self._pack_convs = {}              # id(weight) -> PackConv (LDS-tiled transposing pack)
+        self._late_packs = None            # (pack buffers of the late group, pack buffers of the conv whose first use is the fork point)
+        self._packjoin_at = self._pack_stream = None                     # weight_packs._place_pack_markers
+        self._pack_event = self._pack_event2 = self._pack_late = None    # between refresh_packs(overlap=True) and the markers of one forward
+        self._regions = []                 # [fork marker, join marker or None] of every branch region of the forward list
+        self._in_branch = self._head_fused = False       # emitting the backward of a node inside a branch region; _fuse_head wrote the output
+        self._n_l2_touch = self._n_fused_bottlenecks = 0
+        self.bn_bwd_8d_bytes = 0.0         # what SURVEY 8(d)'s traffic model charges to the BatchNorm backward (bench.py)
         self._producers = {}               # id(raw conv output Act) -> the igemm calls that write it (eval-mode BN folding)
         self.keep = []                     # ctypes objects / tensors referenced by raw pointer
         self._ws_wgrad = 0
@@ -130,58 +139,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             a.grad = self._alloc(a.n, a.h, a.w, a.c, zero=True)
         return a.grad
 
-    def _pack(self, wt, n_out, n_in, strides, taps_rs, what):
-        """Allocate a pack image and register the launch that (re)builds it from ``wt``."""
-        nbytes = C.c_size_t(0)
-        arr = _taps_array(taps_rs)
-        check(self.lib.lh_pack_weight(None, None, C.byref(nbytes), n_out, n_in, *strides, len(taps_rs), arr, self.dt, None), what)
-        buf = self._alloc(max(nbytes.value, 16), dtype=torch.uint8, zero=True)     # padding stays zero for ever
-        if taps_rs and self._pack_regular(wt, buf, n_out, n_in, strides, taps_rs):
-            return buf
-        if taps_rs:
-            it = _lib.PackItem()
-            it.w, it.out, it.n_out, it.n_in, it.ntaps = wt.data_ptr(), buf.data_ptr(), n_out, n_in, len(taps_rs)
-            it.so, it.si, it.sr, it.ss = strides
-            for i, (r, q) in enumerate(taps_rs):
-                it.r[i], it.s[i] = r, q
-            self._pack_items.append(it)
-            self.keep.append(wt)
-        return buf
-
     # positions of lh_igemm's arguments inside a _Call.args tuple
     _IG = dict(desc=0, src=1, pack=2, dst=3, addend=4, addend_mask=5, bias=6, scale=7, shift=8, stats=9)
-
-    def _pack_regular(self, wt, buf, n_out, n_in, strides, taps_rs):
-        """Queue a pack of a plain [d0][d1][kH][kW] weight tensor for the LDS-tiled transposing pack kernel.
-        Returns False when the tensor / strides are not of that form (the stem's staged image, oversize taps)."""
-        if wt.dim() != 4 or not wt.is_contiguous() or len(taps_rs) > 16:
-            return False
-        d0, d1, r, s = wt.shape
-        rs = r * s
-        if 32 * (32 * rs + 2) * self.es > 64 * 1024:
-            return False
-        if tuple(strides) == (d1 * rs, rs, s, 1) and (n_out, n_in) == (d0, d1):
-            row_is_d1 = 0
-        elif tuple(strides) == (rs, d1 * rs, s, 1) and (n_out, n_in) == (d1, d0):
-            row_is_d1 = 1
-        else:
-            return False
-        conv = self._pack_convs.get(id(wt))
-        if conv is None:
-            conv = _lib.PackConv()
-            conv.w, conv.d0, conv.d1, conv.rs, conv.npacks = wt.data_ptr(), d0, d1, rs, 0
-            self._pack_convs[id(wt)] = conv
-            self.keep.append(wt)
-        if conv.npacks >= 5:
-            return False
-        o = conv.packs[conv.npacks]
-        kstep = 128 // self.es
-        o.out, o.row_is_d1, o.ntaps, o.kpad = buf.data_ptr(), row_is_d1, len(taps_rs), (n_in + kstep - 1) // kstep * kstep
-        for i, (rr, ss) in enumerate(taps_rs):
-            o.taps[i] = rr * s + ss
-        conv.npacks += 1
-        return True
-
 
     def _igemm(self, lst, d, src, pack, dst, addend, bias, stats, what, flops=0, produces=None, addend_mask=None):
         self.keep.append(d)
@@ -217,80 +176,17 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             # (networks with parallel branches: gated OUTSIDE their branch regions only -- HRNet's stem, layer1, transitions: 12.93 -> 12.84 ms.
             #  Inside them the members of a batch group run merged tiled launches whose reduce passes are merged too: carrying the gates into
             #  lh_igemm_multi was measured +0.26 ms SLOWER, round 6; a plan computes the same sums whether its branches run as groups or lanes)
-            in_branch = self._emit_group > 1 or self._cur_lane != 0 or getattr(self, "_in_branch", False)
+            in_branch = self._emit_group > 1 or self._cur_lane != 0 or self._in_branch
             gi = self._gate_info.get(id(x)) if (self.opt.bn_gate and first and len(descs) == 1 and self.es == 2 and
                                                 (self.n_lanes == 1 or (self.opt.bn_gate_branches and not in_branch))) else None
             gkind, gbytes = self._gate_kind(gi, x, amask is not None), x.pixels * x.c * self.es
             self._tune([dd], addend=kind, role="dgrad", gate=(gkind, gbytes) if gkind else None)
             cfg = (C.c_int * 5)()
             if gkind and self.lib.lh_igemm_config(C.byref(dd), self.dt, cfg) == 0 and self._cfg_gateable(cfg, gkind, gbytes):
-                # x = relu(BN(raw)) with this convolution as its only consumer -- or a residual tail relu(BN(raw) + r) whose other
-                # consumer, the next tail's identity term, rides in as this launch's masked addend: the launch stores the ReLU-gated
-                # gradient and the BatchNorm-backward partial sums of its tile (the node's backward skips its reduce pass)
-                two = gkind == "mask2"
-                rows = self.lib.lh_igemm_gated_rows(C.byref(dd), self.dt, 2 if two else 1)
-                partial = self._alloc(rows * 2 * x.c, dtype=torch.float32)
-                partial2 = self._alloc(rows * 2 * x.c, dtype=torch.float32) if two else None
-                st = gi["st"]
-                gate = _lib.BnBwdGate(gi["raw"].buf.data_ptr(), st["mean"].data_ptr(), st["invstd"].data_ptr(), st["scale"].data_ptr(),
-                                      st["shift"].data_ptr(), partial.data_ptr(), _ptr(gi.get("mask")))
-                if two:
-                    st2 = gi["st2"]
-                    gate.x2, gate.mean2, gate.invstd2, gate.partial2 = gi["raw2"].buf.data_ptr(), st2["mean"].data_ptr(), st2["invstd"].data_ptr(), partial2.data_ptr()
-                self.keep += [dd, gate]
-                c = _Call(self.lib.lh_igemm_gated, (C.byref(dd), _ptr(dy), _ptr(pk), _ptr(dx), _ptr(addend), _ptr(amask), C.byref(gate), self.dt),
-                          what + " + BN-backward gate" + (" (mask bits)" if gi.get("mask") is not None else ""))
-                c.keep = dd
-                c.ig = dict(src=1, dst=3, addend=4, addend_mask=5)
-                self.bwd.append(c)
-                self._gated[id(x)] = (partial, rows, partial2)
+                self._gated_dgrad(dd, dy, pk, x, dx, addend, amask, gi, gkind, what)
             else:
                 self._igemm(self.bwd, dd, dy, pk, dx, addend, None, None, what, addend_mask=amask)
             yield dd, dd.ntaps
-
-    def _gate_meta(self, dd, x):
-        """(kernel name, extra algorithmic bytes) of the data gradient just emitted when it is a gated launch (lh_igemm_gated): the persistent
-        kernels have gate instantiations of their own (igemm_pw_kernel<.., true, terms>, conv3x3_direct_kernel<.., true, true>), and the
-        epilogue reads the BatchNorm input of every gated term (what the reduce pass of lh_fuse_bwd no longer reads) plus the mask bits."""
-        c = self.bwd[-1]
-        if getattr(c, "fn", None) is not self.lib.lh_igemm_gated:
-            return None, 0.0
-        g = self._gated[id(x)]
-        terms = 2 if len(g) > 2 and g[2] is not None else 1
-        name = self._kname(dd, stats=True)
-        if name.startswith("igemm_pw_kernel"):
-            name = name[:-1] + f", {terms}>"
-        elif name.startswith("conv3x3_direct_kernel"):
-            name = name[:-1] + ", true>"
-        return name, float(terms) * x.pixels * x.c * self.es + (x.pixels * x.c / 8 if "mask" in c.what else 0.0)
-
-    def _gate_kind(self, gi, x, masked_addend):
-        """May the first writer of x.grad, a data gradient, take the BatchNorm-backward gate of x's node (lh_igemm_gated)?  None | 'x' | 'mask'.
-        'x': a single-term node a = relu(BN(raw)) whose only consumer is this convolution.  'mask' (round 6): a residual tail
-        relu(BN(raw) + r) -- this convolution is its only consumer, or the other one is the next tail, whose identity gradient has been
-        folded into this launch as its masked addend."""
-        if gi is None or x.c != x.c_valid:
-            return None
-        uses = len(self._uses.get(id(x), []))
-        if gi.get("mask") is not None:
-            ok = self.opt.bn_gate_tail and (uses == 1 or (uses == 2 and masked_addend))
-            return None if not ok else "mask2" if gi.get("raw2") is not None else "mask"
-        return "x" if uses == 1 else None
-
-    def _cfg_gateable(self, cfg, kind, nbytes):
-        """Does kernel configuration cfg take the gate for a tensor of nbytes?  The tiled kernels up to LH_BN_GATE_MAX_MB (measured,
-        rounds 4-6: beyond it the epilogue's read of raw costs a tile-per-workgroup launch more than the reduce pass it replaces), the
-        persistent kernels (pointwise, direct 3x3: streams of independent waves, the extra read rides with the others) up to
-        LH_BN_GATE_PW_MAX_MB; tails up to LH_BN_GATE_TAIL_MAX_MB on either."""
-        pw, tiled = cfg[2] in (1, 100), (2 <= cfg[2] < 10 or 20 <= cfg[2] < 40)
-        opt, mb = self.opt, nbytes / (1 << 20)
-        if not (tiled or (pw and opt.bn_gate_pw)):
-            return False
-        if kind == "mask2":                # two BatchNorm terms (a projection shortcut): the pointwise kernel only
-            return cfg[2] == 1 and opt.bn_gate_tail2 and mb <= opt.bn_gate_tail_max_mb
-        if kind == "mask":
-            return mb <= (opt.bn_gate_tail_max_mb if pw else min(opt.bn_gate_tail_max_mb, opt.bn_gate_tiled_tail_max_mb))
-        return mb <= (opt.bn_gate_pw_max_mb if pw else opt.bn_gate_max_mb)
 
     def _patch(self, call, relu=None, **ptrs):
         a = list(call.args)
@@ -339,6 +235,32 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         ws = self._alloc(self.lib.lh_channel_sum_workspace_bytes(cout), dtype=torch.uint8)
         return _Call(self.lib.lh_channel_sum_nhwc, (dy.data_ptr(), y.pixels, cout, y.c, gb_.data_ptr(), ws.data_ptr(), self.dt), "bias grad", lane=1)
 
+    def _padded_bias(self, nd, y, cout):
+        """The fp32 bias of convolution node nd padded to y's channel count (refilled with the weight packs); None without a bias."""
+        if not nd["bias"]:
+            return None
+        bias = self._alloc(y.c, dtype=torch.float32, zero=True)
+        self.packs.append(self._copy4(bias[:cout], self.params[nd["bias"]].detach(), "bias pad"))
+        return bias
+
+    def _wgrad_call(self, a, what, slab_bytes, flops, nbytes, wbufs=None, keep_desc=None):
+        """One lh_wgrad_fused call (weight gradient + fold of its pixel splits, argument list ``a``; the slab a[7] is bound by _ws_note) into
+        the weight-gradient list of the node being emitted, which is returned.  wbufs: the tensors behind a's x / dy pointers -- the call
+        may then join a table launch (_table_wgrads); keep_desc: its descriptor -- it may then merge with same-shape launches (_batch_wgrads)."""
+        cw = _Call(self.lib.lh_wgrad_fused, None, what, keep=a[13], lane=1)
+        cw.keep_desc = keep_desc
+        if wbufs is not None:
+            cw.wargs, cw.wbufs = a, wbufs
+
+        def set_ws(ptr):
+            a[7] = ptr
+            cw.args = tuple(a)
+        cw.ws_ent = self._ws_note(set_ws, slab_bytes)
+        wl = self._wl()
+        wl.append(cw)
+        self.profile_meta.append(("bwd", cw, self._kname(a[0]._obj, wgrad=(a[5], a[6])), flops, nbytes))
+        return wl
+
     def _kname(self, d, wgrad=None, stats=False):
         """Kernel instantiation name as rocprofv3 prints it (for roofline attribution)."""
         t = {"fp32": "float", "bf16": "__bf16", "fp16": "_Float16"}[self.precision]
@@ -365,19 +287,22 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             return f"wgrad_ring_kernel<{t}, {a.value}, {b.value}, {wo}, {wi}, {r.value % 10}, {r.value // 10}>"
         return f"wgrad_kernel<{t}, {a.value}, {b.value}, {wo}, {wi}>"
 
-
     def _first_write(self, a):
         """True the first time a gradient buffer is produced in the backward list (every writer calls this once)."""
         n = self._nwrites.get(id(a), 0)
         self._nwrites[id(a)] = n + 1
         return n == 0
 
+    def _alloc_stats(self, y, rows):
+        """The BatchNorm statistics slab of y: ``rows`` rows of [2][C] fp32 partial sums, written by the launches that produce y."""
+        y.stats = self._alloc((self.lib.lh_bn_stats_slab_bytes(rows, y.c) + 3) // 4, dtype=torch.float32)
+        y.stats_rows = rows
+        return y.stats
+
     def _stats_for(self, y, descs):
+        """One slab for the launches of ``descs``; returns the byte offset of each launch's rows."""
         rows = [self.lib.lh_igemm_stats_rows(C.byref(d), self.dt) for d in descs]
-        total = sum(rows)
-        nbytes = self.lib.lh_bn_stats_slab_bytes(total, y.c)
-        y.stats = self._alloc((nbytes + 3) // 4, dtype=torch.float32)
-        y.stats_rows = total
+        self._alloc_stats(y, sum(rows))
         offs, o = [], 0
         for r in rows:
             offs.append(o)
@@ -435,55 +360,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                     self._ready[id(out_act)] = len(self.fwd)      # list position from which this activation is complete
                 bwd_blocks[i] = blk
             self._forced = None
+        self._build_pack_launches()
         # backward list: node blocks in reverse order; accumulate flags resolved in that order
-        if self._pack_items:       # every weight pack of the model is rebuilt by ONE launch
-            arr = (_lib.PackItem * len(self._pack_items))(*self._pack_items)
-            table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-            chunk, kstep = self.lib.lh_pack_chunk_elems(), 128 // self.es
-            c_item, c_start = [], []
-            for i, it in enumerate(self._pack_items):
-                total = (it.n_out + 127) // 128 * 128 * it.ntaps * ((it.n_in + kstep - 1) // kstep * kstep)
-                for s0 in range(0, total, chunk):
-                    c_item.append(i)
-                    c_start.append(s0)
-            t_item = torch.tensor(c_item, dtype=torch.int32, device=self.device)
-            t_start = torch.tensor(c_start, dtype=torch.int64, device=self.device)
-            self.keep += [table, t_item, t_start]
-            self.packs.append(_Call(self.lib.lh_pack_weights_multi,
-                                    (table.data_ptr(), t_item.data_ptr(), t_start.data_ptr(), len(c_item), self.dt), "weight packs"))
-        self._late_packs = None    # (pack buffer pointers of the late group, index of the conv whose first use is the fork point)
-        if self._pack_convs:       # regular conv / deconv weights: the tiled transposing pack kernel
-            convs = list(self._pack_convs.values())        # in the order the forward pass first uses them
-            # Training plans split the launch: the layers the forward pass reaches LATE and that hold most of the bytes
-            # (R50: stage 4 + the head's transposed convolutions, 75 % of the parameters) are packed by a second launch that
-            # runs under the latency-bound middle of the forward pass instead of beside the HBM-bound stem and stage 1.
-            groups = [convs]
-            if self.with_bwd and len(convs) >= 16 and self.opt.late_pack:
-                size = [cv.d0 * cv.d1 * cv.rs for cv in convs]
-                total, acc, cut = sum(size), 0, len(convs)
-                while cut > 0 and acc + size[cut - 1] <= 0.8 * total:
-                    cut -= 1
-                    acc += size[cut]
-                if 8 <= cut < len(convs) and acc >= 0.5 * total:
-                    groups = [convs[:cut], convs[cut:]]
-                    fork_conv = max(1, cut - max(8, int(0.35 * len(convs))))
-                    self._late_packs = ({convs[i].packs[k].out for i in range(cut, len(convs)) for k in range(convs[i].npacks)},
-                                        {convs[fork_conv].packs[k].out for k in range(convs[fork_conv].npacks)})
-            for gi, grp in enumerate(groups):
-                arr = (_lib.PackConv * len(grp))(*grp)
-                table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-                c_conv, c_t0, c_t1 = [], [], []
-                for i, cv in enumerate(grp):
-                    for a in range((cv.d0 + 31) // 32):
-                        for b in range((cv.d1 + 31) // 32):
-                            c_conv.append(i); c_t0.append(a); c_t1.append(b)
-                tabs = [torch.tensor(v, dtype=torch.int32, device=self.device) for v in (c_conv, c_t0, c_t1)]
-                self.keep += [table] + tabs
-                call = _Call(self.lib.lh_pack_weights_tiled,
-                             (table.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(), len(c_conv),
-                              max(cv.rs for cv in grp), self.dt), "weight packs (tiled)" + (", late group" if gi else ""))
-                call.lane = gi           # 1 = the late group (refresh_packs(overlap=True) defers it to the 'packfork2' marker)
-                self.packs.append(call)
         self.bwd_marks = []        # (end index in self.bwd, parameter names whose gradient is final there)
         if self.with_bwd:
             gcount = self._n_groups
@@ -555,26 +433,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         self._attach_l2_touch()
         if self._n_groups:
             self._merge_groups()
-        # where the forward list first reads a pack written by the tiled pack launch (refresh_packs(overlap=True))
-        self._pack_event, self._packjoin_at, self._pack_stream = None, None, None
-        if self.with_bwd and any(getattr(c, "fn", None) is self.lib.lh_pack_weights_tiled for c in self.packs):
-            convs = (self.lib.lh_igemm, self.lib.lh_igemm_multi, self.lib.lh_igemm_phases, self.lib.lh_igemm_phases_head)
-            for i, c in enumerate(self.fwd):
-                if isinstance(c, _Call) and any(c.fn is f for f in convs) and not c.what.endswith("stem fwd"):
-                    self.fwd.insert(i, _Marker("packjoin"))
-                    self._packjoin_at = i
-                    self._pack_stream = torch.cuda.Stream(device=self.device)
-                    break
-            if self._late_packs is not None and self._packjoin_at is not None:
-                late, fork_at = self._late_packs
-                first = lambda ptrs: next((i for i, c in enumerate(self.fwd) if isinstance(c, _Call) and self._call_packs(c) & ptrs), None)
-                j, f = first(late), first(fork_at)
-                if j is not None and f is not None and self._packjoin_at < f < j:
-                    self.fwd.insert(j, _Marker("packjoin2"))
-                    self.fwd.insert(f, _Marker("packfork2"))
-                else:
-                    self._late_packs = None
-        self._pack_late, self._pack_event2 = None, None
+        self._place_pack_markers()
 
     def _attach_l2_touch(self):
         """Training plans: an elementwise BatchNorm / ReLU pass (lh_fuse_fwd) that is followed on its stream by a tiled
@@ -619,24 +478,11 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         attach(self.bwd, lib.lh_fuse_bwd, 2)
         self._n_l2_touch = n
 
-    def _call_packs(self, c):
-        """Pack buffers a forward convolution call reads (addresses)."""
-        lib = self.lib
-        if c.fn is lib.lh_igemm:
-            return {c.args[2]}
-        if c.fn is lib.lh_igemm_multi:
-            return {c.args[0][i].wpack for i in range(c.args[1])}
-        if c.fn is lib.lh_igemm_phases or c.fn is lib.lh_igemm_phases_head:
-            return {c.args[3][i] for i in range(c.args[1])}
-        return set()
-
     def _c_nop(self, nd, blk):
         pass
 
-
     def _c_fork(self, nd, blk):
         self.fwd.append(_Marker("fork"))
-        self._regions = getattr(self, "_regions", [])
         self._regions.append([self.fwd[-1], None])
         blk.append(lambda: self.bwd.append(_Marker("join")))          # backward walks the region in reverse
 
@@ -651,7 +497,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         if not self.use_lanes:
             return False
         i = self.fwd.index(call)
-        return any(r[1] is not None and self.fwd.index(r[0]) < i < self.fwd.index(r[1]) for r in getattr(self, "_regions", []))
+        return any(r[1] is not None and self.fwd.index(r[0]) < i < self.fwd.index(r[1]) for r in self._regions)
 
     def _c_input(self, a, blk):
         pass        # the consumer (stem conv) owns the image transform
@@ -664,7 +510,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
 
     def _c_output(self, nd, blk):
         y = nd["y"]
-        if getattr(self, "_head_fused", False):           # the fused head wrote the fp32 NCHW heat-map itself (_fuse_head)
+        if self._head_fused:           # the fused head wrote the fp32 NCHW heat-map itself (_fuse_head)
             return
         self.out_nchw = self._alloc(y.n, y.c_valid, y.h, y.w, dtype=torch.float32)
         self.fwd.append(_Call(self.lib.lh_nhwc_to_nchw_f32, (y.buf.data_ptr(), self.out_nchw.data_ptr(), y.n, y.h, y.w, y.c_valid, y.c, self.dt), "output transform"))
@@ -677,18 +523,13 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                 self.bwd.append(_Call(self.lib.lh_nchw_f32_to_nhwc, (self.dout_nchw.data_ptr(), g.data_ptr(), y.n, y.h, y.w, y.c_valid, y.c, self.dt), "dheat transform"))
             blk.append(emit)
 
-
     # ---- convolution ---------------------------------------------------------------------------
     def _c_conv(self, nd, blk):
         x, y, k, s, p = nd["x"], nd["y"], nd["k"], nd["s"], nd["p"]
         wt = self.params[nd["w"] + ".weight"]
         cout, cin = wt.shape[0], wt.shape[1]
         ybuf = self._act_buf(y)
-        bias = None
-        if nd["bias"]:
-            bias = self._alloc(y.c, dtype=torch.float32, zero=True)
-            bsrc = self.params[nd["bias"]]
-            self.packs.append(self._copy4(bias[:cout], bsrc.detach(), "bias pad"))
+        bias = self._padded_bias(nd, y, cout)
         all_rs = [(r, q) for r in range(k) for q in range(k)]
         if x.is_image:
             self._c_stem(nd, blk, bias)
@@ -736,20 +577,9 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             dy = self._act_grad(y)
             # weight gradient + fold of the pixel splits as ONE C-ABI call (wgrad kernel, then reduce kernel)
             a = [C.byref(d), 0, xbuf.data_ptr(), dy.data_ptr(), y.c, y.c, cin, 0, gtmp.data_ptr(), cin * k * k, k * k, k, 1, rs_arr, 0, self.dt]
-            tail = 1
-            cw = _Call(self.lib.lh_wgrad_fused, None, nd["w"] + " wgrad", keep=rs_arr, lane=1)
-            cw.keep_desc = d
-            cw.wargs, cw.wbufs = a, (xbuf, dy)
-
-            def set_ws(ptr, cw=cw, a=a):
-                a[7] = ptr
-                cw.args = tuple(a)
-            cw.ws_ent = self._ws_note(set_ws, slab_bytes)
-            wl = self._wl()
-            wl.append(cw)
-            self.profile_meta.append(("bwd", wl[-1], self._kname(d, (y.c, cin)), flops, (x.pixels * x.c + y.pixels * y.c) * self.es))
+            wl = self._wgrad_call(a, nd["w"] + " wgrad", slab_bytes, flops, (x.pixels * x.c + y.pixels * y.c) * self.es, wbufs=(xbuf, dy), keep_desc=d)
             if pad_out:
-                wl.append(self._copy4(gw, gtmp[:cout].view_as(gw), "head grad crop", lane=tail))
+                wl.append(self._copy4(gw, gtmp[:cout].view_as(gw), "head grad crop", lane=1))
             if nd["bias"]:
                 gb_ = self.grads[nd["bias"]]
                 if y is self.out_act:      # the head: reduce the contiguous fp32 NCHW gradient instead of strided bf16
@@ -798,8 +628,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             # training stem (pose_resnet.py:151-152) on the direct kernel: weights in registers, a tile's input patch in LDS,
             # raw convolution output + one statistics row per workgroup (stem_pool.hip, lh_stem_conv)
             rows_ = self.lib.lh_stem_conv_rows(x.n, y.h, y.w)
-            y.stats = self._alloc((self.lib.lh_bn_stats_slab_bytes(rows_, y.c) + 3) // 4, dtype=torch.float32)
-            y.stats_rows = rows_
+            self._alloc_stats(y, rows_)
             self.keep.append(d)
             c_ = _Call(self.lib.lh_stem_conv, (img.data_ptr(), x.n, hp, wp, pack.data_ptr(), ybuf.data_ptr(), y.stats.data_ptr(), y.h, y.w, self.dt),
                        nd["w"] + " stem fwd (direct)")
@@ -844,17 +673,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                 a = [C.byref(dw), k, img.data_ptr(), dy.data_ptr(), y.c, y.c, k * kr, 0, gstage.data_ptr(), k * kr, 1, 0, 0, rs_arr, 0, self.dt]
             else:
                 a = [C.byref(d), 0, img.data_ptr(), dy.data_ptr(), y.c, y.c, kr, 0, gstage.data_ptr(), k * kr, 1, kr, 0, rs_arr, 0, self.dt]
-            tail = 1
-            cw = _Call(self.lib.lh_wgrad_fused, None, "stem wgrad", keep=rs_arr, lane=1)
-
-            def set_ws(ptr):
-                a[7] = ptr
-                cw.args = tuple(a)
-            cw.ws_ent = self._ws_note(set_ws, slab_bytes)
-            wl = self._wl()
-            wl.append(cw)
-            self.profile_meta.append(("bwd", wl[-1], self._kname(dw, (y.c, n_in_w)), flops, (x.pixels * 4 + y.pixels * y.c) * self.es))
-            wl.append(self._copy4(gw, gstage[:, :, :k, :3].permute(0, 3, 1, 2), "stem grad unstage", lane=tail))
+            wl = self._wgrad_call(a, "stem wgrad", slab_bytes, flops, (x.pixels * 4 + y.pixels * y.c) * self.es)
+            wl.append(self._copy4(gw, gstage[:, :, :k, :3].permute(0, 3, 1, 2), "stem grad unstage", lane=1))
         blk.append(emit)
 
     # ---- transposed convolution ------------------------------------------------------------------
@@ -864,11 +684,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         cin, cout = wt.shape[0], wt.shape[1]
         xbuf, ybuf = self._act_buf(x), self._act_buf(y)
         all_rs = [(r, q) for r in range(k) for q in range(k)]
-        bias = None
-        if nd["bias"]:
-            bias = self._alloc(y.c, dtype=torch.float32, zero=True)
-            bsrc = self.params[nd["bias"]]
-            self.packs.append(self._copy4(bias[:cout], bsrc.detach(), "bias pad"))
+        bias = self._padded_bias(nd, y, cout)
         descs, packs = [], []
         for ph in range(2):
             for pw in range(2):
@@ -887,9 +703,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         if prow > 0:                          # the four sub-pixel phases as ONE launch
             stats = None
             if id(y) in self._bn_inputs and self.training:
-                nbytes = self.lib.lh_bn_stats_slab_bytes(4 * prow, y.c)
-                y.stats, y.stats_rows = self._alloc((nbytes + 3) // 4, dtype=torch.float32), 4 * prow
-                stats = y.stats
+                stats = self._alloc_stats(y, 4 * prow)
             self._igemm_phases(self.fwd, descs, xbuf, packs, ybuf, None, bias, stats, nd["w"] + " deconv fwd", produces=y)
             self.profile_meta.append(("fwd", self.fwd[-1], self._kname(descs[0]), 2.0 * x.pixels * cin * cout * k * k,
                                       (x.pixels * x.c + y.pixels * y.c) * self.es))
@@ -924,16 +738,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         def emit():
             dy = self._act_grad(y)
             a = [C.byref(dg), 0, dy.data_ptr(), xbuf.data_ptr(), x.c, cin, cout, 0, gw.data_ptr(), cout * k * k, k * k, k, 1, rs_arr, 0, self.dt]
-            cw = _Call(self.lib.lh_wgrad_fused, None, nd["w"] + " wgrad", keep=rs_arr, lane=1)
-            cw.wargs, cw.wbufs = a, (dy, xbuf)
-
-            def set_ws(ptr):
-                a[7] = ptr
-                cw.args = tuple(a)
-            cw.ws_ent = self._ws_note(set_ws, slab_bytes)
-            wl = self._wl()
-            wl.append(cw)
-            self.profile_meta.append(("bwd", wl[-1], self._kname(dg, (cin, cout)), flops, (x.pixels * x.c + y.pixels * y.c) * self.es))
+            wl = self._wgrad_call(a, nd["w"] + " wgrad", slab_bytes, flops, (x.pixels * x.c + y.pixels * y.c) * self.es, wbufs=(dy, xbuf))
             if nd["bias"]:
                 gb_ = self.grads[nd["bias"]]
                 wl.append(self._bias_grad(dy, y, cout, gb_))
@@ -986,17 +791,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
         if relu and self.with_bwd and len(terms) > 1:
             relu_bits = self._alloc(out.pixels * c // (16 // self.es), dtype=torch.uint8)
             fd.relu_mask = relu_bits.data_ptr()
-        if self.training and self.with_bwd and relu and len(terms) == 1 and terms[0][1] is not None and terms[0][2] == 0:
-            self._gate_info[id(out)] = dict(raw=terms[0][0], st=bn_state[0])
-        bn_terms = [i for i, (_, bn, _) in enumerate(terms) if bn is not None]
-        if (self.training and self.with_bwd and relu_bits is not None and len(terms) == 2 and len(bn_terms) == 1
-                and all(l == 0 for _, _, l in terms) and all(a.c == out.c for a, _, _ in terms)):
-            # a residual tail relu(BN(raw) + identity): its sign is in the mask bits
-            self._gate_info[id(out)] = dict(raw=terms[bn_terms[0]][0], st=bn_state[bn_terms[0]], mask=relu_bits)
-        if (self.training and self.with_bwd and relu_bits is not None and len(terms) == 2 and len(bn_terms) == 2
-                and all(l == 0 for _, _, l in terms) and all(a.c == out.c for a, _, _ in terms)):
-            # ... with a projection shortcut: relu(BN(raw) + BN2(raw2))
-            self._gate_info[id(out)] = dict(raw=terms[0][0], st=bn_state[0], mask=relu_bits, raw2=terms[1][0], st2=bn_state[1])
+        if relu:
+            self._note_gate(out, terms, bn_state, relu_bits)
         self.fwd.append(_Call(self.lib.lh_fuse_fwd, (C.byref(fd), obuf.data_ptr(), out.n, out.h, out.w, c, self.dt), "fuse fwd"))
         if self.training and relu and len(terms) == 1 and terms[0][1] is not None and terms[0][2] == 0 and relu_bits is None:
             # what a max-pool that follows needs to take this node's elementwise pass over (_c_maxpool)
@@ -1053,7 +849,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             passes = ((1 if pre is not None else 2) * (1 + n_bn) if n_bn else 1) + n_dx
             self.profile_meta.append(("bwd", self.bwd[-1], "fuse_bwd(all kernels)", 0.0, float(passes) * out.pixels * c * self.es))
             # what SURVEY 8(d)'s traffic model itself charges to the BatchNorm backward: ONE re-read of y per BatchNorm term
-            self.bn_bwd_8d_bytes = getattr(self, "bn_bwd_8d_bytes", 0.0) + float(n_bn) * out.pixels * c * self.es
+            self.bn_bwd_8d_bytes += float(n_bn) * out.pixels * c * self.es
         blk.append(emit)
 
     def _next_writer_is_conv(self, a, nd):
@@ -1065,7 +861,6 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             return False
         kind, nxt = uses[idx[0] - 1]
         return kind in ("conv", "deconv") and a.c == a.c_valid
-
 
     def _c_maxpool(self, nd, blk):
         x, y = nd["x"], nd["y"]
@@ -1106,10 +901,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
                 # BatchNorm-backward partial sums (the node's backward skips its reduce pass), as lh_igemm_gated does for convolutions
                 rows = self.lib.lh_maxpool3x3s2_bwd_gated_rows(x.n, x.h, x.w, x.c, self.dt)
                 partial = self._alloc(rows * 2 * x.c, dtype=torch.float32)
-                st = gi["st"]
-                gate = _lib.BnBwdGate(gi["raw"].buf.data_ptr(), st["mean"].data_ptr(), st["invstd"].data_ptr(), st["scale"].data_ptr(),
-                                      st["shift"].data_ptr(), partial.data_ptr())
-                self.keep.append(gate)
+                gate = self._make_gate(gi, partial)
                 self.bwd.append(_Call(self.lib.lh_maxpool3x3s2_bwd_gated, (dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), C.byref(gate), x.n, x.h, x.w, x.c,
                                                                          self.dt), "maxpool bwd + BN-backward gate"))
                 self._gated[id(x)] = (partial, rows)
@@ -1141,161 +933,15 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites):
             self.jitter_order = torch.full((self.n, 4), -1, dtype=torch.int32, device=self.device)
             ws_j = self._alloc(self.lib.lh_image_jitter_workspace_bytes(self.n), dtype=torch.uint8)
             self.keep.append(self.jitter_order)
+        # one launch: the plain pipeline, + ColorJitter, or + the affine warp (which takes the jitter operands too, null = none)
+        jit = (self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr()) if jitter else (None, None, None)
         if warp:
-            self.fwd[self._image_call_index] = _Call(self.lib.lh_image_u8_warp_to_nhwc4, (
-                self.img_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, hs, ws, self.h, self.w, self.img_pad, self.img_wp,
-                m3, s3, self.warp_inv.data_ptr(), self.jitter_factors.data_ptr() if jitter else None,
-                self.jitter_order.data_ptr() if jitter else None, ws_j.data_ptr() if jitter else None, self.dt),
-                "uint8 input pipeline + affine warp" + (" + ColorJitter" if jitter else ""))
-            return self.img_u8
-        if jitter:
-            self.fwd[self._image_call_index] = _Call(self.lib.lh_image_u8_jitter_to_nhwc4, (
-                self.img_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, hs, ws, self.h, self.w, self.img_pad, self.img_wp,
-                m3, s3, self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr(), self.dt),
-                "uint8 input pipeline + ColorJitter")
-            return self.img_u8
-        self.fwd[self._image_call_index] = _Call(self.lib.lh_image_u8_to_nhwc4, (
+            fn, extra, what = self.lib.lh_image_u8_warp_to_nhwc4, (self.warp_inv.data_ptr(),) + jit, "uint8 input pipeline + affine warp"
+        elif jitter:
+            fn, extra, what = self.lib.lh_image_u8_jitter_to_nhwc4, jit, "uint8 input pipeline"
+        else:
+            fn, extra, what = self.lib.lh_image_u8_to_nhwc4, (), "uint8 input pipeline"
+        self.fwd[self._image_call_index] = _Call(fn, (
             self.img_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, hs, ws, self.h, self.w, self.img_pad, self.img_wp,
-            m3, s3, self.dt), "uint8 input pipeline")
+            m3, s3) + extra + (self.dt,), what + (" + ColorJitter" if jitter else ""))
         return self.img_u8
-
-    # ------------------------------------------------------------------ run
-    def refresh_packs(self, stream, overlap=False, side_work=None):
-        """Rebuild the device-side weight packs from the parameter arena.  overlap=True (the captured training step): the
-        one large launch -- the tiled transposing pack of every regular convolution, ~0.12 ms -- runs on a side stream
-        under the image transform, the stem and the pool; the forward list waits for it at its 'packjoin' marker, just
-        before the first launch that reads a regular pack.  side_work(stream): more work for that side stream that only
-        depends on the step's inputs (the target render); returns True when it was run there."""
-        side = getattr(self, "_pack_stream", None)
-        if not overlap or side is None or self._packjoin_at is None:
-            for c in self.packs:
-                c(stream)
-            return False
-        main = torch.cuda.current_stream()
-        assert main.cuda_stream == stream
-        side.wait_event(main.record_event())
-        self._pack_late = None
-        for c in self.packs:
-            if c.fn is self.lib.lh_pack_weights_tiled:
-                if c.lane == 1 and self._late_packs is not None:
-                    self._pack_late = c          # launched when the forward list reaches its 'packfork2' marker
-                else:
-                    c(side.cuda_stream)
-            else:
-                c(stream)
-        if side_work is not None:
-            side_work(side.cuda_stream)
-        self._pack_event = side.record_event()
-        return side_work is not None
-
-    def _run_lanes(self, calls, stream):
-        """Launch `calls` with the independent branch chains (stream lane > 0) on side streams: a lane's first launch
-        after a fork waits for the fork's event on the main stream, the join makes the main stream wait for every lane
-        used since; outside fork/join regions (and at the end of the slice) everything is ordered on the main stream.
-        Works eagerly and under hipGraph capture (the side streams join the capture through the events)."""
-        main = torch.cuda.current_stream()
-        assert main.cuda_stream == stream, "lanes need the launch stream to be torch's current stream"
-        ev, forked, used = None, set(), set()
-        wev, wused = {}, set()                 # weight-gradient side streams: pending event per stream, streams used
-        for c in calls:
-            if isinstance(c, _Marker):
-                if c.kind == "packjoin":
-                    if self._pack_event is not None:
-                        main.wait_event(self._pack_event)
-                        self._pack_event = None
-                elif c.kind == "packfork2":      # the late pack group starts here, on the pack stream, under the launches that follow
-                    if self._pack_late is not None:
-                        self._pack_stream.wait_event(main.record_event())
-                        self._pack_late(self._pack_stream.cuda_stream)
-                        self._pack_event2 = self._pack_stream.record_event()
-                        self._pack_late = None
-                elif c.kind == "packjoin2":
-                    if self._pack_event2 is not None:
-                        main.wait_event(self._pack_event2)
-                        self._pack_event2 = None
-                elif c.kind == "wfork":          # the deferred weight gradients that follow may start once their source
-                    src = main if c.lane == 0 else self._lane_streams[c.lane]      # stream got here
-                    wev[c.slane] = src.record_event()
-                elif c.kind == "fork":
-                    ev, forked = main.record_event(), set()
-                else:
-                    for L in used:
-                        main.wait_stream(self._lane_streams[L])
-                    ev, used = None, set()
-                continue
-            L = c.slane
-            if L == 0:
-                c(stream)
-                continue
-            if L < 0:                          # deferred weight-gradient group
-                s = self._lane_streams[L]
-                e = wev.pop(L, None)
-                if e is not None:
-                    s.wait_event(e)
-                elif L not in wused:
-                    s.wait_stream(main)        # slice starts inside a group (data-parallel segments)
-                wused.add(L)
-                c(s.cuda_stream)
-                continue
-            s = self._lane_streams.get(L)
-            if s is None:
-                s = self._lane_streams[L] = torch.cuda.Stream()
-            if L not in forked:
-                if ev is not None:
-                    s.wait_event(ev)
-                else:
-                    s.wait_stream(main)
-                forked.add(L)
-            used.add(L)
-            c(s.cuda_stream)
-        for L in used | wused:
-            main.wait_stream(self._lane_streams[L])
-
-    def _mirrored_forward(self):
-        """The forward list with the image launch replaced by lh_nhwc4_mirror on img_nhwc4: the pass reads the input of the
-        previous forward mirrored horizontally (flip test, runtime.InferStep(flip_test=True)); the rest of the list is the
-        plain pass's, so a training-mode plan normalises with this pass's batch statistics and updates the running ones again."""
-        i = self._image_call_index
-        img = self.fwd[i]
-        assert isinstance(img, _Call) and img.args[1] == self.img_nhwc4.data_ptr(), "the image launch moved in the forward list"
-        self._mirror_call.slane = img.slane
-        return self.fwd[:i] + [self._mirror_call] + self.fwd[i + 1:]
-
-    def run_forward(self, stream, mirrored=False):
-        """mirrored=True: the forward of the horizontal mirror of the image the previous forward read (_mirrored_forward)."""
-        calls = self._mirrored_forward() if mirrored else self.fwd
-        if self.use_lanes:
-            return self._run_lanes(calls, stream)
-        for c in calls:
-            if not isinstance(c, _Marker):
-                c(stream)
-            elif c.kind == "packjoin" and self._pack_event is not None:
-                torch.cuda.current_stream().wait_event(self._pack_event)
-                self._pack_event = None
-            elif c.kind == "packfork2" and self._pack_late is not None:
-                self._pack_late(stream)              # no side streams in this plan: the late group runs in place
-                self._pack_late = None
-
-    def run_backward(self, stream, lo=0, hi=None):
-        """Run bwd[lo:hi] (a segment of the backward list: data-parallel plans replay it bucket by bucket)."""
-        calls = self.bwd[lo:hi]
-        if self.use_lanes:
-            return self._run_lanes(calls, stream)
-        for c in calls:
-            if not isinstance(c, _Marker):
-                c(stream)
-
-    def forward(self, images, repack=True):
-        """images: fp32 NCHW on the device.  Returns the plan's fp32 NCHW heatmap buffer."""
-        if tuple(images.shape) != (self.n, 3, self.h, self.w):
-            raise _lib.LightHandError(f"plan was built for {(self.n, 3, self.h, self.w)}, got {tuple(images.shape)}")
-        self.img_nchw.copy_(images)
-        stream = torch.cuda.current_stream().cuda_stream
-        if repack:
-            self.refresh_packs(stream)
-        self.run_forward(stream)
-        return self.out_nchw
-
-    def backward(self, dheat):
-        self.dout_nchw.copy_(dheat)
-        self.run_backward(torch.cuda.current_stream().cuda_stream)

@@ -164,7 +164,7 @@ class InferRewrites:
         self.profile_meta = [m for m in self.profile_meta if m[1] not in (c1, c2, c3)]
         self.profile_meta.append(("fwd", fused, "bottleneck_infer_kernel", flops, (x.pixels * x.c + 2 * out.pixels * out.c) * self.es))
         self._producers[id(out)] = [fused]
-        self._n_fused_bottlenecks = getattr(self, "_n_fused_bottlenecks", 0) + 1
+        self._n_fused_bottlenecks += 1
         return True
 
     def _fuse_stem_pool(self, nd):
