@@ -492,6 +492,15 @@ int lh_mse_heatmap(const float* pred, const float* target, long numel, float* lo
  * weight > 0 and a zero map otherwise (upstream's `if v > 0.5:`); with vis == NULL it is lh_gaussian_target's everywhere. */
 int lh_gaussian_target_w(const float* joints, int jstride, const float* vis, int vstride, const float* patch, int radius,
                          float* target, float* weight, int b, int j, int size, void* stream);
+/* DARK's unbiased target encoding (Zhang et al. 2020, upstream generate_target; an opt-in extension without a reference
+ * oracle): the window, the skip test and the weight rule of lh_gaussian_target / lh_gaussian_target_w -- window of
+ * (2 * radius + 1)^2 cells centred on mx = (int)(jx * 0.25f + 0.5f), weight = (vis > 0.5 ? vis : 0) * in_frame, a zero map where
+ * the weight is 0, vis == NULL = 1 -- but the value inside the window is the Gaussian around the joint's real-valued position,
+ * expf(-((x - jx * 0.25f)^2 + (y - jy * 0.25f)^2) / (2 * sigma^2)), evaluated per pixel in fp32 (no patch table).
+ * weight == NULL: no weight output and no visibility test (vis is not read).  A joint on a cell centre jx = 4k, k >= 0, gets
+ * lh_gaussian_target's map up to the rounding of expf (for k < 0 the truncation toward zero centres the window on k + 1). */
+int lh_gaussian_target_sub(const float* joints, int jstride, const float* vis, int vstride, int radius, float sigma,
+                           float* target, float* weight, int b, int j, int size, void* stream);
 /* JointsMSELoss(use_target_weight=True) (topk == 0) and JointsOHKMMSELoss (1 <= topk <= j).  pred / target / grad fp32
  * [b][j][hw], weight fp32 [b][j] or NULL (ones), joint_loss optional fp32 [b][j], grad optional, grad_scale an optional
  * device scalar read on the device like lh_mse_heatmap's.  Per plane, fp64 in a fixed order (no atomics: every call gives the
@@ -520,6 +529,22 @@ int lh_heatmap_soft_argmax(const float* heatmaps, int bj, int h, int w, float be
                            void* stream);
 int lh_heatmap_refine(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w,
                       float scale, float* preds, void* stream);
+/* Opt-in DARK decode (Zhang et al. 2020: the published get_final_preds -> gaussian_blur -> taylor chain; NOT in the
+ * reference), the sibling of lh_heatmap_refine: idx / maxvals / preds are the outputs of lh_heatmap_argmax or
+ * lh_heatmap_flip_merge at the same `scale`; preds is updated in place, the heat-maps are only read.  Per plane, in fp32:
+ *   skip     preds stays as it is unless maxvals > 0 and the peak (px, py) satisfies 1 < px < w-2 && 1 < py < h-2;
+ *   blur     B = the plane under a separable, zero-padded Gaussian of blur_kernel taps g[t] = exp(-(t-c)^2 / (2 s^2)) / sum,
+ *            c = (k-1)/2, s = 0.3*((k-1)*0.5 - 1) + 0.8 (cv2.getGaussianKernel's formula; evaluated on the host in fp64 and
+ *            rounded to fp32); rows first, then columns, the taps accumulated in index order;
+ *   log      C = log(max(B * (maxval / max(B)), 1e-10f)), max(B) over the whole blurred plane;
+ *   taylor   dx = 0.5(C[py][px+1] - C[py][px-1]), dxx = 0.25(C[py][px+2] - 2C[py][px] + C[py][px-2]), dy / dyy likewise,
+ *            dxy = 0.25(C[py+1][px+1] - C[py-1][px+1] - C[py+1][px-1] + C[py-1][px-1]), det = dxx*dyy - dxy^2;
+ *            preds = ((px, py) - H^-1 (dx, dy)) * scale when det != 0 and both offsets are finite, unchanged otherwise.
+ * The finiteness guard is this project's; OpenCV's fixed tap tables for kernels <= 7 are not reproduced (the formula above
+ * is used for every size).  One workgroup per plane with the plane in LDS, no atomics: two calls give the same bits.
+ * Supported for h * w <= 96 * 96 and blur_kernel odd in 3..17 (LH_ERR_ARG otherwise, before any launch). */
+int lh_heatmap_dark(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w, int blur_kernel,
+                    float scale, float* preds, void* stream);
 /* Flip test's flip-back and merge (SimpleBaseline's flip_back + SHIFT_HEATMAP + average, TEST.FLIP_TEST of the reference's
  * configs) followed by lh_heatmap_argmax's decode, in one launch.  a = heat-maps of the plain input, m = those of the
  * horizontally mirrored input, fp32 [b*j][h][w]; f[y][x] = m[y][w-x] for x >= 1 and f[y][0] = m[y][w-1] when `shift`,

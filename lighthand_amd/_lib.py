@@ -167,6 +167,7 @@ SIGNATURES = {
     "lh_mse_workspace_bytes": (_SZ, [_L]),
     "lh_mse_heatmap": (_I, [_P, _P, _L, _P, _P, _P, _P, _P]),
     "lh_gaussian_target_w": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "lh_gaussian_target_sub": (_I, [_P, _I, _P, _I, _I, _F, _P, _P, _I, _I, _I, _P]),
     "lh_joints_mse_workspace_bytes": (_SZ, [_I, _I]),
     "lh_joints_mse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "lh_heatmap_argmax": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _P]),
@@ -177,6 +178,7 @@ SIGNATURES = {
     "lh_pck_curve": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "lh_heatmap_soft_argmax": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
     "lh_heatmap_refine": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    "lh_heatmap_dark": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
     "lh_heatmap_flip_merge": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "lh_keypoint_metrics": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "lh_comm_unique_id": (_I, [_P]),

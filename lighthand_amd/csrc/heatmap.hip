@@ -6,9 +6,12 @@
 // visibility x "some part of the patch lies inside the map", a joint of weight 0 gets a zero map, and the thread that owns pixel
 // (0, 0) of a plane writes that plane's weight.  A compile-time switch: the unweighted instantiation never reads vis / weight
 // (passed as null) and keeps the resource table it had as a kernel of its own (tools/kres.py).
-template <bool WEIGHTED>
+// SUB (lh_gaussian_target_sub, DARK's unbiased encoding): the same window, skip test and weight, but the value inside the window
+// is the Gaussian around the joint's real-valued heat-map position, one expf per pixel; `patch` is not read.  A second
+// compile-time switch, so the two quantised instantiations keep their code.
+template <bool WEIGHTED, bool SUB = false>
 __global__ void gaussian_target_kernel(const float* joints, int jstride, const float* vis, int vstride, const float* patch,
-                                       int radius, float* target, float* weight, int bj, int size) {
+                                       int radius, float* target, float* weight, int bj, int size, float sigma) {
     const long total = (long)bj * size * size;
     const int pw = 2 * radius + 1;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -29,7 +32,14 @@ __global__ void gaussian_target_kernel(const float* joints, int jstride, const f
             draw = w > 0.f;
         }
         float out = 0.f;
-        if (draw && x >= x0 && x < x1 && y >= y0 && y < y1) out = patch[(y - y0) * pw + (x - x0)];
+        if (draw && x >= x0 && x < x1 && y >= y0 && y < y1) {
+            if constexpr (SUB) {
+                const float dx = (float)x - jx * 0.25f, dy = (float)y - jy * 0.25f;
+                out = expf(-(dx * dx + dy * dy) / (2.f * sigma * sigma));
+            } else {
+                out = patch[(y - y0) * pw + (x - x0)];
+            }
+        }
         target[i] = out;
         if constexpr (WEIGHTED)
             if (x == 0 && y == 0) weight[j] = w;
@@ -79,7 +89,7 @@ extern "C" int lh_gaussian_target(const float* joints, int jstride, const float*
     LH_REQUIRE(joints && patch && target && jstride >= 2 && b > 0 && j > 0 && size > 0 && radius >= 0,
                "lh_gaussian_target: bad arguments");
     hipLaunchKernelGGL(gaussian_target_kernel<false>, dim3(lh_grid((long)b * j * size * size, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       joints, jstride, (const float*)nullptr, 0, patch, radius, target, (float*)nullptr, b * j, size);
+                       joints, jstride, (const float*)nullptr, 0, patch, radius, target, (float*)nullptr, b * j, size, 0.f);
     LH_LAUNCH_CHECK("gaussian_target launch");
     return LH_OK;
 }
@@ -89,8 +99,23 @@ extern "C" int lh_gaussian_target_w(const float* joints, int jstride, const floa
     LH_REQUIRE(joints && patch && target && weight && jstride >= 2 && (!vis || vstride >= 1) && b > 0 && j > 0 && size > 0 && radius >= 0,
                "lh_gaussian_target_w: bad arguments");
     hipLaunchKernelGGL(gaussian_target_kernel<true>, dim3(lh_grid((long)b * j * size * size, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       joints, jstride, vis, vstride, patch, radius, target, weight, b * j, size);
+                       joints, jstride, vis, vstride, patch, radius, target, weight, b * j, size, 0.f);
     LH_LAUNCH_CHECK("gaussian_target_w launch");
+    return LH_OK;
+}
+
+extern "C" int lh_gaussian_target_sub(const float* joints, int jstride, const float* vis, int vstride, int radius, float sigma,
+                                      float* target, float* weight, int b, int j, int size, void* stream) {
+    LH_REQUIRE(joints && target && jstride >= 2 && (!vis || vstride >= 1) && b > 0 && j > 0 && size > 0 && radius >= 0 && sigma > 0.f,
+               "lh_gaussian_target_sub: bad arguments (sigma must be positive)");
+    const dim3 grid(lh_grid((long)b * j * size * size, 4096));
+    if (weight)
+        hipLaunchKernelGGL((gaussian_target_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, joints, jstride, vis, vstride,
+                           (const float*)nullptr, radius, target, weight, b * j, size, sigma);
+    else
+        hipLaunchKernelGGL((gaussian_target_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, joints, jstride,
+                           (const float*)nullptr, 0, (const float*)nullptr, radius, target, (float*)nullptr, b * j, size, sigma);
+    LH_LAUNCH_CHECK("gaussian_target_sub launch");
     return LH_OK;
 }
 
@@ -372,6 +397,131 @@ extern "C" int lh_heatmap_refine(const float* heatmaps, const int* idx, const fl
     hipLaunchKernelGGL(heatmap_refine_kernel, dim3((bj + 255) / 256), dim3(256), 0, (hipStream_t)stream, heatmaps, idx, maxvals,
                        bj, h, w, scale, preds);
     LH_LAUNCH_CHECK("heatmap_refine launch");
+    return LH_OK;
+}
+
+// Opt-in DARK decode (Zhang et al. 2020, "Distribution-Aware Coordinate Representation of Keypoint": the published
+// get_final_preds -> gaussian_blur -> taylor chain), the sibling of heatmap_refine_kernel.  One workgroup per plane:
+//   1. the plane goes to LDS (16-byte loads where the plane base allows them);
+//   2. row pass of the separable zero-padded Gaussian: every thread blurs its elements i = tid + 256 u into registers, and after
+//      a barrier the registers replace the plane in LDS (one buffer: 36 KB for 96 x 96);
+//   3. column pass from LDS -- a wave's lanes hold consecutive x, so the stride-w reads of one tap are conflict-free -- of
+//      which only the maximum over the plane is kept (wave shuffles, four LDS slots);
+//   4. threads 0..12 redo the column pass at the 13 stencil points and store C = log(max(B * maxval / max B, 1e-10)); thread 0
+//      takes the derivatives and solves the 2 x 2 system.
+// Taps are accumulated in index order, a tap that falls outside the plane adds nothing.  No atomics: two calls give the same
+// bits.  The finiteness guard on the offset is this project's; OpenCV's fixed tap tables for kernels <= 7 are not reproduced.
+constexpr int DARK_MAX_HW = 96 * 96, DARK_MAX_TAPS = 17, DARK_PER_THREAD = DARK_MAX_HW / 256;
+struct DarkTaps { float g[DARK_MAX_TAPS]; };
+
+// column pass at (x, y) of the row-blurred plane in LDS
+__device__ __forceinline__ float dark_col(const float* rowb, const float* g, int k, int c, int x, int y, int h, int w) {
+    float acc = 0.f;
+    for (int t = 0; t < k; ++t) {
+        const int yy = y + t - c;
+        if (yy >= 0 && yy < h) acc += g[t] * rowb[yy * w + x];
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void heatmap_dark_kernel(const float* hm, const int* idx, const float* maxvals, int h, int w, int k,
+                                                          DarkTaps taps, int vec, float scale, float* preds) {
+    __shared__ __attribute__((aligned(16))) float plane[DARK_MAX_HW];
+    __shared__ float g[DARK_MAX_TAPS];
+    __shared__ float red[4];
+    __shared__ float cs[13];
+    const int p = blockIdx.x, tid = threadIdx.x, hw = h * w, c = k >> 1;
+    const float maxval = maxvals[p];
+    if (!(maxval > 0.f)) return;                          // get_max_preds zeroed the coordinate (or the maximum is a NaN)
+    const int peak = idx[p];
+    const int px = peak % w, py = peak / w;
+    if (!(1 < px && px < w - 2 && 1 < py && py < h - 2)) return;      // uniform over the workgroup: no barrier is skipped by a part of it
+    const float* m = hm + (long)p * hw;
+    if (tid < k) g[tid] = taps.g[tid];
+    if (vec) {
+        for (int i = tid; i < hw / 4; i += 256) reinterpret_cast<float4*>(plane)[i] = reinterpret_cast<const float4*>(m)[i];
+    } else {
+        for (int i = tid; i < hw; i += 256) plane[i] = m[i];
+    }
+    __syncthreads();
+    float r[DARK_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < DARK_PER_THREAD; ++u) {
+        const int i = tid + u * 256;
+        r[u] = 0.f;
+        if (i < hw) {
+            const int y = i / w, x = i - y * w;
+            float acc = 0.f;
+            for (int t = 0; t < k; ++t) {
+                const int xx = x + t - c;
+                if (xx >= 0 && xx < w) acc += g[t] * plane[y * w + xx];
+            }
+            r[u] = acc;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < DARK_PER_THREAD; ++u) {
+        const int i = tid + u * 256;
+        if (i < hw) plane[i] = r[u];
+    }
+    __syncthreads();
+    float bmax = -INFINITY;
+#pragma unroll 4
+    for (int u = 0; u < DARK_PER_THREAD; ++u) {
+        const int i = tid + u * 256;
+        if (i < hw) {
+            const int y = i / w, x = i - y * w;
+            bmax = fmaxf(bmax, dark_col(plane, g, k, c, x, y, h, w));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bmax = fmaxf(bmax, __shfl_xor(bmax, o));
+    if ((tid & 63) == 0) red[tid >> 6] = bmax;
+    __syncthreads();
+    if (tid < 13) {
+        // stencil points: 0..4 = (px-2 .. px+2, py), 5..8 = (px, py-2), (px, py-1), (px, py+1), (px, py+2), 9..12 = the diagonals
+        // (-1,-1), (+1,-1), (-1,+1), (+1,+1); all inside the plane by the skip test
+        int ox, oy;
+        if (tid < 5) { ox = tid - 2; oy = 0; }
+        else if (tid < 9) { ox = 0; oy = tid < 7 ? tid - 7 : tid - 6; }
+        else { ox = (tid - 9) & 1 ? 1 : -1; oy = tid < 11 ? -1 : 1; }
+        const float s = maxval / fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        cs[tid] = logf(fmaxf(dark_col(plane, g, k, c, px + ox, py + oy, h, w) * s, 1e-10f));
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float dx = 0.5f * (cs[3] - cs[1]), dy = 0.5f * (cs[7] - cs[6]);
+        const float dxx = 0.25f * (cs[4] - 2.f * cs[2] + cs[0]), dyy = 0.25f * (cs[8] - 2.f * cs[2] + cs[5]);
+        const float dxy = 0.25f * (cs[12] - cs[10] - cs[11] + cs[9]);
+        const float det = dxx * dyy - dxy * dxy;
+        if (det != 0.f) {
+            const float offx = -(dyy * dx - dxy * dy) / det, offy = -(dxx * dy - dxy * dx) / det;
+            if (isfinite(offx) && isfinite(offy)) {
+                preds[p * 2 + 0] = ((float)px + offx) * scale;
+                preds[p * 2 + 1] = ((float)py + offy) * scale;
+            }
+        }
+    }
+}
+
+extern "C" int lh_heatmap_dark(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w, int blur_kernel,
+                               float scale, float* preds, void* stream) {
+    LH_REQUIRE(heatmaps && idx && maxvals && preds && bj > 0 && h > 0 && w > 0, "lh_heatmap_dark: bad arguments");
+    LH_REQUIRE((long)h * w <= DARK_MAX_HW, "lh_heatmap_dark: a plane of %d x %d exceeds the %d elements the kernel holds in LDS", h, w,
+               DARK_MAX_HW);
+    LH_REQUIRE(blur_kernel >= 3 && blur_kernel <= DARK_MAX_TAPS && (blur_kernel & 1),
+               "lh_heatmap_dark: blur_kernel %d must be odd and lie in 3..%d", blur_kernel, DARK_MAX_TAPS);
+    // cv2.getGaussianKernel's formula for sigma <= 0, in fp64, normalised to sum 1 and rounded to fp32
+    DarkTaps taps = {};
+    double gd[DARK_MAX_TAPS], sum = 0.0;
+    const double c = (blur_kernel - 1) * 0.5, sg = 0.3 * ((blur_kernel - 1) * 0.5 - 1.0) + 0.8;
+    for (int t = 0; t < blur_kernel; ++t) sum += gd[t] = exp(-(t - c) * (t - c) / (2.0 * sg * sg));
+    for (int t = 0; t < blur_kernel; ++t) taps.g[t] = (float)(gd[t] / sum);
+    const int vec = (h * w) % 4 == 0 && (uintptr_t)heatmaps % 16 == 0;
+    hipLaunchKernelGGL(heatmap_dark_kernel, dim3(bj), dim3(256), 0, (hipStream_t)stream, heatmaps, idx, maxvals, h, w, blur_kernel, taps,
+                       vec, scale, preds);
+    LH_LAUNCH_CHECK("heatmap_dark launch");
     return LH_OK;
 }
 

@@ -4,7 +4,8 @@ Mirrors the three free functions the reference's training loop uses
 (``CustomDataset.generate_target`` src/tools/dataset.py:165-212, ``JointsMSELoss``
 src/utils/loss.py:306-325, ``get_max_preds`` src/utils/loss.py:327-355) with the same
 names, arguments and error behaviour; the arithmetic runs in liblighthand_hip.  ``WeightedJointsMSELoss`` and the
-``return_weight`` option of the renderers are opt-in extensions (upstream's target_weight and OHKM loss).
+``return_weight`` option of the renderers are opt-in extensions (upstream's target_weight and OHKM loss), as is DARK's
+sub-pixel coding (Zhang et al. 2020): ``unbiased=True`` of the renderers and ``post_process="dark"`` of the decoders.
 """
 import numpy as np
 import torch
@@ -42,18 +43,27 @@ def _patch_on(device):
     return _patch_cache[key]
 
 
-def render_targets(joints, size=HEATMAP_SIZE, out=None, return_weight=False):
+def render_targets(joints, size=HEATMAP_SIZE, out=None, return_weight=False, unbiased=False):
     """joints: device tensor [B, J, >=2] (pixel coordinates in the 256x256 frame) ->
     float32 [B, J, size, size] Gaussian targets (sigma 2, 13x13 patch, clipped assignment).
     ``return_weight=True`` (an extension: the reference computes this weight and never uses it) returns
     ``(target, target_weight [B, J, 1])``: column 2 of ``joints``, when present, is the visibility, weight = (vis > 0.5 ? vis : 0)
-    x (some part of the patch lies inside the map), and a joint of weight 0 gets a zero map."""
+    x (some part of the patch lies inside the map), and a joint of weight 0 gets a zero map.
+    ``unbiased=True`` (an extension: DARK's target encoding) keeps the 13x13 window where it is and evaluates the Gaussian
+    around the joint's real-valued position x / 4 instead of the rounded cell (lh_gaussian_target_sub)."""
     if not joints.is_cuda:
         raise _lib.LightHandError("render_targets needs a HIP device tensor")
     j = joints.to(torch.float32).contiguous()
     b, nj, stride = j.shape
     if out is None:
         out = torch.empty(b, nj, size, size, dtype=torch.float32, device=j.device)
+    if unbiased:
+        weight = torch.empty(b, nj, 1, dtype=torch.float32, device=j.device) if return_weight else None
+        vis = j.data_ptr() + 8 if return_weight and stride >= 3 else None
+        check(_lib.load().lh_gaussian_target_sub(j.data_ptr(), stride, vis, stride, RADIUS, float(SIGMA), out.data_ptr(),
+                                                 None if weight is None else weight.data_ptr(), b, nj, size, _stream()),
+              "lh_gaussian_target_sub")
+        return (out, weight) if return_weight else out
     patch = _patch_on(j.device)
     if return_weight:
         weight = torch.empty(b, nj, 1, dtype=torch.float32, device=j.device)
@@ -66,16 +76,17 @@ def render_targets(joints, size=HEATMAP_SIZE, out=None, return_weight=False):
     return out
 
 
-def generate_target(joints, device="cuda", return_weight=False):
+def generate_target(joints, device="cuda", return_weight=False, unbiased=False):
     """Per-sample form with the reference's signature: joints [21, >=2] (array-like) ->
     torch.float32 [21, 64, 64] (returned on the CPU like the reference's dataset method).  ``return_weight=True`` returns
-    ``(target, target_weight [21, 1])`` as upstream's generate_target does (column 2 = visibility when present)."""
+    ``(target, target_weight [21, 1])`` as upstream's generate_target does (column 2 = visibility when present);
+    ``unbiased``: as ``render_targets``'s."""
     if return_weight:
         j = torch.as_tensor(np.asarray(joints, dtype=np.float32)[:, :3].copy()).to(device)
-        target, weight = render_targets(j[None], return_weight=True)
+        target, weight = render_targets(j[None], return_weight=True, unbiased=unbiased)
         return target[0].cpu(), weight[0].cpu()
     j = torch.as_tensor(np.asarray(joints, dtype=np.float32)[:, :2].copy()).to(device)
-    return render_targets(j[None])[0].cpu()
+    return render_targets(j[None], unbiased=unbiased)[0].cpu()
 
 
 class GenerateHeatmap:
@@ -206,10 +217,32 @@ class WeightedJointsMSELoss(nn.Module):
         return loss
 
 
-def max_preds_device(heatmaps, scale=1.0, post_process=False):
+def decode_mode(post_process):
+    """The ``post_process`` option of the decoders -> None (plain arg-max), "quarter" or "dark".  ``True`` means "quarter"."""
+    if isinstance(post_process, str):
+        if post_process in ("quarter", "dark"):
+            return post_process
+    elif post_process is None or isinstance(post_process, (bool, np.bool_)):
+        return "quarter" if post_process else None
+    raise ValueError(f'post_process must be False, True, "quarter" or "dark", not {post_process!r}')
+
+
+def dark_refine_device(heatmaps, idx, maxvals, preds, scale=1.0, blur_kernel=11):
+    """The DARK launch on its own, for callers that hold the outputs of an arg-max or a flip merge at the same ``scale``:
+    ``preds`` [B, J, 2] is refined in place from ``heatmaps`` float32 [B, J, H, W] (contiguous, only read)."""
+    b, j, h, w = heatmaps.shape
+    check(_lib.load().lh_heatmap_dark(heatmaps.data_ptr(), idx.data_ptr(), maxvals.data_ptr(), b * j, h, w, int(blur_kernel),
+                                       float(scale), preds.data_ptr(), _stream()), "lh_heatmap_dark")
+    return preds
+
+
+def max_preds_device(heatmaps, scale=1.0, post_process=False, blur_kernel=11):
     """Device overload: heatmaps float32 [B, J, H, W] on the device ->
-    (preds [B, J, 2], maxvals [B, J, 1], flat indices [B, J]) device tensors.  ``post_process=True`` adds the opt-in
-    quarter-pixel refinement (an extension: the reference's TEST.POST_PROCESS flag exists but is unused)."""
+    (preds [B, J, 2], maxvals [B, J, 1], flat indices [B, J]) device tensors.  ``post_process=True`` / ``"quarter"`` adds the
+    opt-in quarter-pixel refinement (an extension: the reference's TEST.POST_PROCESS flag exists but is unused);
+    ``post_process="dark"`` the DARK decode instead: a second-order Taylor step on the log of the map blurred with a Gaussian of
+    ``blur_kernel`` taps (lh_heatmap_dark: maps of at most 96 x 96, ``blur_kernel`` odd in 3..17)."""
+    mode = decode_mode(post_process)
     if heatmaps.dim() != 4:
         raise AssertionError("batch_images should be 4-ndim")
     hm = heatmaps.to(torch.float32).contiguous()
@@ -219,9 +252,11 @@ def max_preds_device(heatmaps, scale=1.0, post_process=False):
     idx = torch.empty(b, j, dtype=torch.int32, device=hm.device)
     check(_lib.load().lh_heatmap_argmax(hm.data_ptr(), b * j, h, w, float(scale), preds.data_ptr(), maxvals.data_ptr(),
                                          idx.data_ptr(), _stream()), "lh_heatmap_argmax")
-    if post_process:
+    if mode == "quarter":
         check(_lib.load().lh_heatmap_refine(hm.data_ptr(), idx.data_ptr(), maxvals.data_ptr(), b * j, h, w, float(scale),
                                             preds.data_ptr(), _stream()), "lh_heatmap_refine")
+    elif mode == "dark":
+        dark_refine_device(hm, idx, maxvals, preds, scale, blur_kernel)
     return preds, maxvals, idx
 
 
@@ -261,16 +296,18 @@ def soft_argmax_device(heatmaps, beta=100.0, scale=1.0):
     return preds
 
 
-def get_max_preds(batch_heatmaps, post_process=False):
+def get_max_preds(batch_heatmaps, post_process=False, blur_kernel=11):
     """Reference signature (src/utils/loss.py:327-355): numpy [B, J, H, W] -> (preds float32
     [B, J, 2], maxvals [B, J, 1]) numpy arrays; device tensors are accepted too and then
     device tensors are returned (no host round trip).  ``post_process`` (default off = reference behaviour) enables
-    the quarter-pixel refinement."""
+    the quarter-pixel refinement (``True`` / ``"quarter"``) or the DARK decode (``"dark"``, with ``blur_kernel``), as
+    ``max_preds_device``'s."""
+    decode_mode(post_process)
     if isinstance(batch_heatmaps, torch.Tensor):
-        p, m, _ = max_preds_device(batch_heatmaps, post_process=post_process)
+        p, m, _ = max_preds_device(batch_heatmaps, post_process=post_process, blur_kernel=blur_kernel)
         return p, m
     assert isinstance(batch_heatmaps, np.ndarray), "batch_heatmaps should be numpy.ndarray"
     assert batch_heatmaps.ndim == 4, "batch_images should be 4-ndim"
     p, m, _ = max_preds_device(torch.from_numpy(np.ascontiguousarray(batch_heatmaps, dtype=np.float32)).cuda(),
-                               post_process=post_process)
+                               post_process=post_process, blur_kernel=blur_kernel)
     return p.cpu().numpy(), m.cpu().numpy().astype(batch_heatmaps.dtype)

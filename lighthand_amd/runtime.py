@@ -86,8 +86,15 @@ class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
                  input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
-                 use_target_weight=False, ohkm_topk=0):
+                 use_target_weight=False, ohkm_topk=0, target_encoding="quantised"):
         self.lib = _lib.load()
+        # target_encoding="unbiased" (opt-in, DARK): the target Gaussian is evaluated around the joint's real-valued heat-map
+        # position (lh_gaussian_target_sub) instead of placed around the rounded cell; "quantised" = the step as it was
+        if target_encoding not in ("quantised", "unbiased"):
+            raise ValueError(f'target_encoding must be "quantised" or "unbiased", not {target_encoding!r}')
+        if target_encoding == "unbiased" and not targets_from_joints:
+            raise LightHandError('target_encoding="unbiased" needs targets_from_joints=True: the encoding is applied where the target is rendered')
+        self.target_encoding = target_encoding
         # geometric_aug=(rotation, scale, shift) or a dict that may also carry prob / generator: a random affine warp of the
         # uint8 input per image and step (sample_affine), the joints moved to match (joints_aug) before the target render
         if geometric_aug is not None:
@@ -190,6 +197,12 @@ class TrainStep:
             check(self.lib.lh_affine_points(self.joints.data_ptr(), 2, self.plan.warp_fwd.data_ptr(), self.joints_aug.data_ptr(), 2, b, j,
                                             stream), "lh_affine_points")
             joints = self.joints_aug
+        if self.target_encoding == "unbiased":
+            check(self.lib.lh_gaussian_target_sub(joints.data_ptr(), 2, _ptr(self.vis) if self.use_target_weight else None, 1, heatmap.RADIUS,
+                                                  float(heatmap.SIGMA), self.target.data_ptr(),
+                                                  self.target_weight.data_ptr() if self.use_target_weight else None, b, j, hs, stream),
+                  "lh_gaussian_target_sub")
+            return
         if self.use_target_weight:
             check(self.lib.lh_gaussian_target_w(joints.data_ptr(), 2, self.vis.data_ptr(), 1, self._patch.data_ptr(), heatmap.RADIUS,
                                                 self.target.data_ptr(), self.target_weight.data_ptr(), b, j, hs, stream),
@@ -383,14 +396,17 @@ class InferStep:
     (lh_heatmap_flip_merge); ``heatmaps`` is then that merged buffer.  Both passes run the plan of ``batch``, so with
     ``bn_train`` each pass normalises with its own batch statistics and updates the running ones, as two model() calls do.
     ``shift_heatmap`` (TEST.SHIFT_HEATMAP) shifts the flipped-back maps by one column before the average; it only applies to
-    the flip test.  ``post_process`` (TEST.POST_PROCESS) adds the quarter-pixel refinement (lh_heatmap_refine) to the decode."""
+    the flip test.  ``post_process`` (TEST.POST_PROCESS): ``True`` / ``"quarter"`` adds the quarter-pixel refinement
+    (lh_heatmap_refine) to the decode, ``"dark"`` the DARK decode with a blur of ``blur_kernel`` taps (lh_heatmap_dark) in its
+    place; either reads the merged maps under the flip test."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
-                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None):
+                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
+        post_process = heatmap.decode_mode(post_process)
         self.lib = _lib.load()
         # a plan of its own (never the one model(x) runs): use_uint8_input rewires the plan's image launch, and a pipeline
         # slot replays asynchronously on its own stream -- neither may happen to the plan model.forward() uses
@@ -401,7 +417,7 @@ class InferStep:
         dev = out.device
         # input_u8=(hs, ws): raw uint8 HWC frames; ToTensor / Resize / Normalize run fused on the device (dataset.py:128-159)
         self.images = self.plan.use_uint8_input(*input_u8) if input_u8 else self.plan.img_nchw
-        self.flip_test, self.shift_heatmap, self.post_process = flip_test, shift_heatmap, post_process
+        self.flip_test, self.shift_heatmap, self.post_process, self.blur_kernel = flip_test, shift_heatmap, post_process, int(blur_kernel)
         # flip test: the plain pass's maps are copied here, and the merge writes over them in place
         self.heatmaps = torch.zeros_like(out) if flip_test else out
         self.preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
@@ -426,9 +442,12 @@ class InferStep:
         else:
             check(self.lib.lh_heatmap_argmax(hm.data_ptr(), bj, h, w, self.scale, self.preds.data_ptr(), self.maxvals.data_ptr(),
                                              _ptr(self.idx), s), "lh_heatmap_argmax")
-        if self.post_process:
+        if self.post_process == "quarter":
             check(self.lib.lh_heatmap_refine(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.scale,
                                              self.preds.data_ptr(), s), "lh_heatmap_refine")
+        elif self.post_process == "dark":
+            check(self.lib.lh_heatmap_dark(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.blur_kernel,
+                                           self.scale, self.preds.data_ptr(), s), "lh_heatmap_dark")
 
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
@@ -461,18 +480,19 @@ class InferPipeline:
     a stream of its own.  The stage 3-4 launches of one batch are latency-bound chains of one wave of tiles; a second batch
     fills the machine under them: R50 256x256 bs 64 bf16, 29.9 k img/s with one batch in flight, 33.3 k with two (MI355X).
     Eval-mode only (the batch-statistics quirk of ``pred_store`` updates the running statistics, which slots would race on).
-    ``flip_test`` / ``shift_heatmap`` / ``post_process``: as InferStep's, for every slot.
+    ``flip_test`` / ``shift_heatmap`` / ``post_process`` / ``blur_kernel``: as InferStep's, for every slot.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
         preds0, maxvals0 = pipe.result(t0)          # valid until `depth` more batches have been submitted
     """
 
-    def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False):
+    def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
+                 blur_kernel=11):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
-                                shift_heatmap=shift_heatmap, post_process=post_process) for i in range(depth)]
+                                shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel) for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
         self.count = 0

@@ -28,6 +28,9 @@ after the online warp; the reference computes this weight, src/tools/dataset.py:
 (online hard-keypoint mining, upstream's JointsOHKMMSELoss: per sample only the K joints with the largest loss count).  Both default
 to off = the reference's objective; validation then scores the loss with the same criterion, PCK / EPE stay as they are.
 ``--synthetic_invisible F``: the fraction of synthetic joints marked invisible under ``--use_target_weight`` (default 0.1).
+``--unbiased_target`` / ``--dark_decode`` (DARK, Zhang et al. 2020; both off by default): the target Gaussian is rendered around the
+joint's real-valued position instead of the rounded cell (in the step and in the validation loss), and the validation keypoints
+are decoded with the Taylor step on the log of the blurred map instead of the hard arg-max.
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -92,6 +95,9 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--ohkm_topk", default=0, type=int, help="online hard-keypoint mining: the K hardest joints per sample (0 = off)")
     p.add_argument("--synthetic_invisible", default=0.1, type=float,
                    help="fraction of --synthetic joints marked invisible (read under --use_target_weight only)")
+    p.add_argument("--unbiased_target", action="store_true",
+                   help="DARK's target encoding: the Gaussian around the joint's real-valued position (default: the rounded cell)")
+    p.add_argument("--dark_decode", action="store_true", help="decode the validation keypoints with DARK (default: hard arg-max)")
     args = p.parse_args(argv)
     args.phase = phase
     args.model = args.root.split("/")[0]                  # src/tools/dataset.py:59 overwrites it from the name
@@ -298,6 +304,7 @@ def validate(model, loader, args, u8_step=None):
     model.eval()
     # the loss the step trains with (--use_target_weight / --ohkm_topk), so the best-checkpoint decision follows the objective
     use_weight, topk = getattr(args, "use_target_weight", False), getattr(args, "ohkm_topk", 0)
+    unbiased, decode = getattr(args, "unbiased_target", False), "dark" if getattr(args, "dark_decode", False) else False
     crit = WeightedJointsMSELoss(topk) if use_weight or topk else JointsMSELoss(False)
     acc = torch.zeros(5, device="cuda")          # loss*b, b, pck*b, epe sum, epe count -- reduced on the device
     with torch.no_grad():
@@ -313,11 +320,11 @@ def validate(model, loader, args, u8_step=None):
                 pred = model(images)
             hs = pred.shape[-1]
             if use_weight:
-                target, weight = render_targets(joints3, size=hs, return_weight=True)
+                target, weight = render_targets(joints3, size=hs, return_weight=True, unbiased=unbiased)
             else:
-                target, weight = render_targets(joints, size=hs), None
+                target, weight = render_targets(joints, size=hs, unbiased=unbiased), None
             loss = crit(pred, target, weight)
-            kp, _, _ = max_preds_device(pred, scale=float(args.size // hs))
+            kp, _, _ = max_preds_device(pred, scale=float(args.size // hs), post_process=decode)
             b = images.shape[0]
             pck, esum, ecnt = device_pck_epe(kp, joints, T=0.2)
             acc += torch.stack([loss * b, torch.tensor(float(b), device="cuda"), pck * b, esum, ecnt])
@@ -400,7 +407,8 @@ def main(args, train_set=None, val_set=None):
     sync = parallel.GradSync(world) if world > 1 else None
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
-    loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk)
+    loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk,
+                   target_encoding="unbiased" if args.unbiased_target else "quantised")
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw)
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order

@@ -13,7 +13,8 @@ BATCH statistics at evaluation time.  ``--bn_train`` (default, = reference behav
 
 The configs' TEST block, off by default (= reference behaviour): ``--flip_test`` (TEST.FLIP_TEST) averages the heat-maps of every
 image and of its mirror image, flipped back and shifted one column (``--no_shift_heatmap`` drops the shift, TEST.SHIFT_HEATMAP);
-``--post_process`` (TEST.POST_PROCESS) refines the arg-max by a quarter pixel.  Both run inside the captured InferStep.
+``--post_process`` (TEST.POST_PROCESS) refines the arg-max by a quarter pixel; ``--dark_decode [--blur_kernel K]`` decodes with
+DARK instead (a Taylor step on the log of the blurred map; not both).  All run inside the captured InferStep.
 
 The reference's evaluation set (Armo_hand_dataset) is not redistributable: ``--synthetic N`` builds a seeded
 stand-in with the four occlusion categories and visibility flags.
@@ -52,9 +53,9 @@ class _Steps:
     (argparser.py:258-262) -- padding it would put foreign samples into the BatchNorm batch statistics that
     ``pred_store``'s train-mode forward uses, and into the running-statistics update."""
 
-    def __init__(self, model, size, bn_train, flip_test=False, shift_heatmap=True, post_process=False):
+    def __init__(self, model, size, bn_train, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11):
         self.model, self.size, self.bn_train, self.steps = model, size, bn_train, {}
-        self.options = dict(flip_test=flip_test, shift_heatmap=shift_heatmap, post_process=post_process)
+        self.options = dict(flip_test=flip_test, shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel)
 
     def __call__(self, images):
         from lighthand_amd.runtime import InferStep
@@ -65,10 +66,11 @@ class _Steps:
         return step(images.cuda(non_blocking=True))
 
 
-def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
+def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False,
+               blur_kernel=11):
     """src/utils/argparser.py:246-281 with the forward + arg-max decode on the device."""
     meta = {c: {"bb": [], "pred": [], "gt": []} for c in CATEGORIES}
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
     for images, joints_v, cats in loader:
         preds = step(images).cpu()                       # already x4 (method.py:157)
         gt = joints_v[:, :, :2]
@@ -85,12 +87,13 @@ def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=Fa
     return meta
 
 
-def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
+def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False,
+                    blur_kernel=11):
     """src/utils/argparser.py:284-323 -- the category-less variant: one entry per BATCH of predictions (x4, 256-px frame),
     ground truth and bounding-box diagonals; read back by ``lighthand_amd.metrics.pred_test``.  The loader yields
     (images, gt_2d_joints[, ...])."""
     meta = {"pred": [], "gt": [], "bb": []}
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
     for item in loader:
         images, gt = item[0], item[1][:, :, :2]
         preds = step(images).cpu()
@@ -105,13 +108,13 @@ def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_te
     return meta
 
 
-def device_eval(model, loader, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False):
+def device_eval(model, loader, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11):
     """Same evaluation reduced ON THE DEVICE: per threshold set the PCK-curve counts of all visible
     joints are accumulated by lh_pck_curve, summed across data-parallel ranks with one small all-reduce, and read by
     the host once.  Returns {(type, T1): [auc, epe_mm, curve]}; the AUC equals pred_eval's 'mean_auc' AUC (whose EPE is
     diluted by the reference's zeros quirk; the EPE here is the plain mean)."""
     from lighthand_amd.metrics import auc_from_counts, device_pck_curve
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
     acc = {(t, tuple(T)): None for t, T in THRESHOLDS}
     for images, joints_v, _ in loader:
         preds = step(images)
@@ -160,6 +163,9 @@ def build_parser():
     ap.add_argument("--no_shift_heatmap", dest="shift_heatmap", action="store_false",
                     help="with --flip_test: no one-column shift of the flipped-back heat-maps (TEST.SHIFT_HEATMAP off)")
     ap.add_argument("--post_process", action="store_true", help="quarter-pixel refinement of the arg-max (TEST.POST_PROCESS)")
+    ap.add_argument("--dark_decode", action="store_true",
+                    help="DARK decode: a Taylor step on the log of the blurred heat-map, in place of --post_process")
+    ap.add_argument("--blur_kernel", default=11, type=int, help="with --dark_decode: taps of the Gaussian blur (odd, 3..17)")
     return ap
 
 
@@ -170,7 +176,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not args.shift_heatmap and not args.flip_test:
         ap.error("--no_shift_heatmap applies to --flip_test")
-    test_opts = dict(flip_test=args.flip_test, shift_heatmap=args.shift_heatmap, post_process=args.post_process)
+    if args.post_process and args.dark_decode:
+        ap.error("--post_process and --dark_decode are two decodes: pass one")
+    test_opts = dict(flip_test=args.flip_test, shift_heatmap=args.shift_heatmap,
+                     post_process="dark" if args.dark_decode else args.post_process, blur_kernel=args.blur_kernel)
     if not args.synthetic:
         raise SystemExit("the Armo_hand evaluation set is not shipped: pass --synthetic N or plug your own Dataset")
     data = SyntheticEvalSet(args.synthetic, args.size)
