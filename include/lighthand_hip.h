@@ -529,6 +529,26 @@ int lh_heatmap_soft_argmax(const float* heatmaps, int bj, int h, int w, float be
                            void* stream);
 int lh_heatmap_refine(const float* heatmaps, const int* idx, const float* maxvals, int bj, int h, int w,
                       float scale, float* preds, void* stream);
+/* Integral-regression coordinate loss (Sun et al. 2018; an opt-in extension without a reference oracle): the L1 distance between
+ * lh_heatmap_soft_argmax's expectation and the ground-truth joint, in input pixels, and its gradient through the softmax.
+ * heatmaps / grad fp32 [b*j][h*w], joints fp32 read at joints[n * jstride + {0, 1}], weight fp32 [b*j] or NULL (ones), preds
+ * fp32 [b*j][2], joint_loss optional fp32 [b*j], loss a device scalar, grad optional, grad_scale an optional device scalar read
+ * on the device like lh_mse_heatmap's.  Per plane n, x_p = p % w, y_p = p / w:
+ *   e_p = expf(beta * (hm_p - max hm)) in fp32; S0 = sum e_p, sum e_p x_p, sum e_p y_p in fp64 in a fixed order;
+ *   ex = sum e_p x_p / S0, ey likewise (fp64); preds[n] = ((float)ex * scale, (float)ey * scale): lh_heatmap_soft_argmax's bits;
+ *   r = preds[n] - joints[n] (fp32), s = sgn(r) per axis with sgn(0) = 0; joint_loss[n] = wgt_n * (|rx| + |ry|);
+ *   loss_c = lambda * sum_n joint_loss[n] / (2*b*j), folded in fp64 in plane order by one small launch; *loss = loss_c, or
+ *   *loss += loss_c when add_to_loss; the first 4 bytes of the workspace receive loss_c alone (fp32) either way;
+ *   g_p = (e_p * k_n) * (float)((x_p - ex) * sx + (y_p - ey) * sy), the bracket in fp64,
+ *   k_n = (float)(gs * lambda * wgt_n * scale * beta / (2*b*j) / S0), gs = grad_scale ? *grad_scale : 1;
+ *   grad_p = g_p, or grad_p += g_p when add_to_grad.  A plane of weight 0 gets exactly 0.f (add_to_grad: it is not touched).
+ * One workgroup per plane with the plane in LDS (read from memory once), 16-byte accesses on grad, no atomics: two calls give
+ * the same bits.  Supported for h * w <= 96 * 96, h * w % 4 == 0, heatmaps / grad / workspace 16-byte aligned, beta > 0, finite
+ * beta / scale / lambda (LH_ERR_ARG otherwise, before any launch); workspace >= lh_integral_l1_workspace_bytes(b, j). */
+size_t lh_integral_l1_workspace_bytes(int b, int j);
+int lh_integral_l1(const float* heatmaps, const float* joints, int jstride, const float* weight, int b, int j, int h, int w,
+                   float beta, float scale, float lambda, float* preds, float* joint_loss, float* loss, int add_to_loss,
+                   float* grad, int add_to_grad, const float* grad_scale, void* workspace, void* stream);
 /* Opt-in DARK decode (Zhang et al. 2020: the published get_final_preds -> gaussian_blur -> taylor chain; NOT in the
  * reference), the sibling of lh_heatmap_refine: idx / maxvals / preds are the outputs of lh_heatmap_argmax or
  * lh_heatmap_flip_merge at the same `scale`; preds is updated in place, the heat-maps are only read.  Per plane, in fp32:

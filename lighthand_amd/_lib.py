@@ -179,6 +179,8 @@ SIGNATURES = {
     "lh_heatmap_soft_argmax": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
     "lh_heatmap_refine": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     "lh_heatmap_dark": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
+    "lh_integral_l1_workspace_bytes": (_SZ, [_I, _I]),
+    "lh_integral_l1": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "lh_heatmap_flip_merge": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "lh_keypoint_metrics": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "lh_comm_unique_id": (_I, [_P]),

@@ -1,4 +1,5 @@
 // Heat-maps: Gaussian target renderers, MSE / weighted / hard-keypoint-mining losses, arg-max family decode, PCK / EPE metrics.
+#include <cmath>
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------------ Gaussian target
@@ -650,6 +651,144 @@ extern "C" int lh_heatmap_soft_argmax(const float* heatmaps, int bj, int h, int 
     LH_REQUIRE(heatmaps && preds && bj > 0 && h > 0 && w > 0, "lh_heatmap_soft_argmax: bad arguments");
     hipLaunchKernelGGL(heatmap_soft_argmax_kernel, dim3(bj), dim3(256), 0, (hipStream_t)stream, heatmaps, h * w, w, beta, scale, preds);
     LH_LAUNCH_CHECK("heatmap_soft_argmax launch");
+    return LH_OK;
+}
+
+// ---- Integral-regression coordinate loss (Sun et al. 2018, "Integral Human Pose Regression"; an opt-in extension without a
+// reference oracle): L1 between the soft-arg-max of a plane and its ground-truth joint, and the gradient of that through the
+// softmax, added to the heat-map loss's outputs (lh_integral_l1).  One workgroup per plane:
+//   1. the plane goes to LDS (h*w floats, sized by the launch: 16 KB for a 64 x 64 plane) with 16-byte loads, the maximum is
+//      taken on the way;
+//   2. e_p = expf(beta * (hm_p - max)) replaces the plane in LDS; S0, sum e x, sum e y in fp64 with the thread stride, the wave
+//      shuffles and the four LDS slots of heatmap_soft_argmax_kernel, so preds has that kernel's bits;
+//   3. every thread forms the expectation, the residual's signs and k_n from the slots, thread 0 stores preds and the plane's
+//      loss; the gradient pass reads e_p from LDS and reads / writes grad with 16-byte accesses.
+// A plane of weight 0 skips pass 3's gradient (accumulate) or stores zeros (write).  No atomics: two calls give the same bits.
+constexpr int INTEGRAL_MAX_HW = 96 * 96;
+constexpr size_t INTEGRAL_WS_HEAD = 16;                   // workspace: fp32 loss_c (+ padding), then the fp64 plane losses
+
+__device__ __forceinline__ float sgnf(float r) { return r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(256) void integral_l1_kernel(const float* hm, const float* joints, int jstride, const float* weight, int bj,
+                                                         int hw, int w, float beta, float scale, float lambda, float* preds,
+                                                         float* joint_loss, double* plane_loss, float* grad, int add_to_grad,
+                                                         const float* grad_scale) {
+    extern __shared__ __attribute__((aligned(16))) float plane[];      // hw floats, sized by the launch
+    __shared__ float rmax[4];
+    __shared__ double rs[4][3];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const float4* m4 = reinterpret_cast<const float4*>(hm + (long)n * hw);
+    float mx = -INFINITY;
+    for (int i = tid; i < hw / 4; i += 256) {
+        const float4 v = m4[i];
+        reinterpret_cast<float4*>(plane)[i] = v;
+        mx = fmaxf(fmaxf(mx, v.x), fmaxf(fmaxf(v.y, v.z), v.w));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((tid & 63) == 0) rmax[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+    double s0 = 0.0, sx = 0.0, sy = 0.0;
+    for (int i = tid; i < hw; i += 256) {                  // element i is read and replaced by this thread only
+        const float ef = expf(beta * (plane[i] - mx));
+        plane[i] = ef;
+        const double e = (double)ef;
+        s0 += e; sx += e * (double)(i % w); sy += e * (double)(i / w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); }
+    if ((tid & 63) == 0) { rs[tid >> 6][0] = s0; rs[tid >> 6][1] = sx; rs[tid >> 6][2] = sy; }
+    __syncthreads();
+    const double t0 = rs[0][0] + rs[1][0] + rs[2][0] + rs[3][0];
+    const double ex = (rs[0][1] + rs[1][1] + rs[2][1] + rs[3][1]) / t0;
+    const double ey = (rs[0][2] + rs[1][2] + rs[2][2] + rs[3][2]) / t0;
+    const float px = (float)ex * scale, py = (float)ey * scale;
+    const float rx = px - joints[(long)n * jstride], ry = py - joints[(long)n * jstride + 1];
+    const float wgt = weight ? weight[n] : 1.f;
+    if (tid == 0) {
+        preds[n * 2 + 0] = px;
+        preds[n * 2 + 1] = py;
+        const float jl = wgt * (fabsf(rx) + fabsf(ry));
+        if (joint_loss) joint_loss[n] = jl;
+        plane_loss[n] = (double)jl;
+    }
+    if (!grad) return;
+    float4* g4 = reinterpret_cast<float4*>(grad + (long)n * hw);
+    if (wgt == 0.f) {                                      // exactly 0.f: written, or nothing to add
+        if (!add_to_grad)
+            for (int i = tid; i < hw / 4; i += 256) g4[i] = float4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const double dsx = (double)sgnf(rx), dsy = (double)sgnf(ry);
+    const double gs = grad_scale ? (double)*grad_scale : 1.0;
+    const float k = (float)(gs * (double)lambda * (double)wgt * (double)scale * (double)beta / (2.0 * (double)bj) / t0);
+    for (int i = tid; i < hw / 4; i += 256) {
+        const float4 e = reinterpret_cast<const float4*>(plane)[i];
+        const float ev[4] = {e.x, e.y, e.z, e.w};
+        float g[4];
+        int yc =(i * 4) / w, xc = i * 4 - yc * w;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            g[c] = (ev[c] * k) * (float)(((double)xc - ex) * dsx + ((double)yc - ey) * dsy);
+            if (++xc == w) { xc = 0; ++yc; }                           // the four elements may cross a row end
+        }
+        if (add_to_grad) {
+            const float4 o = g4[i];
+            g4[i] = float4{o.x + g[0], o.y + g[1], o.z + g[2], o.w + g[3]};
+        } else {
+            g4[i] = float4{g[0], g[1], g[2], g[3]};
+        }
+    }
+}
+
+// loss_c = lambda * sum_n plane_loss[n] / (2*b*j), summed in fp64 in plane order by thread 0 (the others stage tiles of 256 in LDS)
+__global__ __launch_bounds__(256) void integral_l1_fold_kernel(const double* plane_loss, int bj, float lambda, float* loss_c, float* loss,
+                                                              int add_to_loss) {
+    __shared__ double tile[256];
+    double acc = 0.0;
+    for (int base = 0; base < bj; base += 256) {
+        tile[threadIdx.x] = base + (int)threadIdx.x < bj ? plane_loss[base + threadIdx.x] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int cnt = bj - base < 256 ? bj - base : 256;
+            for (int k = 0; k < cnt; ++k) acc += tile[k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float lc = (float)((double)lambda * acc / (2.0 * (double)bj));
+        *loss_c = lc;
+        *loss = add_to_loss ? *loss + lc : lc;
+    }
+}
+
+extern "C" size_t lh_integral_l1_workspace_bytes(int b, int j) {
+    return b > 0 && j > 0 ? INTEGRAL_WS_HEAD + (size_t)b * j * sizeof(double) : 0;
+}
+
+extern "C" int lh_integral_l1(const float* heatmaps, const float* joints, int jstride, const float* weight, int b, int j, int h, int w,
+                              float beta, float scale, float lambda, float* preds, float* joint_loss, float* loss, int add_to_loss,
+                              float* grad, int add_to_grad, const float* grad_scale, void* workspace, void* stream) {
+    LH_REQUIRE(heatmaps && joints && preds && loss && workspace && jstride >= 2 && b > 0 && j > 0 && h > 0 && w > 0,
+               "lh_integral_l1: bad arguments");
+    LH_REQUIRE((long)b * j < (1L << 30), "lh_integral_l1: too many planes");
+    LH_REQUIRE(beta > 0.f && std::isfinite(beta) && std::isfinite(scale) && std::isfinite(lambda),
+               "lh_integral_l1: beta must be positive, beta / scale / lambda finite");
+    LH_REQUIRE((long)h * w <= INTEGRAL_MAX_HW, "lh_integral_l1: a plane of %d x %d exceeds the %d elements the kernel holds in LDS", h, w,
+               INTEGRAL_MAX_HW);
+    LH_REQUIRE((h * w) % 4 == 0, "lh_integral_l1: the plane size %d must be a multiple of 4", h * w);
+    LH_REQUIRE(((uintptr_t)heatmaps % 16 == 0) && (!grad || (uintptr_t)grad % 16 == 0) && ((uintptr_t)workspace % 16 == 0),
+               "lh_integral_l1: buffers must be 16-byte aligned");
+    const int bj = b * j;
+    float* loss_c = (float*)workspace;
+    double* plane_loss = (double*)((char*)workspace + INTEGRAL_WS_HEAD);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(integral_l1_kernel, dim3(bj), dim3(256), (size_t)h * w * sizeof(float), s, heatmaps, joints, jstride, weight, bj, h * w, w, beta, scale, lambda,
+                       preds, joint_loss, plane_loss, grad, add_to_grad ? 1 : 0, grad_scale);
+    hipLaunchKernelGGL(integral_l1_fold_kernel, dim3(1), dim3(256), 0, s, (const double*)plane_loss, bj, lambda, loss_c, loss,
+                       add_to_loss ? 1 : 0);
+    LH_LAUNCH_CHECK("integral_l1 launch");
     return LH_OK;
 }
 

@@ -5,7 +5,8 @@ Mirrors the three free functions the reference's training loop uses
 src/utils/loss.py:306-325, ``get_max_preds`` src/utils/loss.py:327-355) with the same
 names, arguments and error behaviour; the arithmetic runs in liblighthand_hip.  ``WeightedJointsMSELoss`` and the
 ``return_weight`` option of the renderers are opt-in extensions (upstream's target_weight and OHKM loss), as is DARK's
-sub-pixel coding (Zhang et al. 2020): ``unbiased=True`` of the renderers and ``post_process="dark"`` of the decoders.
+sub-pixel coding (Zhang et al. 2020): ``unbiased=True`` of the renderers and ``post_process="dark"`` of the decoders, and integral
+regression (Sun et al. 2018): ``IntegralL1Loss`` and ``post_process="soft"``.
 """
 import numpy as np
 import torch
@@ -217,14 +218,72 @@ class WeightedJointsMSELoss(nn.Module):
         return loss
 
 
+class _IntegralL1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, joints, target_weight, beta, scale):
+        lib = _lib.load()
+        p = output.detach().to(torch.float32).contiguous()
+        if p.dim() != 4:
+            raise ValueError(f"prediction {tuple(p.shape)} must be [B, J, H, W]")
+        b, j, h, w = p.shape
+        g = joints.detach().to(torch.float32).contiguous()
+        if g.dim() != 3 or tuple(g.shape[:2]) != (b, j) or g.shape[2] < 2:
+            raise ValueError(f"joints {tuple(g.shape)} must be [{b}, {j}, >=2]")
+        wt = None
+        if target_weight is not None:
+            wt = target_weight.detach().to(torch.float32).contiguous()
+            if wt.numel() != b * j:
+                raise ValueError(f"target_weight {tuple(wt.shape)} does not hold one weight per joint plane ({b} x {j})")
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        preds = torch.empty(b, j, 2, dtype=torch.float32, device=p.device)
+        joint_loss = torch.empty(b, j, dtype=torch.float32, device=p.device)
+        grad = torch.empty_like(p) if ctx.needs_input_grad[0] else None      # no gradient wanted: the kernel skips that pass
+        ws = torch.empty(lib.lh_integral_l1_workspace_bytes(b, j), dtype=torch.uint8, device=p.device)
+        check(lib.lh_integral_l1(p.data_ptr(), g.data_ptr(), g.shape[2], None if wt is None else wt.data_ptr(), b, j, h, w, float(beta),
+                                 float(scale), 1.0, preds.data_ptr(), joint_loss.data_ptr(), loss.data_ptr(), 0,
+                                 None if grad is None else grad.data_ptr(), 0, None, ws.data_ptr(), _stream()), "lh_integral_l1")
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(preds, joint_loss)
+        return loss, preds, joint_loss
+
+    @staticmethod
+    def backward(ctx, gout, _gpreds, _gjoint):
+        (grad,) = ctx.saved_tensors
+        return grad * gout, None, None, None, None
+
+
+class IntegralL1Loss(nn.Module):
+    """An extension without a reference oracle: the coordinate loss of integral regression (Sun et al. 2018).  The prediction of a
+    plane is the expected position under softmax(``beta`` * heat-map), times ``scale`` (heat-map cells -> input pixels); the loss is
+    the L1 distance to ``joints`` [B, J, >=2] (input pixels), weighted per joint by ``target_weight`` ([B, J, 1] / [B, J] or None
+    = ones) and averaged over the 2 * B * J coordinates (lh_integral_l1 with lambda = 1).  ``preds`` [B, J, 2] and ``joint_loss``
+    [B, J] hold the last call's outputs; the gradient reaches the heat-maps through autograd."""
+
+    def __init__(self, beta=100.0, scale=1.0):
+        super().__init__()
+        if not (beta > 0 and np.isfinite(beta)):
+            raise ValueError(f"beta must be positive and finite, not {beta!r}")
+        if not np.isfinite(scale):
+            raise ValueError(f"scale must be finite, not {scale!r}")
+        self.beta, self.scale = float(beta), float(scale)
+        self.preds = self.joint_loss = None
+
+    def forward(self, output, joints, target_weight=None):
+        if not output.is_cuda:
+            raise _lib.LightHandError("IntegralL1Loss runs on the HIP device only")
+        loss, self.preds, self.joint_loss = _IntegralL1Fn.apply(output, joints, target_weight, self.beta, self.scale)
+        return loss
+
+
 def decode_mode(post_process):
-    """The ``post_process`` option of the decoders -> None (plain arg-max), "quarter" or "dark".  ``True`` means "quarter"."""
+    """The ``post_process`` option of the decoders -> None (plain arg-max), "quarter", "dark" or "soft".  ``True`` means "quarter"."""
     if isinstance(post_process, str):
-        if post_process in ("quarter", "dark"):
+        if post_process in ("quarter", "dark", "soft"):
             return post_process
     elif post_process is None or isinstance(post_process, (bool, np.bool_)):
         return "quarter" if post_process else None
-    raise ValueError(f'post_process must be False, True, "quarter" or "dark", not {post_process!r}')
+    raise ValueError(f'post_process must be False, True, "quarter", "dark" or "soft", not {post_process!r}')
 
 
 def dark_refine_device(heatmaps, idx, maxvals, preds, scale=1.0, blur_kernel=11):
@@ -236,12 +295,14 @@ def dark_refine_device(heatmaps, idx, maxvals, preds, scale=1.0, blur_kernel=11)
     return preds
 
 
-def max_preds_device(heatmaps, scale=1.0, post_process=False, blur_kernel=11):
+def max_preds_device(heatmaps, scale=1.0, post_process=False, blur_kernel=11, soft_argmax_beta=100.0):
     """Device overload: heatmaps float32 [B, J, H, W] on the device ->
     (preds [B, J, 2], maxvals [B, J, 1], flat indices [B, J]) device tensors.  ``post_process=True`` / ``"quarter"`` adds the
     opt-in quarter-pixel refinement (an extension: the reference's TEST.POST_PROCESS flag exists but is unused);
     ``post_process="dark"`` the DARK decode instead: a second-order Taylor step on the log of the map blurred with a Gaussian of
-    ``blur_kernel`` taps (lh_heatmap_dark: maps of at most 96 x 96, ``blur_kernel`` odd in 3..17)."""
+    ``blur_kernel`` taps (lh_heatmap_dark: maps of at most 96 x 96, ``blur_kernel`` odd in 3..17); ``post_process="soft"`` the
+    soft-arg-max: preds is the expectation under softmax(``soft_argmax_beta`` * heat-map) (lh_heatmap_soft_argmax), while maxvals
+    and the indices stay the arg-max's."""
     mode = decode_mode(post_process)
     if heatmaps.dim() != 4:
         raise AssertionError("batch_images should be 4-ndim")
@@ -257,6 +318,9 @@ def max_preds_device(heatmaps, scale=1.0, post_process=False, blur_kernel=11):
                                             preds.data_ptr(), _stream()), "lh_heatmap_refine")
     elif mode == "dark":
         dark_refine_device(hm, idx, maxvals, preds, scale, blur_kernel)
+    elif mode == "soft":
+        check(_lib.load().lh_heatmap_soft_argmax(hm.data_ptr(), b * j, h, w, float(soft_argmax_beta), float(scale), preds.data_ptr(),
+                                                  _stream()), "lh_heatmap_soft_argmax")
     return preds, maxvals, idx
 
 
@@ -296,18 +360,18 @@ def soft_argmax_device(heatmaps, beta=100.0, scale=1.0):
     return preds
 
 
-def get_max_preds(batch_heatmaps, post_process=False, blur_kernel=11):
+def get_max_preds(batch_heatmaps, post_process=False, blur_kernel=11, soft_argmax_beta=100.0):
     """Reference signature (src/utils/loss.py:327-355): numpy [B, J, H, W] -> (preds float32
     [B, J, 2], maxvals [B, J, 1]) numpy arrays; device tensors are accepted too and then
     device tensors are returned (no host round trip).  ``post_process`` (default off = reference behaviour) enables
-    the quarter-pixel refinement (``True`` / ``"quarter"``) or the DARK decode (``"dark"``, with ``blur_kernel``), as
-    ``max_preds_device``'s."""
+    the quarter-pixel refinement (``True`` / ``"quarter"``), the DARK decode (``"dark"``, with ``blur_kernel``) or the soft-arg-max
+    (``"soft"``, with ``soft_argmax_beta``), as ``max_preds_device``'s."""
     decode_mode(post_process)
     if isinstance(batch_heatmaps, torch.Tensor):
-        p, m, _ = max_preds_device(batch_heatmaps, post_process=post_process, blur_kernel=blur_kernel)
+        p, m, _ = max_preds_device(batch_heatmaps, post_process=post_process, blur_kernel=blur_kernel, soft_argmax_beta=soft_argmax_beta)
         return p, m
     assert isinstance(batch_heatmaps, np.ndarray), "batch_heatmaps should be numpy.ndarray"
     assert batch_heatmaps.ndim == 4, "batch_images should be 4-ndim"
     p, m, _ = max_preds_device(torch.from_numpy(np.ascontiguousarray(batch_heatmaps, dtype=np.float32)).cuda(),
-                               post_process=post_process, blur_kernel=blur_kernel)
+                               post_process=post_process, blur_kernel=blur_kernel, soft_argmax_beta=soft_argmax_beta)
     return p.cpu().numpy(), m.cpu().numpy().astype(batch_heatmaps.dtype)

@@ -8,6 +8,9 @@ arg-max decode (kept on the device) -> backward -> [gradient all-reduce] -> fuse
 Loss and keypoints stay on the device; ``.loss`` / ``.preds`` are read only when the caller
 asks (no per-iteration stream sync).
 """
+import math
+import numbers
+
 import torch
 
 from . import _lib, heatmap
@@ -82,12 +85,33 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _is_number(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def _check_beta(soft_argmax_beta):
+    if not _is_number(soft_argmax_beta) or soft_argmax_beta <= 0:
+        raise ValueError(f"soft_argmax_beta must be a finite number > 0, not {soft_argmax_beta!r}")
+
+
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
                  input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
-                 use_target_weight=False, ohkm_topk=0, target_encoding="quantised"):
+                 use_target_weight=False, ohkm_topk=0, target_encoding="quantised", coord_loss_weight=0.0, soft_argmax_beta=100.0):
+        """``coord_loss_weight`` = L > 0 (opt-in, integral regression; 0 = the step as it was: the same launches and buffers) adds
+        L * mean |soft-arg-max(beta * heat-map) * 4 - joint| to the loss and its gradient to ``plan.dout_nchw`` (lh_integral_l1 right
+        behind the MSE kernel, on the joints the target was rendered from, weighted by ``target_weight`` under ``use_target_weight``,
+        with the step's loss scale).  The coordinate term covers EVERY joint whatever ``ohkm_topk`` says: mining selects planes of
+        the MSE term only.  ``coord_loss`` holds the coordinate term alone, ``soft_preds`` the soft-arg-max keypoints and
+        ``coord_joint_loss`` [B, J] the weighted L1 distance of every joint (lh_integral_l1's joint_loss); ``preds`` stays the arg-max.  Data parallel needs nothing new: the normaliser 2*b*j is a constant every rank shares."""
         self.lib = _lib.load()
+        if not _is_number(coord_loss_weight) or coord_loss_weight < 0:
+            raise ValueError(f"coord_loss_weight must be a finite number >= 0, not {coord_loss_weight!r}")
+        _check_beta(soft_argmax_beta)
+        if coord_loss_weight > 0 and not targets_from_joints:
+            raise LightHandError("coord_loss_weight needs targets_from_joints=True: the coordinate loss reads the joints the target is rendered from")
+        self.coord_loss_weight, self.soft_argmax_beta = float(coord_loss_weight), float(soft_argmax_beta)
         # target_encoding="unbiased" (opt-in, DARK): the target Gaussian is evaluated around the joint's real-valued heat-map
         # position (lh_gaussian_target_sub) instead of placed around the rounded cell; "quantised" = the step as it was
         if target_encoding not in ("quantised", "unbiased"):
@@ -153,6 +177,12 @@ class TrainStep:
         self.preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
         self.maxvals = torch.zeros(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
         self.decode = decode
+        self.coord_loss = self.soft_preds = self.coord_joint_loss = self._integral_ws = None
+        if self.coord_loss_weight > 0:
+            self._integral_ws = torch.zeros(self.lib.lh_integral_l1_workspace_bytes(batch, out.shape[1]), dtype=torch.uint8, device=dev)
+            self.coord_loss = self._integral_ws[:4].view(torch.float32)[0]       # the fold writes the coordinate term alone here
+            self.soft_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
+            self.coord_joint_loss = torch.zeros(batch, out.shape[1], dtype=torch.float32, device=dev)
         self._mse_ws = torch.empty(self.lib.lh_mse_workspace_bytes(out.numel()), dtype=torch.uint8, device=dev)
         self._patch = heatmap._patch_on(dev)
         self.optimizer = optimizer or Adam(model.parameters(), lr=lr, betas=betas, eps=eps)
@@ -234,6 +264,13 @@ class TrainStep:
         else:
             check(self.lib.lh_mse_heatmap(out.data_ptr(), self.target.data_ptr(), out.numel(), self.loss.data_ptr(),
                                           p.dout_nchw.data_ptr(), _ptr(self._loss_scale_dev), self._mse_ws.data_ptr(), stream), "lh_mse_heatmap")
+        if self._integral_ws is not None:
+            joints = self.joints_aug if self.joints_aug is not None else self.joints
+            check(self.lib.lh_integral_l1(out.data_ptr(), joints.data_ptr(), 2, self.target_weight.data_ptr() if self.use_target_weight else None,
+                                          out.shape[0], out.shape[1], out.shape[2], out.shape[3], self.soft_argmax_beta, self.heat_scale,
+                                          self.coord_loss_weight, self.soft_preds.data_ptr(), self.coord_joint_loss.data_ptr(),
+                                          self.loss.data_ptr(), 1, p.dout_nchw.data_ptr(), 1, _ptr(self._loss_scale_dev),
+                                          self._integral_ws.data_ptr(), stream), "lh_integral_l1")
         if self.decode:
             check(self.lib.lh_heatmap_argmax(out.data_ptr(), out.shape[0] * out.shape[1], out.shape[2], out.shape[3],
                                              self.heat_scale, self.preds.data_ptr(), self.maxvals.data_ptr(), None,
@@ -398,15 +435,18 @@ class InferStep:
     ``shift_heatmap`` (TEST.SHIFT_HEATMAP) shifts the flipped-back maps by one column before the average; it only applies to
     the flip test.  ``post_process`` (TEST.POST_PROCESS): ``True`` / ``"quarter"`` adds the quarter-pixel refinement
     (lh_heatmap_refine) to the decode, ``"dark"`` the DARK decode with a blur of ``blur_kernel`` taps (lh_heatmap_dark) in its
-    place; either reads the merged maps under the flip test."""
+    place, ``"soft"`` overwrites ``preds`` with the soft-arg-max under softmax(``soft_argmax_beta`` * heat-map)
+    (lh_heatmap_soft_argmax; ``maxvals`` stays the arg-max's); each reads the merged maps under the flip test."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
-                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11):
+                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
         post_process = heatmap.decode_mode(post_process)
+        _check_beta(soft_argmax_beta)
+        self.soft_argmax_beta = float(soft_argmax_beta)
         self.lib = _lib.load()
         # a plan of its own (never the one model(x) runs): use_uint8_input rewires the plan's image launch, and a pipeline
         # slot replays asynchronously on its own stream -- neither may happen to the plan model.forward() uses
@@ -422,7 +462,7 @@ class InferStep:
         self.heatmaps = torch.zeros_like(out) if flip_test else out
         self.preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
         self.maxvals = torch.zeros(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
-        self.idx = torch.zeros(batch, out.shape[1], dtype=torch.int32, device=dev) if post_process else None
+        self.idx = torch.zeros(batch, out.shape[1], dtype=torch.int32, device=dev) if post_process in ("quarter", "dark") else None
         self.scale = float(height // out.shape[2])
         self.use_graph = use_graph
         self.graph = None
@@ -448,6 +488,9 @@ class InferStep:
         elif self.post_process == "dark":
             check(self.lib.lh_heatmap_dark(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.blur_kernel,
                                            self.scale, self.preds.data_ptr(), s), "lh_heatmap_dark")
+        elif self.post_process == "soft":
+            check(self.lib.lh_heatmap_soft_argmax(hm.data_ptr(), bj, h, w, self.soft_argmax_beta, self.scale, self.preds.data_ptr(), s),
+                  "lh_heatmap_soft_argmax")
 
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
@@ -480,7 +523,7 @@ class InferPipeline:
     a stream of its own.  The stage 3-4 launches of one batch are latency-bound chains of one wave of tiles; a second batch
     fills the machine under them: R50 256x256 bs 64 bf16, 29.9 k img/s with one batch in flight, 33.3 k with two (MI355X).
     Eval-mode only (the batch-statistics quirk of ``pred_store`` updates the running statistics, which slots would race on).
-    ``flip_test`` / ``shift_heatmap`` / ``post_process`` / ``blur_kernel``: as InferStep's, for every slot.
+    ``flip_test`` / ``shift_heatmap`` / ``post_process`` / ``blur_kernel`` / ``soft_argmax_beta``: as InferStep's, for every slot.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -488,11 +531,12 @@ class InferPipeline:
     """
 
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
-                 blur_kernel=11):
+                 blur_kernel=11, soft_argmax_beta=100.0):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
-                                shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel) for i in range(depth)]
+                                shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
+                                soft_argmax_beta=soft_argmax_beta) for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
         self.count = 0

@@ -31,6 +31,10 @@ to off = the reference's objective; validation then scores the loss with the sam
 ``--unbiased_target`` / ``--dark_decode`` (DARK, Zhang et al. 2020; both off by default): the target Gaussian is rendered around the
 joint's real-valued position instead of the rounded cell (in the step and in the validation loss), and the validation keypoints
 are decoded with the Taylor step on the log of the blurred map instead of the hard arg-max.
+``--coord_loss_weight L`` / ``--soft_argmax_beta B`` / ``--soft_decode`` (integral regression, Sun et al. 2018; off by default): the
+step adds L x the L1 distance between the soft-arg-max under softmax(B * heat-map) and the joint, in input pixels, to the heat-map
+loss (every joint, whatever ``--ohkm_topk`` selects; weighted like the heat-map loss under ``--use_target_weight``); the validation
+loss stays the heat-map loss, and ``--soft_decode`` decodes the validation keypoints with that soft-arg-max (not with ``--dark_decode``).
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -98,7 +102,17 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--unbiased_target", action="store_true",
                    help="DARK's target encoding: the Gaussian around the joint's real-valued position (default: the rounded cell)")
     p.add_argument("--dark_decode", action="store_true", help="decode the validation keypoints with DARK (default: hard arg-max)")
+    p.add_argument("--coord_loss_weight", default=0.0, type=float,
+                   help="integral regression: weight of the L1 loss on the soft-arg-max coordinates, input pixels (0 = off)")
+    p.add_argument("--soft_argmax_beta", default=100.0, type=float, help="softmax temperature of the soft-arg-max (heat-map x beta)")
+    p.add_argument("--soft_decode", action="store_true", help="decode the validation keypoints with the soft-arg-max (default: hard arg-max)")
     args = p.parse_args(argv)
+    if args.soft_decode and args.dark_decode:
+        p.error("--soft_decode and --dark_decode are two decodes: pass one")
+    if not (args.coord_loss_weight >= 0 and np.isfinite(args.coord_loss_weight)):
+        p.error("--coord_loss_weight must be a finite number >= 0")
+    if not (args.soft_argmax_beta > 0 and np.isfinite(args.soft_argmax_beta)):
+        p.error("--soft_argmax_beta must be a finite number > 0")
     args.phase = phase
     args.model = args.root.split("/")[0]                  # src/tools/dataset.py:59 overwrites it from the name
     args.name = os.path.join(args.root, args.name)
@@ -305,6 +319,9 @@ def validate(model, loader, args, u8_step=None):
     # the loss the step trains with (--use_target_weight / --ohkm_topk), so the best-checkpoint decision follows the objective
     use_weight, topk = getattr(args, "use_target_weight", False), getattr(args, "ohkm_topk", 0)
     unbiased, decode = getattr(args, "unbiased_target", False), "dark" if getattr(args, "dark_decode", False) else False
+    beta = getattr(args, "soft_argmax_beta", 100.0)
+    if getattr(args, "soft_decode", False):
+        decode = "soft"
     crit = WeightedJointsMSELoss(topk) if use_weight or topk else JointsMSELoss(False)
     acc = torch.zeros(5, device="cuda")          # loss*b, b, pck*b, epe sum, epe count -- reduced on the device
     with torch.no_grad():
@@ -324,7 +341,7 @@ def validate(model, loader, args, u8_step=None):
             else:
                 target, weight = render_targets(joints, size=hs, unbiased=unbiased), None
             loss = crit(pred, target, weight)
-            kp, _, _ = max_preds_device(pred, scale=float(args.size // hs), post_process=decode)
+            kp, _, _ = max_preds_device(pred, scale=float(args.size // hs), post_process=decode, soft_argmax_beta=beta)
             b = images.shape[0]
             pck, esum, ecnt = device_pck_epe(kp, joints, T=0.2)
             acc += torch.stack([loss * b, torch.tensor(float(b), device="cuda"), pck * b, esum, ecnt])
@@ -408,7 +425,8 @@ def main(args, train_set=None, val_set=None):
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
     loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk,
-                   target_encoding="unbiased" if args.unbiased_target else "quantised")
+                   target_encoding="unbiased" if args.unbiased_target else "quantised",
+                   coord_loss_weight=args.coord_loss_weight, soft_argmax_beta=args.soft_argmax_beta)
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw)
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order

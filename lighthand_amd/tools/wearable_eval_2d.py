@@ -14,7 +14,8 @@ BATCH statistics at evaluation time.  ``--bn_train`` (default, = reference behav
 The configs' TEST block, off by default (= reference behaviour): ``--flip_test`` (TEST.FLIP_TEST) averages the heat-maps of every
 image and of its mirror image, flipped back and shifted one column (``--no_shift_heatmap`` drops the shift, TEST.SHIFT_HEATMAP);
 ``--post_process`` (TEST.POST_PROCESS) refines the arg-max by a quarter pixel; ``--dark_decode [--blur_kernel K]`` decodes with
-DARK instead (a Taylor step on the log of the blurred map; not both).  All run inside the captured InferStep.
+DARK instead (a Taylor step on the log of the blurred map; not both); ``--soft_decode [--soft_argmax_beta B]`` decodes with the
+soft-arg-max under softmax(B * heat-map) instead (with neither of the other two).  All run inside the captured InferStep.
 
 The reference's evaluation set (Armo_hand_dataset) is not redistributable: ``--synthetic N`` builds a seeded
 stand-in with the four occlusion categories and visibility flags.
@@ -53,9 +54,11 @@ class _Steps:
     (argparser.py:258-262) -- padding it would put foreign samples into the BatchNorm batch statistics that
     ``pred_store``'s train-mode forward uses, and into the running-statistics update."""
 
-    def __init__(self, model, size, bn_train, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11):
+    def __init__(self, model, size, bn_train, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11,
+                 soft_argmax_beta=100.0):
         self.model, self.size, self.bn_train, self.steps = model, size, bn_train, {}
-        self.options = dict(flip_test=flip_test, shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel)
+        self.options = dict(flip_test=flip_test, shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
+                            soft_argmax_beta=soft_argmax_beta)
 
     def __call__(self, images):
         from lighthand_amd.runtime import InferStep
@@ -67,10 +70,10 @@ class _Steps:
 
 
 def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False,
-               blur_kernel=11):
+               blur_kernel=11, soft_argmax_beta=100.0):
     """src/utils/argparser.py:246-281 with the forward + arg-max decode on the device."""
     meta = {c: {"bb": [], "pred": [], "gt": []} for c in CATEGORIES}
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel, soft_argmax_beta)
     for images, joints_v, cats in loader:
         preds = step(images).cpu()                       # already x4 (method.py:157)
         gt = joints_v[:, :, :2]
@@ -88,12 +91,12 @@ def pred_store(model, loader, out_json, batch, size, bn_train=True, flip_test=Fa
 
 
 def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False,
-                    blur_kernel=11):
+                    blur_kernel=11, soft_argmax_beta=100.0):
     """src/utils/argparser.py:284-323 -- the category-less variant: one entry per BATCH of predictions (x4, 256-px frame),
     ground truth and bounding-box diagonals; read back by ``lighthand_amd.metrics.pred_test``.  The loader yields
     (images, gt_2d_joints[, ...])."""
     meta = {"pred": [], "gt": [], "bb": []}
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel, soft_argmax_beta)
     for item in loader:
         images, gt = item[0], item[1][:, :, :2]
         preds = step(images).cpu()
@@ -108,13 +111,14 @@ def pred_store_test(model, loader, out_json, batch, size, bn_train=True, flip_te
     return meta
 
 
-def device_eval(model, loader, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11):
+def device_eval(model, loader, batch, size, bn_train=True, flip_test=False, shift_heatmap=True, post_process=False, blur_kernel=11,
+                soft_argmax_beta=100.0):
     """Same evaluation reduced ON THE DEVICE: per threshold set the PCK-curve counts of all visible
     joints are accumulated by lh_pck_curve, summed across data-parallel ranks with one small all-reduce, and read by
     the host once.  Returns {(type, T1): [auc, epe_mm, curve]}; the AUC equals pred_eval's 'mean_auc' AUC (whose EPE is
     diluted by the reference's zeros quirk; the EPE here is the plain mean)."""
     from lighthand_amd.metrics import auc_from_counts, device_pck_curve
-    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel)
+    step = _Steps(model, size, bn_train, flip_test, shift_heatmap, post_process, blur_kernel, soft_argmax_beta)
     acc = {(t, tuple(T)): None for t, T in THRESHOLDS}
     for images, joints_v, _ in loader:
         preds = step(images)
@@ -166,6 +170,9 @@ def build_parser():
     ap.add_argument("--dark_decode", action="store_true",
                     help="DARK decode: a Taylor step on the log of the blurred heat-map, in place of --post_process")
     ap.add_argument("--blur_kernel", default=11, type=int, help="with --dark_decode: taps of the Gaussian blur (odd, 3..17)")
+    ap.add_argument("--soft_decode", action="store_true",
+                    help="soft-arg-max decode: the expectation under softmax(beta * heat-map), in place of --post_process / --dark_decode")
+    ap.add_argument("--soft_argmax_beta", default=100.0, type=float, help="with --soft_decode: the softmax temperature (> 0)")
     return ap
 
 
@@ -178,8 +185,13 @@ def main(argv=None):
         ap.error("--no_shift_heatmap applies to --flip_test")
     if args.post_process and args.dark_decode:
         ap.error("--post_process and --dark_decode are two decodes: pass one")
+    if args.soft_decode and (args.post_process or args.dark_decode):
+        ap.error("--soft_decode excludes --post_process and --dark_decode: pass one decode")
+    if not (args.soft_argmax_beta > 0 and np.isfinite(args.soft_argmax_beta)):
+        ap.error("--soft_argmax_beta must be a finite number > 0")
     test_opts = dict(flip_test=args.flip_test, shift_heatmap=args.shift_heatmap,
-                     post_process="dark" if args.dark_decode else args.post_process, blur_kernel=args.blur_kernel)
+                     post_process="soft" if args.soft_decode else "dark" if args.dark_decode else args.post_process,
+                     blur_kernel=args.blur_kernel, soft_argmax_beta=args.soft_argmax_beta)
     if not args.synthetic:
         raise SystemExit("the Armo_hand evaluation set is not shipped: pass --synthetic N or plug your own Dataset")
     data = SyntheticEvalSet(args.synthetic, args.size)

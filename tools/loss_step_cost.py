@@ -3,8 +3,9 @@
 (lh_gaussian_target + lh_mse_heatmap) against use_target_weight (lh_gaussian_target_w + lh_joints_mse: the same passes), ohkm_topk=8
 (plane sums, select, gradient: one more read of the selected planes) and both, alternated in ONE process on R50 64 x 256^2 bf16.
 Every joint is visible and in frame, so all forms train on the same planes.  Device events around `steps` replays, after a warm-up;
-median over the rounds.
-usage (GPU box): python tools/loss_step_cost.py [steps] [rounds]"""
+median over the rounds.  --coord_loss_weight L adds a leg: the plain step plus the integral-regression coordinate loss
+(lh_integral_l1 behind lh_mse_heatmap: one more read of the heat-maps, one read and write of their gradient).
+usage (GPU box): python tools/loss_step_cost.py [steps] [rounds] [--coord_loss_weight L]"""
 import os
 import statistics
 import sys
@@ -15,8 +16,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from lighthand_amd.runtime import TrainStep  # noqa: E402
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+argv = sys.argv[1:]
+coord = None
+if "--coord_loss_weight" in argv:
+    k = argv.index("--coord_loss_weight")
+    coord = float(argv[k + 1])
+    del argv[k:k + 2]
+steps = int(argv[0]) if len(argv) > 0 else 30
+rounds = int(argv[1]) if len(argv) > 1 else 5
 dev = torch.device("cuda", 0)
 batch = 64
 
@@ -33,8 +40,11 @@ def timed(step, n):
 
 images, joints = bench.synthetic_batch(batch, 256, dev)
 forms = {}
-for tag, kw in (("plain", {}), ("weighted", dict(use_target_weight=True)), ("ohkm-8", dict(ohkm_topk=8)),
-                ("weighted+ohkm-8", dict(use_target_weight=True, ohkm_topk=8))):
+legs = [("plain", {}), ("weighted", dict(use_target_weight=True)), ("ohkm-8", dict(ohkm_topk=8)),
+        ("weighted+ohkm-8", dict(use_target_weight=True, ohkm_topk=8))]
+if coord is not None:
+    legs.append((f"coord-{coord:g}", dict(coord_loss_weight=coord)))
+for tag, kw in legs:
     step = TrainStep(bench.build_model(depth=50, precision="bf16"), batch, 256, 256, lr=1e-3, **kw)
     step(images, joints)
     timed(step, 10)                                                   # warm-up (capture happened in the first call)
