@@ -83,9 +83,9 @@ class BnGate:
         self._gated[id(x)] = (partial, rows, partial2)
 
     def _gate_meta(self, dd, x):
-        """(kernel name, extra algorithmic bytes) of the data gradient just emitted when it is a gated launch (lh_igemm_gated): the persistent
-        kernels have gate instantiations of their own (igemm_pw_kernel<.., true, terms>, conv3x3_direct_kernel<.., true, true>), and the
-        epilogue reads the BatchNorm input of every gated term (what the reduce pass of lh_fuse_bwd no longer reads) plus the mask bits."""
+        """(kernel name, extra algorithmic bytes) of the data gradient just emitted when it is a gated launch (lh_igemm_gated): every kernel
+        has gate instantiations of its own (igemm_ring_gated_kernel<..>, igemm_pw_kernel<.., true, terms>, conv3x3_direct_kernel<.., true, true>),
+        and the epilogue reads the BatchNorm input of every gated term (what the reduce pass of lh_fuse_bwd no longer reads) plus the mask bits."""
         c = self.bwd[-1]
         if getattr(c, "fn", None) is not self.lib.lh_igemm_gated:
             return None, 0.0
@@ -96,4 +96,6 @@ class BnGate:
             name = name[:-1] + f", {terms}>"
         elif name.startswith("conv3x3_direct_kernel"):
             name = name[:-1] + ", true>"
+        elif name.startswith("igemm_ring_kernel"):
+            name = name.replace("igemm_ring_kernel", "igemm_ring_gated_kernel", 1)
         return name, float(terms) * x.pixels * x.c * self.es + (x.pixels * x.c / 8 if "mask" in c.what else 0.0)

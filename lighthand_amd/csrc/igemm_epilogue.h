@@ -36,7 +36,18 @@ __device__ __forceinline__ void igemm_epilogue_consts(const IgemmArgs& p, float*
     }
 }
 
-template <typename T, int BM, int BP, int WC, int WP>
+// What the BatchNorm-backward gate (lh_igemm_gated) keeps per thread: the BN input and mask bits of its NR rows and the gate constants of its
+// EPC channels.  Members of the GATE instantiation only: behind run-time tests they sat beside ad[] in every launch and pushed the
+// 256-pixel tiles into scratch memory (round 8; the rule of igemm_pw_kernel's GATE parameter).
+template <int NR, int EPC, bool GATE> struct EpilogueGate {
+    uint4 xd[NR];                                     // the BN input at the output position
+    unsigned gbits[NR];
+    float gmean[EPC], ginv[EPC], gsc[EPC], gsh[EPC];  // every thread loads, index clamped
+};
+template <int NR, int EPC> struct EpilogueGate<NR, EPC, false> {};
+
+// GATE: the launch carries the gate (p.gx is set; igemm_ring_gated_kernel) -- the host selects the instantiation.
+template <typename T, int BM, int BP, int WC, int WP, bool GATE = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char* smem, f32x4 (&acc)[BM / WC / 16][BP / WP / 16],
                                                int pblk, int cblk, int tid, int lane, int wc, int wp, int hw,
                                                int ooh, int oow, float* stats) {
@@ -120,17 +131,14 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char
     static_assert(BP % RPP == 0, "rows per thread");
     int opx[NR];                                      // output pixel of row k, -1: nothing to store
     uint4 ad[NR];
-    uint4 xd[NR];                                     // BatchNorm-backward gate (lh_igemm_gated): the BN input at the output position
     unsigned mbits[NR];
-    unsigned gbits[NR];
-    // gate constants of this thread's EPC channels (every thread loads, index clamped)
-    float gmean[EPC], ginv[EPC], gsc[EPC], gsh[EPC];
-    if (p.gx) {
+    EpilogueGate<NR, EPC, GATE> gt;
+    if constexpr (GATE) {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const int gk = col0 + e < p.cout ? col0 + e : p.cout - 1;
-            gmean[e] = p.gmean[gk]; ginv[e] = p.ginv[gk];
-            gsc[e] = p.gmask ? 0.f : p.gscale[gk]; gsh[e] = p.gmask ? 0.f : p.gshift[gk];
+            gt.gmean[e] = p.gmean[gk]; gt.ginv[e] = p.ginv[gk];
+            gt.gsc[e] = p.gmask ? 0.f : p.gscale[gk]; gt.gsh[e] = p.gmask ? 0.f : p.gshift[gk];
         }
     }
 #pragma unroll
@@ -151,13 +159,12 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char
             ad[k] = *reinterpret_cast<const uint4*>(ok ? p.addend + eoff * ES : p.zero);
             if (p.addend_mask) mbits[k] = *(ok ? p.addend_mask + eoff / EPC : p.zero);    // addend = upstream gradient, gated by the activation's ReLU mask
         }
-        xd[k] = uint4{0u, 0u, 0u, 0u};
-        gbits[k] = 0xffu;
-        if (p.gx) {
+        if constexpr (GATE) {
+            gt.gbits[k] = 0xffu;
             const bool ok = opx[k] >= 0;
             const long eoff = (long)((unsigned long)(unsigned)(ok ? opx[k] : 0) * (unsigned)p.out_pix_stride) + col0;
-            xd[k] = *reinterpret_cast<const uint4*>(ok ? p.gx + eoff * ES : p.zero);
-            if (p.gmask) gbits[k] = *(ok ? p.gmask + eoff / EPC : p.zero);      // a residual tail: its sign was stored as mask bits
+            gt.xd[k] = *reinterpret_cast<const uint4*>(ok ? p.gx + eoff * ES : p.zero);
+            if (p.gmask) gt.gbits[k] = *(ok ? p.gmask + eoff / EPC : p.zero);      // a residual tail: its sign was stored as mask bits
         }
     }
 #pragma unroll
@@ -188,17 +195,17 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char
             }
             u = pack16<T>(v);
         }
-        if (p.gx) {
+        if constexpr (GATE) {
             // the stored value is the gradient of relu(BN(x)): gate it with the activation's sign (recomputed from x as the
             // BN-backward kernels do, fuse_bwd.hip fuse_bwd_reduce_flat<T, MASK_X>) and take its share of the BatchNorm-backward sums
             float g[EPC], xv[EPC];
             unpack16<T>(u, g);
-            unpack16<T>(xd[k], xv);
+            unpack16<T>(gt.xd[k], xv);
 #pragma unroll
             for (int e = 0; e < EPC; ++e) {
-                g[e] = (p.gmask ? ((gbits[k] >> e) & 1u) != 0u : (xv[e] * gsc[e] + gsh[e]) > 0.f) ? g[e] : 0.f;
+                g[e] = (p.gmask ? ((gt.gbits[k] >> e) & 1u) != 0u : (xv[e] * gt.gsc[e] + gt.gsh[e]) > 0.f) ? g[e] : 0.f;
                 s1[e] += g[e];
-                s2[e] += g[e] * (xv[e] - gmean[e]) * ginv[e];
+                s2[e] += g[e] * (xv[e] - gt.gmean[e]) * gt.ginv[e];
             }
             u = pack16<T>(g);
         } else if (stats) {

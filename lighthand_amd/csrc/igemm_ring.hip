@@ -19,6 +19,15 @@ int lh_ring_launch_f16_small(const IgemmArgs& a, const RingCfg& c, hipStream_t s
 int lh_ring_launch_bf16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_f16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_launch_f32(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+// the gated kernels (igemm_ring_gated_kernel: launches that carry a BatchNorm-backward gate), translation units of their own
+int lh_ring_gated_launch_bf16_big(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_bf16_mid(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_bf16_small(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_bf16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_f16_big(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_f16_mid(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_f16_small(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
+int lh_ring_gated_launch_f16_dense(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
 int lh_ring_multi_launch_bf16(const LhMulti<IgemmArgs>& m, const RingCfg& c, hipStream_t s);
 int lh_ring_multi_launch_f16(const LhMulti<IgemmArgs>& m, const RingCfg& c, hipStream_t s);
 int lh_pw_launch_bf16(const IgemmArgs& a, const RingCfg& c, hipStream_t s);
@@ -361,20 +370,39 @@ int lh_igemm_ring_launch(const IgemmArgs& a0, const RingCfg& c, int dtype, hipSt
         return rc;
     }
     if (int e = lh_ring_offsets_fit(a, c.bm, c.bp, dtype == LH_F32 ? 4 : 2)) return e;
+    const bool gated = a.gx != nullptr;                  // the gate is compiled into kernels of its own (igemm_ring_gated_kernel)
     switch (dtype) {
         case LH_BF16:
+            if (gated) {
+                rc = lh_ring_gated_launch_bf16_big(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_bf16_mid(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_bf16_small(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_bf16_dense(a, c, s);
+                break;
+            }
             rc = lh_ring_launch_bf16_big(a, c, s);
             if (rc == 1) rc = lh_ring_launch_bf16_mid(a, c, s);
             if (rc == 1) rc = lh_ring_launch_bf16_small(a, c, s);
             if (rc == 1) rc = lh_ring_launch_bf16_dense(a, c, s);
             break;
         case LH_F16:
+            if (gated) {
+                rc = lh_ring_gated_launch_f16_big(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_f16_mid(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_f16_small(a, c, s);
+                if (rc == 1) rc = lh_ring_gated_launch_f16_dense(a, c, s);
+                break;
+            }
             rc = lh_ring_launch_f16_big(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_mid(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_small(a, c, s);
             if (rc == 1) rc = lh_ring_launch_f16_dense(a, c, s);
             break;
         case LH_F32:
+            if (gated) {
+                lh_set_error("igemm_ring: the BatchNorm-backward gate exists for the 16-bit types only");
+                return LH_ERR_UNSUPPORTED;
+            }
             rc = lh_ring_launch_f32(a, c, s);
             break;
         default:
@@ -395,6 +423,8 @@ int lh_igemm_ring_multi_launch(LhMulti<IgemmArgs>& m, const RingCfg& c, int dtyp
         return LH_ERR_HIP;
     }
     for (int i = 0; i < m.n; ++i) { m.a[i].zero = z; m.a[i].dump = dump_page(); }
+    for (int i = 0; i < m.n; ++i)                        // (lh_igemm_multi has no gate argument; the multi-problem kernel is compiled without one)
+        LH_REQUIRE(!m.a[i].gx, "igemm_ring_multi: problem %d carries a BatchNorm-backward gate, which the multi-problem kernel does not have", i);
     for (int i = 0; i < m.n; ++i)
         if (int e = lh_ring_offsets_fit(m.a[i], c.bm, c.bp, 2)) return e;
     int rc = 1;

@@ -91,7 +91,8 @@ template <int L, int MAXS> __device__ __forceinline__ void wait_stages(int stage
 
 // The kernel proper, for workgroup `bid` of `nblk` of ONE problem: the plain kernel passes its block index, the
 // multi-problem kernel (multi.h) the index inside the problem the workgroup belongs to.
-template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
+// GATE: the epilogue carries the BatchNorm-backward gate (igemm_epilogue.h) -- the body of igemm_ring_gated_kernel.
+template <typename T, int BM, int BP, int WC, int WP, int D, int KB, bool GATE = false>
 __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned char* smem, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)      // the buffer builtins exist in the device pass only
     constexpr int ES = sizeof(T);
@@ -291,13 +292,13 @@ __device__ __forceinline__ void igemm_ring_body(const IgemmArgs& p, unsigned cha
             step(ic<1>{}, so);
         }
     }
-    if constexpr (BM == 256 && BP == 256 && sizeof(T) == 2) {
+    if constexpr (BM == 256 && BP == 256 && sizeof(T) == 2 && !GATE) {       // (a gated launch is a data gradient: no head)
         if (p.head_w) {
             igemm_epilogue_head<T, BM, BP, WC, WP, MmaR<T>>(p, smem, acc, pblk, tid, lane, wave, wc, wp, hw, ooh, oow);
             return;
         }
     }
-    igemm_epilogue<T, BM, BP, WC, WP>(p, smem, acc, pblk, cblk, tid, lane, wc, wp, hw, ooh, oow, stats);
+    igemm_epilogue<T, BM, BP, WC, WP, GATE>(p, smem, acc, pblk, cblk, tid, lane, wc, wp, hw, ooh, oow, stats);
 #endif
 }
 
@@ -310,6 +311,15 @@ __global__ __launch_bounds__(64 * WC * WP, (ring_waves_per_simd<BM, BP, WC, WP>(
     igemm_ring_body<T, BM, BP, WC, WP, D, KB>(p, smem, blockIdx.x, gridDim.x);
 }
 
+// The same kernel with the BatchNorm-backward gate in its epilogue (lh_igemm_gated; launch_ring picks it when the launch carries a gate).
+// An instantiation of its own, as the pointwise kernel's GATE forms are: the gate's registers exist only here, and the plain kernel above
+// keeps its name and its register budget.  (lh_igemm_multi takes no gate, so the multi-problem kernel below has no gated twin.)
+template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
+__global__ __launch_bounds__(64 * WC * WP, (ring_waves_per_simd<BM, BP, WC, WP>())) void igemm_ring_gated_kernel(const IgemmArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    igemm_ring_body<T, BM, BP, WC, WP, D, KB, true>(p, smem, blockIdx.x, gridDim.x);
+}
+
 // Up to LH_MULTI_MAX independent convolutions that share the kernel configuration as ONE grid (lh_igemm_multi).
 template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
 __global__ __launch_bounds__(64 * WC * WP, 2) void igemm_ring_multi_kernel(const LhMulti<IgemmArgs> m) {
@@ -319,25 +329,34 @@ __global__ __launch_bounds__(64 * WC * WP, 2) void igemm_ring_multi_kernel(const
     igemm_ring_body<T, BM, BP, WC, WP, D, KB>(m.a[i], smem, bid, nblk);
 }
 
-template <typename T, int BM, int BP, int WC, int WP, int D, int KB>
+// GATE names the kernel of the translation unit (igemm_ring_inst.h: the gated instantiations are compiled apart from the plain ones);
+// a launch that carries a gate runs the gated kernel and no other.
+template <typename T, int BM, int BP, int WC, int WP, int D, int KB, bool GATE = false>
 static int launch_ring(const IgemmArgs& a, hipStream_t s) {
     constexpr int ES = sizeof(T);
     constexpr int ring = D * (BM + BP) * KB;
     constexpr int epi = lh_epi_lds_bytes<T, BM, BP, (BM == 256 && BP == 256 && ES == 2)>();   // tile + the fused head's weights + per-channel constants
     constexpr int lds = ring > epi ? ring : epi;
     static_assert(lds <= 160 * 1024, "LDS budget");
+    if ((a.gx != nullptr) != GATE) {
+        lh_set_error("igemm_ring: a launch %s a BatchNorm-backward gate was handed to the %s kernel", a.gx ? "with" : "without", GATE ? "gated" : "plain");
+        return LH_ERR_ARG;
+    }
+    const void* kernel;
+    if constexpr (GATE) kernel = reinterpret_cast<const void*>(&igemm_ring_gated_kernel<T, BM, BP, WC, WP, D, KB>);
+    else kernel = reinterpret_cast<const void*>(&igemm_ring_kernel<T, BM, BP, WC, WP, D, KB>);
     if (lds > 64 * 1024) {
         // per-device function attribute; cheap enough to set on every launch (no process-wide "done" flag:
         // a process may drive several devices)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_ring_kernel<T, BM, BP, WC, WP, D, KB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) {
             lh_set_error("igemm_ring: cannot raise dynamic LDS to %d bytes: %s", lds, hipGetErrorString(e));
             return LH_ERR_HIP;
         }
     }
     dim3 grid(ceil_div(a.M, BP) * ceil_div(a.cout, BM) * (a.nphase > 1 ? a.nphase : 1));
-    hipLaunchKernelGGL((igemm_ring_kernel<T, BM, BP, WC, WP, D, KB>), grid, dim3(64 * WC * WP), lds, s, a);
+    if constexpr (GATE) hipLaunchKernelGGL((igemm_ring_gated_kernel<T, BM, BP, WC, WP, D, KB>), grid, dim3(64 * WC * WP), lds, s, a);
+    else hipLaunchKernelGGL((igemm_ring_kernel<T, BM, BP, WC, WP, D, KB>), grid, dim3(64 * WC * WP), lds, s, a);
     LH_LAUNCH_CHECK("igemm_ring launch");
     return LH_OK;
 }

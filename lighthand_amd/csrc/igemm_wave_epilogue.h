@@ -20,7 +20,8 @@
 // tail (p.gmask) -- and s1 / s2 take { g, g * (gx - mean) * invstd }: the first half of that BatchNorm's backward pass (fuse_bwd.hip
 // fuse_bwd_reduce_flat) on the tile the wave holds.  cst = mean[BM], invstd[BM], scale[BM], shift[BM]; no affine on the accumulator.
 // GATE = 2: the tail's other term is a projection shortcut r = BN2(gx2): s3 takes g * (gx2 - mean2) * invstd2 (cst continues with mean2[BM],
-// invstd2[BM]); the sign comes from the mask bits.
+// invstd2[BM]); the sign comes from the mask bits (lh_igemm_gated refuses x2 without mask), so scale / shift are never fetched: their 16
+// registers are what pushed igemm_pw_kernel<.., 128, 64, 2, true, 2> into scratch memory.
 template <typename T, int BM, int PT, bool STATS, int GATE = 0, typename PixFn, int NS, int NS3>
 __device__ __forceinline__ void wave_epilogue(const IgemmArgs& p, f32x4 (&acc)[BM / 16][PT], unsigned char* stg, const float* cst,
                                               const int cblk, const int lane, PixFn&& pix, float (&s1)[NS][8], float (&s2)[NS][8],
@@ -64,11 +65,17 @@ __device__ __forceinline__ void wave_epilogue(const IgemmArgs& p, f32x4 (&acc)[B
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float4 a = *reinterpret_cast<const float4*>(cst + cc + 4 * h), b = *reinterpret_cast<const float4*>(cst + BM + cc + 4 * h);
-                const float4 c = *reinterpret_cast<const float4*>(cst + 2 * BM + cc + 4 * h), d = *reinterpret_cast<const float4*>(cst + 3 * BM + cc + 4 * h);
+                float4 c = float4{0.f, 0.f, 0.f, 0.f}, d = c;
+                if constexpr (GATE != 2) {
+                    c = *reinterpret_cast<const float4*>(cst + 2 * BM + cc + 4 * h);
+                    d = *reinterpret_cast<const float4*>(cst + 3 * BM + cc + 4 * h);
+                }
                 gmean[4 * h] = a.x; gmean[4 * h + 1] = a.y; gmean[4 * h + 2] = a.z; gmean[4 * h + 3] = a.w;
                 ginv[4 * h] = b.x; ginv[4 * h + 1] = b.y; ginv[4 * h + 2] = b.z; ginv[4 * h + 3] = b.w;
-                gsc[4 * h] = c.x; gsc[4 * h + 1] = c.y; gsc[4 * h + 2] = c.z; gsc[4 * h + 3] = c.w;
-                gsh[4 * h] = d.x; gsh[4 * h + 1] = d.y; gsh[4 * h + 2] = d.z; gsh[4 * h + 3] = d.w;
+                if constexpr (GATE != 2) {
+                    gsc[4 * h] = c.x; gsc[4 * h + 1] = c.y; gsc[4 * h + 2] = c.z; gsc[4 * h + 3] = c.w;
+                    gsh[4 * h] = d.x; gsh[4 * h + 1] = d.y; gsh[4 * h + 2] = d.z; gsh[4 * h + 3] = d.w;
+                }
                 if constexpr (GATE == 2) {
                     const float4 a2 = *reinterpret_cast<const float4*>(cst + 4 * BM + cc + 4 * h), b2 = *reinterpret_cast<const float4*>(cst + 5 * BM + cc + 4 * h);
                     gmean2[4 * h] = a2.x; gmean2[4 * h + 1] = a2.y; gmean2[4 * h + 2] = a2.z; gmean2[4 * h + 3] = a2.w;
@@ -124,10 +131,10 @@ __device__ __forceinline__ void wave_epilogue(const IgemmArgs& p, f32x4 (&acc)[B
                 float g[EPC], xv[EPC];
                 unpack16<T>(u, g);
                 unpack16<T>(xd[k], xv);
-                if (p.gmask) {
+                if (GATE == 2 || p.gmask) {
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) g[e] = ((gm[k] >> e) & 1u) ? g[e] : 0.f;
-                } else {
+                } else if constexpr (GATE != 2) {
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) g[e] = (xv[e] * gsc[e] + gsh[e]) > 0.f ? g[e] : 0.f;
                 }
