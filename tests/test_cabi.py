@@ -146,6 +146,29 @@ def test_explicit_wgrad_configuration_must_fit():
     assert b"does not fit" in lib.lh_last_error()
 
 
+# R50's stage 4 (three bottlenecks + the projection, pose_resnet.py:61-99, 177-192) as (cout, cin, kernel)
+_R50_STAGE4 = [(512, 2048, 1), (512, 512, 3), (2048, 512, 1)] * 2 + [(512, 1024, 1), (512, 512, 3), (2048, 512, 1), (2048, 1024, 1)]
+
+
+def _wgrad_table_calls(convs, n, h, w):
+    """The lh_wgrad_call array of the weight gradients of `convs` = (cout, cin, kernel, stride), each on an n x h x w input, with
+    dense OIHW gradients; the second value keeps the descriptors and tap lists alive."""
+    from lighthand_amd import _lib
+    keep, calls = [], (_lib.WgradCall * len(convs))()
+    for i, (cout, cin, k, st) in enumerate(convs):
+        d = _conv_desc(cin, cout, k=k)
+        d.n, d.hi, d.wi, d.sh, d.sw = n, h, w, st, st
+        d.ho = d.OH = (h - 1) // st + 1
+        d.wo = d.OW = (w - 1) // st + 1
+        taps = (C.c_int * (2 * k * k))(*[v for r in range(k) for q in range(k) for v in (r, q)])
+        keep += [d, taps]
+        calls[i].d, calls[i].rows, calls[i].x, calls[i].dy, calls[i].dy_pix_stride = C.pointer(d), 0, 4096, 8192, cout
+        calls[i].n_out, calls[i].n_in, calls[i].grad = cout, cin, 1 << 20
+        calls[i].so, calls[i].si, calls[i].sr, calls[i].ss = cin * k * k, k * k, k, 1
+        calls[i].taps_rs, calls[i].accumulate = C.cast(taps, C.POINTER(C.c_int)), 0
+    return calls, keep
+
+
 def test_wgrad_table_planner_runs_without_a_device(monkeypatch):
     """lh_wgrad_table_build's size query is host arithmetic: the weight gradients of R50's stage 4 at batch 64 (three bottlenecks +
     the projection, pose_resnet.py:61-99, 177-192: M = 64 x 8 x 8 pixels) in one table.  Automatic item length: the tiles alone fill the
@@ -154,17 +177,8 @@ def test_wgrad_table_planner_runs_without_a_device(monkeypatch):
     from lighthand_amd import _lib
     lib = _lib.load()
     monkeypatch.setenv("LH_WGRAD_TABLE_XCD", "0")                  # the plain longest-first item order: exact item counts
-    shapes = [(512, 2048, 1), (512, 512, 3), (2048, 512, 1)] * 2 + [(512, 1024, 1), (512, 512, 3), (2048, 512, 1), (2048, 1024, 1)]
-    descs, rs, calls = [], [], (_lib.WgradCall * len(shapes))()
-    for i, (cout, cin, k) in enumerate(shapes):
-        d = _conv_desc(cin, cout, hw=8, k=k)
-        d.n = 64
-        taps = (C.c_int * (2 * k * k))(*[v for r in range(k) for q in range(k) for v in (r, q)])
-        descs.append(d); rs.append(taps)
-        calls[i].d, calls[i].rows, calls[i].x, calls[i].dy, calls[i].dy_pix_stride = C.pointer(d), 0, 4096, 8192, cout
-        calls[i].n_out, calls[i].n_in, calls[i].grad = cout, cin, 1 << 20
-        calls[i].so, calls[i].si, calls[i].sr, calls[i].ss = cin * k * k, k * k, k, 1
-        calls[i].taps_rs, calls[i].accumulate = C.cast(taps, C.POINTER(C.c_int)), 0
+    shapes = _R50_STAGE4
+    calls, _keep = _wgrad_table_calls([(co, ci, k, 1) for co, ci, k in shapes], 64, 8, 8)
     info = _lib.WgradTableInfo()
     cfg = (C.c_int * 4)(128, 128, 64, 3)
     assert lib.lh_wgrad_table_build(calls, len(shapes), _lib.LH_BF16, cfg, 0, None, None, 0, C.byref(info)) == 0, lib.lh_last_error()
@@ -187,6 +201,49 @@ def test_wgrad_table_planner_runs_without_a_device(monkeypatch):
     assert lib.lh_wgrad_table_build(calls, len(shapes), _lib.LH_BF16, bad, 0, None, None, 0, C.byref(info)) == -3
     assert b"not compiled in" in lib.lh_last_error()
     assert lib.lh_wgrad_table_build(calls, len(shapes), _lib.LH_F32, cfg, 0, None, None, 0, C.byref(info)) == -1
+
+
+def _wgrad_table_infos():
+    """Every integer field of lh_wgrad_table_info from the size query, for R50's stage 4 at batch 64 and for the small mixed table
+    of tests/test_gpu_wgrad_table.py's ChainNet (n = 3, 12 x 20 pixels), three tile classes, automatic and forced item length, both
+    item orders.  Returns {case name: [status, field values in WgradTableInfo order]}."""
+    from lighthand_amd import _lib
+    lib = _lib.load()
+    tables = {"r50_stage4": _wgrad_table_calls([(co, ci, k, 1) for co, ci, k in _R50_STAGE4], 64, 8, 8),
+              "chain": _wgrad_table_calls([(128, 64, 3, 1), (256, 128, 1, 1), (256, 256, 1, 2), (256, 128, 3, 1)], 3, 12, 20)}
+    saved, out = os.environ.get("LH_WGRAD_TABLE_XCD"), {}
+    try:
+        for xcd in (None, "0"):
+            os.environ.pop("LH_WGRAD_TABLE_XCD", None)
+            if xcd is not None:
+                os.environ["LH_WGRAD_TABLE_XCD"] = xcd
+            for name, (calls, _keep) in tables.items():
+                for cfg in ((256, 256, 32, 3), (128, 128, 64, 3), (64, 64, 32, 4)):
+                    for target in (0, 8):
+                        info = _lib.WgradTableInfo()
+                        rc = lib.lh_wgrad_table_build(calls, len(calls), _lib.LH_BF16, (C.c_int * 4)(*cfg), target, None, None, 0, C.byref(info))
+                        case = f"{name} cfg={','.join(map(str, cfg))} target={target} xcd={'unset' if xcd is None else xcd}"
+                        out[case] = [rc] + [int(getattr(info, f)) for f, _ in _lib.WgradTableInfo._fields_]
+    finally:
+        os.environ.pop("LH_WGRAD_TABLE_XCD", None)
+        if saved is not None:
+            os.environ["LH_WGRAD_TABLE_XCD"] = saved
+    return out
+
+
+def test_wgrad_table_planner_output_is_pinned():
+    """The table planner decides every member's split count -- the fp32 summation order, hence the bits of the gradients -- and the
+    work-item order.  Its size-query output is pinned to tests/golden/wgrad_table_info.json, recorded from the library before the
+    planner was split into steps: item and fold counts, the largest split count, the item length, the fold's LDS, the blob offsets,
+    table and workspace sizes must all be equal."""
+    import json
+    from lighthand_amd import _lib
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "wgrad_table_info.json")))
+    assert want["fields"] == ["status"] + [f for f, _ in _lib.WgradTableInfo._fields_]
+    got = _wgrad_table_infos()
+    assert sorted(got) == sorted(want["cases"]) and len(got) == 24
+    for case, values in got.items():
+        assert values == want["cases"][case], (case, dict(zip(want["fields"], zip(values, want["cases"][case]))))
 
 
 def test_ctypes_structs_mirror_the_header_layout(tmp_path):
