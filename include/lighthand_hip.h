@@ -80,6 +80,31 @@ int lh_affine_points(const float* pts, int pstride, const float* fwd_dev, float*
  * lh_image_to_nhwc4 and the lh_image_u8_* entries write, run dtype) in place, img'[y][x] = img[y][w-1-x]; the padding is
  * not touched.  A bit-exact copy: a second call restores the input. */
 int lh_nhwc4_mirror(void* img, int n, int h, int w, int pad, int wp, int dtype, void* stream);
+/* Top-down inference on full frames.  Coordinates are pixel indices (pixel centres on the integers, an image spans
+ * [-0.5, size-0.5]); a box is (x0, y0, x1, y1), the box that encloses pixels i0..i1 is (i0-0.5, i1+0.5).  All fp32, in this order:
+ * lh_box_affine: boxes_dev fp32 [b][4], frame_index_dev int32 [b] -> mat_dev fp32 [b][6] (crop pixel index -> frame pixel index of
+ * an h x w crop) and src_frame_dev int32 [b].  bw = x1-x0, bh = y1-y0, cx = (x0+x1)*0.5, cy = (y0+y1)*0.5,
+ * sw = padding * max(bw, bh*w/h), sh = sw*h/w, a = sw/w, mat = [a, 0, (cx - sw*0.5) + a*0.5, 0, a, (cy - sh*0.5) + a*0.5].
+ * src_frame[i] = frame_index[i] when that lies in 0..n_frames-1 and the box is finite with bw > 0 and bh > 0; otherwise the slot
+ * is empty: src_frame[i] = -1 and mat[i] = 0. */
+int lh_box_affine(const float* boxes_dev, const int* frame_index_dev, int b, int n_frames, int h, int w, float padding,
+                  float* mat_dev, int* src_frame_dev, void* stream);
+/* frames_u8 [n_frames][hs][ws][3], shared by all b slots -> padded NHWC4 crops [b][h+2*pad][wp][4] in the run dtype.  Output pixel
+ * (ox, oy) of slot i samples frame src_frame[i] at fx = (m0*ox + m1*oy) + m2, fy = (m3*ox + m4*oy) + m5: inside
+ * [-0.5, ws-0.5] x [-0.5, hs-0.5] bilinearly with lh_image_u8_warp_to_nhwc4's edge clamp and blend order, * (1/255); outside
+ * (NaN included) and in every pixel of an empty slot (src_frame outside 0..n_frames-1) black, 0 before Normalize; then
+ * (c - mean) * (1/std) (HOST float[3] arrays).  The whole buffer is written: padding and channel 3 are zero.  out must be 8-byte aligned
+ * (every dtype: the 16-bit dtypes store a pixel record as one 8-byte word).  A whole-frame box
+ * with hs = h, ws = w and padding 1 reproduces lh_image_u8_to_nhwc4 bit for bit. */
+int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
+                            int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                            int dtype, void* stream);
+/* preds_dev fp32 [b][j][2] (frame coordinates), maxvals_dev fp32 [b][j] -> next_boxes_dev fp32 [b][4], lost_dev int32 [b]: the bounds
+ * of the keypoints with maxval >= min_score, each side widened about its centre to at least min_side.  With fewer than min_joints
+ * such keypoints, or for an empty slot (src_frame < 0), next_boxes[i] = boxes[i] and lost[i] = 1; otherwise lost[i] = 0.  No
+ * atomics: bit-reproducible.  next_boxes_dev must not be boxes_dev. */
+int lh_keypoints_to_boxes(const float* preds_dev, const float* maxvals_dev, const float* boxes_dev, const int* src_frame_dev, int b,
+                          int j, float min_score, int min_joints, float min_side, float* next_boxes_dev, int* lost_dev, void* stream);
 /* NHWC (run dtype) -> NCHW fp32 heatmaps (what model(images) returns, pose_resnet.py:246)
  * and the inverse for the incoming gradient. c_stride = channel stride of the NHWC side. */
 int lh_nhwc_to_nchw_f32(const void* nhwc, float* nchw, int n, int h, int w, int c, int c_stride,

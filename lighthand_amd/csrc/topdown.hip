@@ -1,0 +1,156 @@
+// Top-down inference on full frames: hand box -> crop matrix, crop of a shared uint8 frame buffer to padded NHWC4, keypoints -> next box.
+// Coordinates are pixel indices (pixel centres on the integers, an image spans [-0.5, size-0.5]); a box is (x0, y0, x1, y1) in them.
+// All arithmetic is fp32 in the order written (-ffp-contract=off): lighthand_amd/topdown.py restates it in numpy.
+#include "common.h"
+
+// ------------------------------------------------------------------------------------------------ box -> matrix
+// mat[i] takes a CROP pixel index to a FRAME pixel index: the crop kernel samples through it and lh_affine_points moves the decoded
+// keypoints back to the frame through it -- one matrix per slot, no inverse.  The padded box keeps the crop's aspect ratio.
+__global__ void box_affine_kernel(const float* boxes, const int* frame_index, int b, int n_frames, float h, float w, float padding,
+                                  float* mat, int* src_frame) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b) return;
+    const float x0 = boxes[i * 4], y0 = boxes[i * 4 + 1], x1 = boxes[i * 4 + 2], y1 = boxes[i * 4 + 3];
+    const int fi = frame_index[i];
+    const float bw = x1 - x0, bh = y1 - y0;
+    const bool ok = fi >= 0 && fi < n_frames && isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && bw > 0.f && bh > 0.f;
+    float* m = mat + i * 6;
+    if (!ok) {                                                    // an empty slot: black crop, keypoints at (0, 0)
+        src_frame[i] = -1;
+        m[0] = m[1] = m[2] = m[3] = m[4] = m[5] = 0.f;
+        return;
+    }
+    const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f;
+    const float sw = padding * fmaxf(bw, bh * w / h), sh = sw * h / w, a = sw / w;
+    src_frame[i] = fi;
+    m[0] = a;   m[1] = 0.f; m[2] = (cx - sw * 0.5f) + a * 0.5f;
+    m[3] = 0.f; m[4] = a;   m[5] = (cy - sh * 0.5f) + a * 0.5f;
+}
+
+extern "C" int lh_box_affine(const float* boxes_dev, const int* frame_index_dev, int b, int n_frames, int h, int w, float padding,
+                             float* mat_dev, int* src_frame_dev, void* stream) {
+    LH_REQUIRE(boxes_dev && frame_index_dev && mat_dev && src_frame_dev && b > 0 && n_frames > 0 && h > 0 && w > 0 && padding > 0.f
+               && padding <= 3.0e38f, "lh_box_affine: bad arguments");
+    hipLaunchKernelGGL(box_affine_kernel, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, boxes_dev, frame_index_dev, b, n_frames,
+                       (float)h, (float)w, padding, mat_dev, src_frame_dev);
+    LH_LAUNCH_CHECK("box_affine launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frames -> crops
+// Slot blockIdx.y reads frame src_frame[slot] of a buffer every slot shares: several boxes per frame, frames of any size.  The slot's
+// matrix and frame number are the same for the whole workgroup (scalar loads); one thread per pixel of the padded output, as
+// image_u8_kernel.  A gather over bytes: neighbouring lanes read neighbouring source pixels (a box maps rows to rows), the four taps
+// of a pixel share cache lines with its neighbours', and the frame's reuse across the boxes that read it is the L2's.
+struct CropArgs {
+    const unsigned char* src;
+    void* dst;
+    const float* mat;
+    const int* src_frame;
+    int n_frames, hs, ws, h, w, pad, hp, wp;
+    float mean[3], istd[3];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
+    const int slot = blockIdx.y;
+    const float* m = p.mat + slot * 6;
+    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    const int sf = p.src_frame[slot];
+    const bool live = sf >= 0 && sf < p.n_frames;                 // anything else is an empty slot: never an address
+    const unsigned char* base = p.src + (long)(live ? sf : 0) * p.hs * p.ws * 3;
+    const int per_slot = p.hp * p.wp;
+    T* dst = (T*)p.dst + (long)slot * per_slot * 4;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per_slot; i += gridDim.x * blockDim.x) {
+        const int y = i / p.wp, x = i - y * p.wp;
+        const int oy = y - p.pad, ox = x - p.pad;
+        float v[3] = {0.f, 0.f, 0.f};
+        if ((unsigned)oy < (unsigned)p.h && (unsigned)ox < (unsigned)p.w) {
+            float c[3] = {0.f, 0.f, 0.f};
+            float fx = (m0 * ox + m1 * oy) + m2, fy = (m3 * ox + m4 * oy) + m5;
+            if (live && fx >= -0.5f && fx <= p.ws - 0.5f && fy >= -0.5f && fy <= p.hs - 0.5f) {        // NaN fails the test: black
+                fy = fy < 0.f ? 0.f : fy;
+                fx = fx < 0.f ? 0.f : fx;
+                // f up to size-0.5: the upper clamp only keeps the gather in bounds (x1 == x0 there, the weight does not matter)
+                const int y0 = min((int)fy, p.hs - 1), x0 = min((int)fx, p.ws - 1);
+                const int y1 = y0 + 1 < p.hs ? y0 + 1 : p.hs - 1, x1 = x0 + 1 < p.ws ? x0 + 1 : p.ws - 1;
+                const float wy = fy - y0, wx = fx - x0;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float a00 = base[((long)y0 * p.ws + x0) * 3 + ch], a01 = base[((long)y0 * p.ws + x1) * 3 + ch];
+                    const float a10 = base[((long)y1 * p.ws + x0) * 3 + ch], a11 = base[((long)y1 * p.ws + x1) * 3 + ch];
+                    const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+                    c[ch] = (top + (bot - top) * wy) * (1.f / 255.f);
+                }
+            }
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
+        }
+        if constexpr (sizeof(T) == 2) {                           // one 8-byte store per pixel
+            union { uint2 u; T e[4]; } pk;
+            pk.e[0] = from_f<T>(v[0]); pk.e[1] = from_f<T>(v[1]); pk.e[2] = from_f<T>(v[2]); pk.e[3] = from_f<T>(0.f);
+            *reinterpret_cast<uint2*>(dst + (long)i * 4) = pk.u;
+        } else {
+            T* o = dst + (long)i * 4;
+            o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]); o[3] = from_f<T>(0.f);
+        }
+    }
+}
+
+extern "C" int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
+                                       int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                       int dtype, void* stream) {
+    LH_REQUIRE(frames_u8 && out && mean3 && std3 && mat_dev && src_frame_dev && b > 0 && b <= 65535 && n_frames > 0 && hs > 0 && ws > 0
+               && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "lh_frames_crop_to_nhwc4: bad arguments");
+    LH_REQUIRE(lh_dtype_size(dtype) > 0, "lh_frames_crop_to_nhwc4: unsupported dtype %d", dtype);
+    LH_REQUIRE(((uintptr_t)out & 7) == 0, "lh_frames_crop_to_nhwc4: out must be 8-byte aligned");
+    CropArgs a;
+    a.src = frames_u8; a.dst = out; a.mat = mat_dev; a.src_frame = src_frame_dev;
+    a.n_frames = n_frames; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
+    // one slot's pixels and one frame's bytes are 32-bit quantities; the frame BUFFER is indexed with long (64 frames of 1080p pass 2^31)
+    LH_REQUIRE((long)a.hp * wp < (1L << 29) && (long)hs * ws * 3 < (1L << 31), "lh_frames_crop_to_nhwc4: crop or frame too large for 32-bit pixel indices");
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
+    const int chunks = lh_grid((long)a.hp * wp, 1024);
+    LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((frames_crop_kernel<T>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a));
+    LH_LAUNCH_CHECK("frames_crop_to_nhwc4 launch");
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ keypoints -> next box
+// One thread per slot walks its joints in order: comparisons and a widening about the centre, no atomics, so a replay is bit-reproducible.
+__global__ void keypoints_to_boxes_kernel(const float* preds, const float* maxvals, const float* boxes, const int* src_frame, int b, int j,
+                                          float min_score, int min_joints, float min_side, float* next_boxes, int* lost) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b) return;
+    float lo_x = 0.f, lo_y = 0.f, hi_x = 0.f, hi_y = 0.f;
+    int n = 0;
+    for (int k = 0; k < j; ++k) {
+        if (!(maxvals[(long)i * j + k] >= min_score)) continue;
+        const float x = preds[((long)i * j + k) * 2], y = preds[((long)i * j + k) * 2 + 1];
+        if (n == 0) { lo_x = hi_x = x; lo_y = hi_y = y; }
+        lo_x = x < lo_x ? x : lo_x; hi_x = x > hi_x ? x : hi_x;
+        lo_y = y < lo_y ? y : lo_y; hi_y = y > hi_y ? y : hi_y;
+        ++n;
+    }
+    float* o = next_boxes + i * 4;
+    if (n < min_joints || src_frame[i] < 0) {                     // too few confident joints, or nothing was cropped: keep the box
+        o[0] = boxes[i * 4]; o[1] = boxes[i * 4 + 1]; o[2] = boxes[i * 4 + 2]; o[3] = boxes[i * 4 + 3];
+        lost[i] = 1;
+        return;
+    }
+    if (hi_x - lo_x < min_side) { const float c = (lo_x + hi_x) * 0.5f; lo_x = c - min_side * 0.5f; hi_x = c + min_side * 0.5f; }
+    if (hi_y - lo_y < min_side) { const float c = (lo_y + hi_y) * 0.5f; lo_y = c - min_side * 0.5f; hi_y = c + min_side * 0.5f; }
+    o[0] = lo_x; o[1] = lo_y; o[2] = hi_x; o[3] = hi_y;
+    lost[i] = 0;
+}
+
+extern "C" int lh_keypoints_to_boxes(const float* preds_dev, const float* maxvals_dev, const float* boxes_dev, const int* src_frame_dev, int b,
+                                     int j, float min_score, int min_joints, float min_side, float* next_boxes_dev, int* lost_dev, void* stream) {
+    LH_REQUIRE(preds_dev && maxvals_dev && boxes_dev && src_frame_dev && next_boxes_dev && lost_dev && b > 0 && j > 0 && min_joints >= 1
+               && (long)b * j < (1L << 30) && min_side >= 0.f && min_side <= 3.0e38f && min_score == min_score && next_boxes_dev != boxes_dev,
+               "lh_keypoints_to_boxes: bad arguments");
+    hipLaunchKernelGGL(keypoints_to_boxes_kernel, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, preds_dev, maxvals_dev, boxes_dev,
+                       src_frame_dev, b, j, min_score, min_joints, min_side, next_boxes_dev, lost_dev);
+    LH_LAUNCH_CHECK("keypoints_to_boxes launch");
+    return LH_OK;
+}

@@ -94,6 +94,31 @@ def _check_beta(soft_argmax_beta):
         raise ValueError(f"soft_argmax_beta must be a finite number > 0, not {soft_argmax_beta!r}")
 
 
+def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side):
+    """InferStep / InferPipeline(frames=, box_padding=, track*=): refuse what cannot run, before any device work.  Returns the
+    (n_frames, hs, ws) tuple of ints, or None."""
+    if frames is None:
+        if track:
+            raise ValueError("track=True follows hand boxes on full frames: pass frames=(n_frames, hs, ws)")
+        return None
+    if input_u8:
+        raise ValueError("frames= and input_u8= are two input paths: pass one of them")
+    ok = isinstance(frames, (tuple, list)) and len(frames) == 3 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v > 0
+                                                                        for v in frames)
+    if not ok:
+        raise ValueError(f"frames must be (n_frames, hs, ws), three positive integers, not {frames!r}")
+    if not _is_number(box_padding) or box_padding <= 0:
+        raise ValueError(f"box_padding must be a finite number > 0, not {box_padding!r}")
+    if track:
+        if not _is_number(min_score):
+            raise ValueError(f"track_min_score must be a finite number, not {min_score!r}")
+        if not isinstance(min_joints, numbers.Integral) or isinstance(min_joints, bool) or min_joints < 1:
+            raise ValueError(f"track_min_joints must be an integer >= 1, not {min_joints!r}")
+        if not _is_number(min_side) or min_side < 0:
+            raise ValueError(f"track_min_side must be a finite number >= 0, not {min_side!r}")
+    return tuple(int(v) for v in frames)
+
+
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
@@ -436,14 +461,28 @@ class InferStep:
     the flip test.  ``post_process`` (TEST.POST_PROCESS): ``True`` / ``"quarter"`` adds the quarter-pixel refinement
     (lh_heatmap_refine) to the decode, ``"dark"`` the DARK decode with a blur of ``blur_kernel`` taps (lh_heatmap_dark) in its
     place, ``"soft"`` overwrites ``preds`` with the soft-arg-max under softmax(``soft_argmax_beta`` * heat-map)
-    (lh_heatmap_soft_argmax; ``maxvals`` stays the arg-max's); each reads the merged maps under the flip test."""
+    (lh_heatmap_soft_argmax; ``maxvals`` stays the arg-max's); each reads the merged maps under the flip test.
+
+    Top-down inference on full frames, opt-in (``frames=None``: the step as it was, the same launches and buffers):
+    ``frames=(n_frames, hs, ws)`` makes the static inputs ``frames`` (uint8 [n_frames][hs][ws][3], shared by all slots), ``boxes``
+    (fp32 [batch][4] = x0 y0 x1 y1 in frame pixel-index coordinates) and ``frame_index`` (int32 [batch]); the graph turns every box,
+    padded by ``box_padding`` at the crop's aspect ratio, into a matrix (lh_box_affine), crops the frames through it
+    (lh_frames_crop_to_nhwc4) and, after the decode -- flip-test merge and ``post_process`` included -- takes the keypoints back to
+    the frame through the same matrix (lh_affine_points): ``preds`` are then FRAME coordinates, ``crop_preds`` keeps the crop's,
+    ``valid`` is ``src_frame >= 0`` (a slot whose box is degenerate / not finite or whose frame index is out of range is empty:
+    a black crop, preds (0, 0)).  ``track=True`` ends the graph with lh_keypoints_to_boxes: ``next_boxes`` = the bounds of the joints
+    with maxval >= ``track_min_score``, at least ``track_min_side`` wide, and ``lost`` = 1 where fewer than ``track_min_joints``
+    joints qualify (``next_boxes`` then repeats the box); ``advance()`` copies ``next_boxes`` into ``boxes`` on the device, so frame
+    t+1 is replayed with no host arithmetic.  The graph never writes ``boxes``: the box behind ``preds`` stays readable."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
-                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0):
+                 flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
+                 frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
+        frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
         self.soft_argmax_beta = float(soft_argmax_beta)
@@ -452,11 +491,22 @@ class InferStep:
         # slot replays asynchronously on its own stream -- neither may happen to the plan model.forward() uses
         InferStep._serial += 1
         self.plan = model.plan(batch, height, width, training=bn_train, backward=False, slot=slot,
-                               owner=("infer", "u8" if input_u8 else "f32", InferStep._serial), options=plan_options)
+                               owner=("infer", "frames" if frames else "u8" if input_u8 else "f32", InferStep._serial), options=plan_options)
         out = self.plan.out_nchw
         dev = out.device
         # input_u8=(hs, ws): raw uint8 HWC frames; ToTensor / Resize / Normalize run fused on the device (dataset.py:128-159)
         self.images = self.plan.use_uint8_input(*input_u8) if input_u8 else self.plan.img_nchw
+        self.frames = self.boxes = self.frame_index = self.crop_preds = self.next_boxes = self.lost = None
+        self.track = bool(track) and frames is not None
+        self.track_min_score, self.track_min_joints, self.track_min_side = float(track_min_score), int(track_min_joints), float(track_min_side)
+        if frames:
+            self.images = None                                      # the inputs of such a step are frames / boxes / frame_index
+            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding))
+            self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
+            self.crop_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
+            if self.track:
+                self.next_boxes = self.boxes.clone()
+                self.lost = torch.ones(batch, dtype=torch.int32, device=dev)
         self.flip_test, self.shift_heatmap, self.post_process, self.blur_kernel = flip_test, shift_heatmap, post_process, int(blur_kernel)
         # flip test: the plain pass's maps are copied here, and the merge writes over them in place
         self.heatmaps = torch.zeros_like(out) if flip_test else out
@@ -473,32 +523,63 @@ class InferStep:
         self.plan.run_forward(s)
         out, hm = self.plan.out_nchw, self.heatmaps
         bj, h, w = out.shape[0] * out.shape[1], out.shape[2], out.shape[3]
+        preds = self.preds if self.frames is None else self.crop_preds      # the decode works in crop coordinates
         if self.flip_test:
             hm.copy_(out)
             self.plan.run_forward(s, mirrored=True)
             check(self.lib.lh_heatmap_flip_merge(hm.data_ptr(), out.data_ptr(), bj, h, w, int(self.shift_heatmap), self.scale,
-                                                 hm.data_ptr(), self.preds.data_ptr(), self.maxvals.data_ptr(), _ptr(self.idx), s),
+                                                 hm.data_ptr(), preds.data_ptr(), self.maxvals.data_ptr(), _ptr(self.idx), s),
                   "lh_heatmap_flip_merge")
         else:
-            check(self.lib.lh_heatmap_argmax(hm.data_ptr(), bj, h, w, self.scale, self.preds.data_ptr(), self.maxvals.data_ptr(),
+            check(self.lib.lh_heatmap_argmax(hm.data_ptr(), bj, h, w, self.scale, preds.data_ptr(), self.maxvals.data_ptr(),
                                              _ptr(self.idx), s), "lh_heatmap_argmax")
         if self.post_process == "quarter":
             check(self.lib.lh_heatmap_refine(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.scale,
-                                             self.preds.data_ptr(), s), "lh_heatmap_refine")
+                                             preds.data_ptr(), s), "lh_heatmap_refine")
         elif self.post_process == "dark":
             check(self.lib.lh_heatmap_dark(hm.data_ptr(), self.idx.data_ptr(), self.maxvals.data_ptr(), bj, h, w, self.blur_kernel,
-                                           self.scale, self.preds.data_ptr(), s), "lh_heatmap_dark")
+                                           self.scale, preds.data_ptr(), s), "lh_heatmap_dark")
         elif self.post_process == "soft":
-            check(self.lib.lh_heatmap_soft_argmax(hm.data_ptr(), bj, h, w, self.soft_argmax_beta, self.scale, self.preds.data_ptr(), s),
+            check(self.lib.lh_heatmap_soft_argmax(hm.data_ptr(), bj, h, w, self.soft_argmax_beta, self.scale, preds.data_ptr(), s),
                   "lh_heatmap_soft_argmax")
+        if self.frames is not None:
+            p = self.plan
+            check(self.lib.lh_affine_points(preds.data_ptr(), 2, p.crop_mat.data_ptr(), self.preds.data_ptr(), 2, out.shape[0], out.shape[1], s),
+                  "lh_affine_points")
+            if self.track:
+                check(self.lib.lh_keypoints_to_boxes(self.preds.data_ptr(), self.maxvals.data_ptr(), self.boxes.data_ptr(), p.src_frame.data_ptr(),
+                                                     out.shape[0], out.shape[1], self.track_min_score, self.track_min_joints,
+                                                     self.track_min_side, self.next_boxes.data_ptr(), self.lost.data_ptr(), s),
+                      "lh_keypoints_to_boxes")
+
+    @property
+    def valid(self):
+        """bool [batch]: the slots whose box and frame index were usable in the last run (None without ``frames``)."""
+        return None if self.frames is None else self.plan.src_frame >= 0
+
+    def advance(self):
+        """boxes <- next_boxes, on the device (``track=True``): the next call crops where this one found the hand.  On a step built without
+        ``track`` it raises LightHandError (a call the step cannot serve, as a stale ticket of InferPipeline.result; the ValueErrors
+        are for bad argument values)."""
+        if not self.track:
+            raise LightHandError("advance() needs InferStep(frames=..., track=True)")
+        self.boxes.copy_(self.next_boxes, non_blocking=True)
 
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
         self._packed = True
 
-    def __call__(self, images=None):
+    def __call__(self, images=None, frames=None, boxes=None, frame_index=None):
+        if self.frames is None:
+            if frames is not None or boxes is not None or frame_index is not None:
+                raise ValueError("frames / boxes / frame_index are the inputs of InferStep(frames=(n_frames, hs, ws))")
+        elif images is not None:
+            raise ValueError("a step built with frames= takes frames / boxes / frame_index, not images")
         if images is not None:
             self.images.copy_(images, non_blocking=True)
+        for dst, src in ((self.frames, frames), (self.boxes, boxes), (self.frame_index, frame_index)):
+            if src is not None:
+                dst.copy_(src, non_blocking=True)
         if not self._packed:
             self.refresh_weights()
         if not self.use_graph:
@@ -524,6 +605,8 @@ class InferPipeline:
     fills the machine under them: R50 256x256 bs 64 bf16, 29.9 k img/s with one batch in flight, 33.3 k with two (MI355X).
     Eval-mode only (the batch-statistics quirk of ``pred_store`` updates the running statistics, which slots would race on).
     ``flip_test`` / ``shift_heatmap`` / ``post_process`` / ``blur_kernel`` / ``soft_argmax_beta``: as InferStep's, for every slot.
+    ``frames`` / ``box_padding`` / ``track`` / ``track_min_*``: as InferStep's; every slot owns its frame buffer and boxes, and
+    ``submit(frames=, boxes=, frame_index=)`` fills them (``steps[i]`` gives a slot's ``valid`` / ``next_boxes`` / ``lost``).
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -531,12 +614,16 @@ class InferPipeline:
     """
 
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
-                 blur_kernel=11, soft_argmax_beta=100.0):
+                 blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
+                 track_min_joints=8, track_min_side=16.0):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side)
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
                                 shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
-                                soft_argmax_beta=soft_argmax_beta) for i in range(depth)]
+                                soft_argmax_beta=soft_argmax_beta, frames=frames, box_padding=box_padding, track=track,
+                                track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side)
+                      for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
         self.count = 0
@@ -546,16 +633,17 @@ class InferPipeline:
         for s in self.steps:
             s._packed = False
 
-    def submit(self, images=None):
+    def submit(self, images=None, frames=None, boxes=None, frame_index=None):
         i = self.count % len(self.steps)
         st = self.streams[i]
         st.wait_stream(torch.cuda.current_stream())          # the caller's copy of `images` into place is ordered before
-        if images is not None and images.is_cuda:
-            # the slot's copy of `images` runs on `st`: tell the caching allocator, or a caller that drops the batch right
-            # after submit() gets the same block back for the next batch while this copy is still queued
-            images.record_stream(st)
+        for t in (images, frames, boxes, frame_index):
+            if t is not None and t.is_cuda:
+                # the slot's copy of an input runs on `st`: tell the caching allocator, or a caller that drops the batch right
+                # after submit() gets the same block back for the next batch while this copy is still queued
+                t.record_stream(st)
         with torch.cuda.stream(st):
-            self.steps[i](images)
+            self.steps[i](images, frames, boxes, frame_index)
             self.events[i] = st.record_event()
         self.count += 1
         return self.count - 1
@@ -568,10 +656,11 @@ class InferPipeline:
         return self.steps[i].preds, self.steps[i].maxvals
 
     def map(self, batches):
-        """Yields (preds, maxvals) clones for every batch of the iterable, in order, keeping `depth` batches in flight."""
+        """Yields (preds, maxvals) clones for every batch of the iterable, in order, keeping `depth` batches in flight.  A batch is
+        an image tensor, or a dict of submit()'s keyword arguments (frames / boxes / frame_index)."""
         pending = []
         for images in batches:
-            pending.append(self.submit(images))
+            pending.append(self.submit(**images) if isinstance(images, dict) else self.submit(images))
             if len(pending) == len(self.steps):
                 p, m = self.result(pending.pop(0))
                 yield p.clone(), m.clone()

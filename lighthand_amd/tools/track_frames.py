@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Top-down inference on full camera frames, closed loop: every frame is cropped at the hand boxes ON THE DEVICE, the keypoints are
+decoded and taken back to frame coordinates, and the next frame's boxes are the bounds of this frame's keypoints -- one replay of a
+captured graph plus one device-to-device copy per frame, no host arithmetic in between (runtime.InferStep(frames=..., track=True)).
+
+    track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
+
+``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
+(camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
+``step.boxes`` once, then calls ``step()`` / ``step.advance()`` per frame).  Prints ONE JSON line: frames per second, the number of
+(frame, hand) slots that were lost (too few confident joints: the box is kept), and the options.  The weights
+are seeded random ones, so the keypoints mean nothing and their confidences are far below InferStep's default ``track_min_score``:
+the tool sets the threshold to the median confidence of the first frame (a replay of a probe step), so about half of the joints count,
+the boxes move from frame to frame and some slots are lost -- the loop runs as it would with a trained model."""
+import argparse
+import json
+import time
+
+import numpy as np
+
+
+def _frame_size(text):
+    parts = text.lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() and int(p) > 0 for p in parts):
+        raise argparse.ArgumentTypeError(f"--frame_size wants HSxWS (e.g. 1080x1920), not {text!r}")
+    return int(parts[0]), int(parts[1])
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--synthetic", default=0, type=int, help="number of seeded synthetic frames to render and track")
+    ap.add_argument("--frame_size", default=(1080, 1920), type=_frame_size, help="HSxWS of the camera frames")
+    ap.add_argument("--hands", default=2, type=int, help="hand boxes per frame (slots of the captured step)")
+    ap.add_argument("--depth", default=50, type=int)
+    ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--size", default=256, type=int, help="side of the square crop the model reads")
+    ap.add_argument("--flip_test", action="store_true", help="average with the flipped-back heat-maps of the mirrored crop")
+    ap.add_argument("--dark_decode", action="store_true", help="DARK decode in place of the plain arg-max")
+    ap.add_argument("--seed", default=0, type=int)
+    return ap
+
+
+def synthetic_sequence(n, hs, ws, hands, seed=0):
+    """n frames uint8 [n][hs][ws][3] and the first frame's hand boxes fp32 [hands][4] (pixel-index coordinates, the bounds of each
+    hand's 21 joints).  Every hand is a fixed constellation of 21 discs, about a fifth of the frame's short side across, whose
+    centre drifts on a seeded smooth path that stays inside the frame."""
+    rng = np.random.RandomState(seed)
+    span = max(8.0, min(hs, ws) / 5.0)
+    frames = rng.randint(0, 32, size=(n, hs, ws, 3)).astype(np.uint8)
+    shape = rng.uniform(-0.5, 0.5, size=(hands, 21, 2)) * span
+    start = np.stack([rng.uniform(span, ws - span, size=hands), rng.uniform(span, hs - span, size=hands)], 1)
+    phase, speed = rng.uniform(0, 2 * np.pi, size=(hands, 2)), rng.uniform(0.02, 0.08, size=(hands, 2))
+    r = max(2, int(span / 16))
+    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+    disc = (255 * np.clip(1.25 - np.hypot(xx, yy) / r, 0, 1)).astype(np.uint8)
+    boxes = np.zeros((hands, 4), np.float32)
+    for t in range(n):
+        drift = 0.5 * span * np.sin(phase + speed * t) - 0.5 * span * np.sin(phase)
+        joints = shape + np.clip(start + drift, [span, span], [ws - span, hs - span])[:, None, :]
+        if t == 0:
+            boxes[:, :2], boxes[:, 2:] = joints.min(1), joints.max(1)
+        for x, y in np.rint(joints.reshape(-1, 2)).astype(int):
+            y0, y1, x0, x1 = max(y - r, 0), min(y + r + 1, hs), max(x - r, 0), min(x + r + 1, ws)
+            if y0 < y1 and x0 < x1:
+                patch = disc[y0 - (y - r):y1 - (y - r), x0 - (x - r):x1 - (x - r), None]
+                frames[t, y0:y1, x0:x1] = np.maximum(frames[t, y0:y1, x0:x1], patch)
+    return frames, boxes
+
+
+def main(argv=None):
+    import torch
+
+    from lighthand_amd.runtime import InferStep
+    from lighthand_amd.modeling.simplebaseline.config import default_config
+    from lighthand_amd.modeling.simplebaseline.pose_resnet import get_pose_net
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.synthetic < 1:
+        raise SystemExit("camera footage is not shipped: pass --synthetic N")
+    if args.hands < 1:
+        ap.error("--hands must be >= 1")
+    hs, ws = args.frame_size
+    frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed)
+    torch.manual_seed(args.seed)
+    model = get_pose_net(default_config(args.depth), is_train=True).cuda().set_precision(args.precision)
+    model.eval()
+    options = dict(frames=(1, hs, ws), flip_test=args.flip_test, post_process="dark" if args.dark_decode else False)
+    seq = torch.from_numpy(frames).pin_memory()
+    probe = InferStep(model, args.hands, args.size, args.size, **options)
+    probe(frames=seq[:1], boxes=torch.from_numpy(boxes))
+    score = float(probe.maxvals.median())                          # random weights: see the module docstring
+    del probe
+    step = InferStep(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
+    step.boxes.copy_(torch.from_numpy(boxes))
+    lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
+    step(frames=seq[:1])                                           # capture; the loop below starts from the first frame's boxes again
+    step.boxes.copy_(torch.from_numpy(boxes))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for t in range(args.synthetic):
+        step(frames=seq[t:t + 1])
+        lost += step.lost
+        step.advance()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    result = {"frames_per_s": round(args.synthetic / dt, 2), "frames": args.synthetic, "slots": args.synthetic * args.hands,
+              "slots_lost": int(lost.sum()), "frame_size": [hs, ws], "hands": args.hands, "depth": args.depth,
+              "precision": args.precision, "size": args.size, "track_min_score": score, "flip_test": args.flip_test, "dark_decode": args.dark_decode, "seed": args.seed}
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()

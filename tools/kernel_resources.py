@@ -2,8 +2,13 @@
 """Scratch memory and spilled registers of every kernel in the built library, read from the metadata notes of its gfx950 code objects.
 
 usage: tools/kernel_resources.py [--write] [filter]
-  prints  <scratch bytes> <spilled VGPRs> <kernel symbol>  per kernel; --write regenerates tests/golden/kernel_resources.json
+  prints  <scratch bytes> <spilled VGPRs> <kernel symbol>  per kernel; --write regenerates tests/golden/kernel_ceilings.json
   (the ceilings tests/test_kernel_resources.py holds every kernel to) from the library as built.
+
+Two tables: tests/golden/kernel_resources.json is the first table, frozen as committed (a change that adds kernels adds test files and
+leaves the existing ones alone); kernel_ceilings.json is the table in force.  It may only extend the frozen one -- every entry of
+kernel_resources.json is in it with figures no higher (tests/test_kernel_ceilings.py) -- so a kernel can gain an entry or earn a lower
+one, never a higher one.
 
 The library carries one clang offload bundle per translation unit in its .hip_fatbin section; each bundle holds the gfx950 code object
 whose NT_AMDGPU_METADATA note lists .private_segment_fixed_size and .vgpr_spill_count per kernel (llvm-readelf --notes prints it)."""
@@ -18,7 +23,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "lighthand_amd", "liblighthand_hip.so")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
+FROZEN = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_ceilings.json")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 

@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""What top-down inference on full frames costs per captured inference step (README): InferStep(input_u8=(256, 256)) --
+the crops already exist -- against InferStep(frames=(32, 1080, 1920)) with two hand boxes per frame and against the same with
+track=True, alternated in ONE process on R50 64 x 256^2 bf16.  The frame legs add lh_box_affine, lh_affine_points [and
+lh_keypoints_to_boxes] and swap the uint8 input kernel for lh_frames_crop_to_nhwc4, which writes the same bytes but gathers them from
+199 MB of frames.  Device events around `steps` replays, after a warm-up; median over the rounds.
+usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from lighthand_amd.runtime import InferStep  # noqa: E402
+
+
+def timed(step, n):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        step()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def main():
+    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    batch, size, n_frames, hs, ws = 64, 256, 32, 1080, 1920
+    rng = np.random.RandomState(0)
+    model = bench.build_model(depth=50, precision="bf16").eval()
+    crops = torch.from_numpy(rng.randint(0, 256, size=(batch, size, size, 3)).astype(np.uint8)).cuda()
+    frames = torch.from_numpy(rng.randint(0, 256, size=(n_frames, hs, ws, 3)).astype(np.uint8)).cuda()
+    # two hands per frame: boxes of 150..500 px around centres inside the frame (a hand at arm's length to close to the camera)
+    centre = np.stack([rng.uniform(200, ws - 200, size=batch), rng.uniform(200, hs - 200, size=batch)], 1)
+    half = rng.uniform(75, 250, size=(batch, 1))
+    boxes = torch.from_numpy(np.concatenate([centre - half, centre + half], 1).astype(np.float32)).cuda()
+    index = (torch.arange(batch, dtype=torch.int32) // 2).cuda()
+
+    forms = {"uint8 crops": InferStep(model, batch, size, size, input_u8=(size, size)),
+             "frames": InferStep(model, batch, size, size, frames=(n_frames, hs, ws)),
+             "frames+track": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True)}
+    forms["uint8 crops"](crops)
+    for tag in ("frames", "frames+track"):
+        forms[tag](frames=frames, boxes=boxes, frame_index=index)
+    for step in forms.values():
+        timed(step, 10)                                                   # warm-up (capture happened in the first call)
+    ms = {tag: [] for tag in forms}
+    for _ in range(rounds):
+        for tag, step in forms.items():
+            ms[tag].append(timed(step, steps))
+    med = {tag: statistics.median(v) for tag, v in ms.items()}
+    print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
+    for tag, v in ms.items():
+        print(f"  {tag:14s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops; rounds: "
+              f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
+
+
+if __name__ == "__main__":
+    main()
