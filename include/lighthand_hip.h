@@ -105,6 +105,35 @@ int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, in
  * atomics: bit-reproducible.  next_boxes_dev must not be boxes_dev. */
 int lh_keypoints_to_boxes(const float* preds_dev, const float* maxvals_dev, const float* boxes_dev, const int* src_frame_dev, int b,
                           int j, float min_score, int min_joints, float min_side, float* next_boxes_dev, int* lost_dev, void* stream);
+/* Oriented, mirrored ROIs (opt-in siblings of the two entries above; the crop kernel and lh_affine_points take the matrix as it is).
+ * lh_roi_affine: as lh_box_affine, plus rot_dev fp32 [b][2] = (rx, ry), the frame direction of the crop's +x axis (any length,
+ * (1, 0) = upright) and mirror_dev int32 [b] (non-zero: the crop's x axis is flipped, a left hand reaches the network as a right
+ * one).  The box gives the ROI's centre and its extents along the ROI's own axes (the box before it is turned about its centre).
+ * bw, bh, cx, cy, sw, a as lh_box_affine's; n = sqrtf(rx*rx + ry*ry), c = rx/n, s = ry/n, ac = a*c, as = a*s, g = mirror ? -1 : 1,
+ * m0 = g*ac, m1 = -as, m3 = g*as, m4 = ac, hx = (w-1)*0.5, hy = (h-1)*0.5, m2 = cx - (m0*hx + m1*hy), m5 = cy - (m3*hx + m4*hy).
+ * Empty slots as lh_box_affine's, and also when rot is not finite or n is not > 0. */
+int lh_roi_affine(const float* boxes_dev, const float* rot_dev, const int* mirror_dev, const int* frame_index_dev, int b, int n_frames,
+                  int h, int w, float padding, float* mat_dev, int* src_frame_dev, void* stream);
+/* The oriented sibling of lh_keypoints_to_boxes: next_boxes_dev fp32 [b][4], next_rot_dev fp32 [b][2], lost_dev int32 [b].  With
+ * both anchor joints confident (maxval >= min_score) and d = sqrtf(dx*dx + dy*dy) >= min_axis, (dx, dy) = p[axis_to] - p[axis_from]:
+ * (c, s) = next_rot = (-(dy/d), dx/d), so that the crop's -y axis points from axis_from to axis_to (mirrored or not); otherwise
+ * (c, s) = rot / its norm.  Every confident joint is projected, p = x*c + y*s, q = y*c - x*s; their bounds, each widened about its
+ * centre to at least min_side, give the centre (cp, cq) and half extents (hp, hq); the centre returns to the frame as
+ * (cp*c - cq*s, cp*s + cq*c) and next_boxes = centre -+ half extents.  With fewer than min_joints confident joints, for an empty
+ * slot (src_frame < 0) or when (c, s) is not finite, next_boxes = boxes, next_rot = rot and lost = 1.  One thread per slot, no
+ * atomics.  min_axis > 0, axis_from != axis_to, both in 0..j-1; the outputs must not be boxes_dev / rot_dev. */
+int lh_keypoints_to_rois(const float* preds_dev, const float* maxvals_dev, const float* boxes_dev, const float* rot_dev,
+                         const int* src_frame_dev, int b, int j, int axis_from, int axis_to, float min_score, int min_joints,
+                         float min_side, float min_axis, float* next_boxes_dev, float* next_rot_dev, int* lost_dev, void* stream);
+/* One-Euro filter (Casiez et al. 2012) of x_dev fp32 [b][j][2] into out_dev, one launch per frame; state xhat_dev, dxhat_dev fp32
+ * [b][j][2] and init_dev int32 [b]; dt_dev fp32 [b] in seconds; lost_dev int32 [b] may be NULL.  alpha(fc) = r / (r + 1) with
+ * r = (6.2831855f * fc) * dt.  init[slot] = 1: dx = (x - xhat) / dt, ad = alpha(d_cutoff), dxhat = ad*dx + (1-ad)*dxhat,
+ * fc = min_cutoff + beta*fabsf(dxhat), al = alpha(fc), xhat = al*x + (1-al)*xhat, out = xhat.  init[slot] = 0, or dt not finite or
+ * not > 0: xhat = x, dxhat = 0, out = x.  init becomes 1.  A slot with src_frame < 0 or lost != 0 passes x through, keeps its state
+ * and ends with init = 0.  One workgroup per slot; init is written behind a barrier.  min_cutoff, d_cutoff > 0, beta >= 0 (it
+ * multiplies |dxhat|, units of x per second). */
+int lh_one_euro(const float* x_dev, const int* src_frame_dev, const int* lost_dev, const float* dt_dev, int b, int j, float min_cutoff,
+                float beta, float d_cutoff, float* xhat_dev, float* dxhat_dev, int* init_dev, float* out_dev, void* stream);
 /* NHWC (run dtype) -> NCHW fp32 heatmaps (what model(images) returns, pose_resnet.py:246)
  * and the inverse for the incoming gradient. c_stride = channel stride of the NHWC side. */
 int lh_nhwc_to_nchw_f32(const void* nhwc, float* nchw, int n, int h, int w, int c, int c_stride,

@@ -117,6 +117,9 @@ SIGNATURES = {
     "lh_box_affine": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
     "lh_frames_crop_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _I, _P]),
     "lh_keypoints_to_boxes": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _F, _P, _P, _P]),
+    "lh_roi_affine": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "lh_keypoints_to_rois": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P]),
+    "lh_one_euro": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "lh_nhwc_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lh_nchw_f32_to_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lh_pack_weight": (_I, [_P, _P, C.POINTER(_SZ), _I, _I, _L, _L, _L, _L, _I, C.POINTER(_I), _I, _P]),

@@ -946,14 +946,16 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             m3, s3) + extra + (self.dt,), what + (" + ColorJitter" if jitter else ""))
         return self.img_u8
 
-    def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
         all read at every launch (replay), and the image launch becomes two: lh_box_affine writes ``crop_mat`` (fp32 [n][6], crop
         pixel index -> frame pixel index of the box padded by ``padding`` at the crop's aspect ratio) and ``src_frame`` (int32 [n],
         -1 = empty slot), lh_frames_crop_to_nhwc4 samples the frames through them, normalises and writes the stem's padded NHWC4
-        input.  run_forward(mirrored=True) still replaces only the launch that writes img_nhwc4.  Returns the frame buffer."""
+        input.  run_forward(mirrored=True) still replaces only the launch that writes img_nhwc4.  ``oriented=True``: the plan also
+        owns ``rot`` (fp32 [n][2], the frame direction of each crop's +x axis, (1, 0) = upright until the caller writes it) and
+        ``mirror`` (int32 [n], 0), and lh_roi_affine writes ``crop_mat`` in lh_box_affine's place.  Returns the frame buffer."""
         self.frames_u8 = self._alloc(n_frames, hs, ws, 3, dtype=torch.uint8, zero=True)
         self.boxes = self._alloc(self.n, 4, dtype=torch.float32)
         self.boxes.copy_(torch.tensor([-0.5, -0.5, ws - 0.5, hs - 0.5], dtype=torch.float32, device=self.device).expand(self.n, 4))
@@ -969,9 +971,18 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         self.fwd[i] = _Call(self.lib.lh_frames_crop_to_nhwc4, (
             self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3, s3,
             self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt), "frame crop input pipeline")
-        self.fwd.insert(i, _Call(self.lib.lh_box_affine, (
-            self.boxes.data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h, self.w, float(padding),
-            self.crop_mat.data_ptr(), self.src_frame.data_ptr()), "hand box -> crop matrix"))
+        self.rot = self.mirror = None
+        if oriented:
+            self.rot = self._alloc(self.n, 2, dtype=torch.float32)
+            self.rot.copy_(torch.tensor([1.0, 0.0], dtype=torch.float32, device=self.device).expand(self.n, 2))
+            self.mirror = self._alloc(self.n, dtype=torch.int32, zero=True)
+            self.fwd.insert(i, _Call(self.lib.lh_roi_affine, (
+                self.boxes.data_ptr(), self.rot.data_ptr(), self.mirror.data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h,
+                self.w, float(padding), self.crop_mat.data_ptr(), self.src_frame.data_ptr()), "oriented hand ROI -> crop matrix"))
+        else:
+            self.fwd.insert(i, _Call(self.lib.lh_box_affine, (
+                self.boxes.data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h, self.w, float(padding),
+                self.crop_mat.data_ptr(), self.src_frame.data_ptr()), "hand box -> crop matrix"))
         self.fwd[i].slane = self.fwd[i + 1].slane = slane
         self._image_call_index = i + 1                            # the launch that writes img_nhwc4 (what the flip test's mirror replaces)
         return self.frames_u8

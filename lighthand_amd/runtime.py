@@ -119,6 +119,35 @@ def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, m
     return tuple(int(v) for v in frames)
 
 
+def _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth):
+    """InferStep / InferPipeline(oriented=, track_axis=, track_min_axis=, smooth=): refuse what cannot run, before any device work.
+    The joint count is the model's ``final_layer.out_channels`` (both model families end in that convolution); a model without one
+    leaves the upper range of ``track_axis`` to lh_keypoints_to_rois' own argument check.  Returns smooth as (min_cutoff, beta,
+    d_cutoff) floats, or None."""
+    if oriented and frames is None:
+        raise ValueError("oriented=True turns hand ROIs on full frames: pass frames=(n_frames, hs, ws)")
+    if smooth is not None and frames is None:
+        raise ValueError("smooth= filters keypoints in frame coordinates: pass frames=(n_frames, hs, ws)")
+    if oriented:
+        ok = isinstance(track_axis, (tuple, list)) and len(track_axis) == 2 and all(
+            isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 0 for v in track_axis) and track_axis[0] != track_axis[1]
+        if not ok:
+            raise ValueError(f"track_axis must be two different joint numbers (from, to), not {track_axis!r}")
+        joints = getattr(getattr(model, "final_layer", None), "out_channels", None)
+        if isinstance(joints, numbers.Integral) and max(track_axis) >= joints:
+            raise ValueError(f"track_axis {tuple(track_axis)!r} names a joint the model does not have ({joints} joints)")
+        if not _is_number(track_min_axis) or track_min_axis <= 0:
+            raise ValueError(f"track_min_axis must be a finite number > 0, not {track_min_axis!r}")
+    if smooth is None:
+        return None
+    if not isinstance(smooth, (tuple, list)) or len(smooth) not in (2, 3) or not all(_is_number(v) for v in smooth):
+        raise ValueError(f"smooth must be (min_cutoff, beta) or (min_cutoff, beta, d_cutoff), finite numbers, not {smooth!r}")
+    min_cutoff, beta, d_cutoff = (tuple(smooth) + (1.0,))[:3]
+    if min_cutoff <= 0 or d_cutoff <= 0 or beta < 0:
+        raise ValueError(f"smooth wants cut-offs > 0 and beta >= 0, not {smooth!r}")
+    return float(min_cutoff), float(beta), float(d_cutoff)
+
+
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
@@ -473,16 +502,35 @@ class InferStep:
     a black crop, preds (0, 0)).  ``track=True`` ends the graph with lh_keypoints_to_boxes: ``next_boxes`` = the bounds of the joints
     with maxval >= ``track_min_score``, at least ``track_min_side`` wide, and ``lost`` = 1 where fewer than ``track_min_joints``
     joints qualify (``next_boxes`` then repeats the box); ``advance()`` copies ``next_boxes`` into ``boxes`` on the device, so frame
-    t+1 is replayed with no host arithmetic.  The graph never writes ``boxes``: the box behind ``preds`` stays readable."""
+    t+1 is replayed with no host arithmetic.  The graph never writes ``boxes``: the box behind ``preds`` stays readable.
+
+    Oriented, mirrored ROIs and a temporal filter, opt-in on top of ``frames=`` (both off: the launches above, nothing else):
+    ``oriented=True`` adds the static inputs ``rot`` (fp32 [batch][2], the frame direction of each crop's +x axis, any length,
+    (1, 0) = upright; topdown.rot_from_angle) and ``mirror`` (int32 [batch], non-zero = a left hand: the crop's x axis is flipped),
+    filled through ``rot=`` / ``mirror=``; a box is then the ROI's centre and its extents along the ROI's own axes, and lh_roi_affine
+    writes the matrix in lh_box_affine's place.  The decode stays in crop coordinates and lh_affine_points maps back through the same
+    matrix, mirror included, so ``flip_test`` and every ``post_process`` compose.  With ``track=True`` the graph ends with
+    lh_keypoints_to_rois in lh_keypoints_to_boxes' place: ``next_rot`` turns the next crop so that joint ``track_axis[0]`` ->
+    ``track_axis[1]`` (wrist -> middle-finger MCP) points up, when both are confident and at least ``track_min_axis`` frame pixels
+    apart (otherwise the orientation is kept), ``next_boxes`` bounds the confident joints along that direction, and ``advance()``
+    copies both.  ``mirror`` is the caller's: the graph never writes it.
+    ``smooth=(min_cutoff, beta)`` or ``(min_cutoff, beta, d_cutoff=1.0)`` makes lh_one_euro the last launch: ``smooth_preds`` is the
+    One-Euro filter of ``preds`` (frame pixels; ``beta`` multiplies a speed in frame pixels per second), ``preds`` stays raw and the next ROI is computed
+    from the raw keypoints (a filtered ROI lags).  ``dt`` (fp32 [batch], seconds since the slot's previous frame, 1/30 until
+    written; ``dt=`` takes a tensor or one number) is an input.  One call is one frame.  A slot that is empty, or lost under
+    ``track=True``, passes its keypoints through and starts fresh when it is found again; ``reset_filter(slots=None)`` does the same
+    by hand (a scene cut, a new hand in the slot)."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
-                 frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0):
+                 frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0,
+                 oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
         frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side)
+        smooth = _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
         self.soft_argmax_beta = float(soft_argmax_beta)
@@ -499,14 +547,27 @@ class InferStep:
         self.frames = self.boxes = self.frame_index = self.crop_preds = self.next_boxes = self.lost = None
         self.track = bool(track) and frames is not None
         self.track_min_score, self.track_min_joints, self.track_min_side = float(track_min_score), int(track_min_joints), float(track_min_side)
+        self.oriented, self.smooth = bool(oriented) and frames is not None, smooth
+        self.rot = self.mirror = self.next_rot = self.dt = self.smooth_preds = None
+        if self.oriented:
+            self.track_axis, self.track_min_axis = (int(track_axis[0]), int(track_axis[1])), float(track_min_axis)
         if frames:
             self.images = None                                      # the inputs of such a step are frames / boxes / frame_index
-            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding))
+            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented)
             self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
+            self.rot, self.mirror = self.plan.rot, self.plan.mirror
             self.crop_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
             if self.track:
                 self.next_boxes = self.boxes.clone()
                 self.lost = torch.ones(batch, dtype=torch.int32, device=dev)
+                if self.oriented:
+                    self.next_rot = self.rot.clone()
+            if smooth:
+                self.dt = torch.full((batch,), 1.0 / 30.0, dtype=torch.float32, device=dev)
+                self.smooth_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
+                # the filter's state: the last filtered keypoints, their filtered derivative, and whether the slot has seen a frame
+                self._xhat, self._dxhat = torch.zeros_like(self.smooth_preds), torch.zeros_like(self.smooth_preds)
+                self._seen = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.flip_test, self.shift_heatmap, self.post_process, self.blur_kernel = flip_test, shift_heatmap, post_process, int(blur_kernel)
         # flip test: the plain pass's maps are copied here, and the merge writes over them in place
         self.heatmaps = torch.zeros_like(out) if flip_test else out
@@ -546,11 +607,21 @@ class InferStep:
             p = self.plan
             check(self.lib.lh_affine_points(preds.data_ptr(), 2, p.crop_mat.data_ptr(), self.preds.data_ptr(), 2, out.shape[0], out.shape[1], s),
                   "lh_affine_points")
-            if self.track:
+            if self.track and self.oriented:
+                check(self.lib.lh_keypoints_to_rois(self.preds.data_ptr(), self.maxvals.data_ptr(), self.boxes.data_ptr(), self.rot.data_ptr(),
+                                                    p.src_frame.data_ptr(), out.shape[0], out.shape[1], self.track_axis[0], self.track_axis[1],
+                                                    self.track_min_score, self.track_min_joints, self.track_min_side, self.track_min_axis,
+                                                    self.next_boxes.data_ptr(), self.next_rot.data_ptr(), self.lost.data_ptr(), s),
+                      "lh_keypoints_to_rois")
+            elif self.track:
                 check(self.lib.lh_keypoints_to_boxes(self.preds.data_ptr(), self.maxvals.data_ptr(), self.boxes.data_ptr(), p.src_frame.data_ptr(),
                                                      out.shape[0], out.shape[1], self.track_min_score, self.track_min_joints,
                                                      self.track_min_side, self.next_boxes.data_ptr(), self.lost.data_ptr(), s),
                       "lh_keypoints_to_boxes")
+            if self.smooth:
+                check(self.lib.lh_one_euro(self.preds.data_ptr(), p.src_frame.data_ptr(), _ptr(self.lost), self.dt.data_ptr(), out.shape[0],
+                                           out.shape[1], self.smooth[0], self.smooth[1], self.smooth[2], self._xhat.data_ptr(),
+                                           self._dxhat.data_ptr(), self._seen.data_ptr(), self.smooth_preds.data_ptr(), s), "lh_one_euro")
 
     @property
     def valid(self):
@@ -558,28 +629,47 @@ class InferStep:
         return None if self.frames is None else self.plan.src_frame >= 0
 
     def advance(self):
-        """boxes <- next_boxes, on the device (``track=True``): the next call crops where this one found the hand.  On a step built without
+        """boxes <- next_boxes (and rot <- next_rot with ``oriented=True``), on the device (``track=True``): the next call crops where
+        this one found the hand.  On a step built without
         ``track`` it raises LightHandError (a call the step cannot serve, as a stale ticket of InferPipeline.result; the ValueErrors
         are for bad argument values)."""
         if not self.track:
             raise LightHandError("advance() needs InferStep(frames=..., track=True)")
         self.boxes.copy_(self.next_boxes, non_blocking=True)
+        if self.oriented:
+            self.rot.copy_(self.next_rot, non_blocking=True)
+
+    def reset_filter(self, slots=None):
+        """Forget the One-Euro filter's state of ``slots`` (indices or a mask; None: all), on the device: their next frame passes
+        through unfiltered and starts the filter again.  LightHandError on a step built without ``smooth=``, as advance()'s."""
+        if not self.smooth:
+            raise LightHandError("reset_filter() needs InferStep(frames=..., smooth=(min_cutoff, beta))")
+        if slots is None:
+            self._seen.zero_()
+        else:
+            self._seen[torch.as_tensor(slots, device=self._seen.device)] = 0
 
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
         self._packed = True
 
-    def __call__(self, images=None, frames=None, boxes=None, frame_index=None):
+    def __call__(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None):
         if self.frames is None:
             if frames is not None or boxes is not None or frame_index is not None:
                 raise ValueError("frames / boxes / frame_index are the inputs of InferStep(frames=(n_frames, hs, ws))")
         elif images is not None:
             raise ValueError("a step built with frames= takes frames / boxes / frame_index, not images")
+        if (rot is not None or mirror is not None) and not self.oriented:
+            raise ValueError("rot / mirror are the inputs of InferStep(frames=..., oriented=True)")
+        if dt is not None and not self.smooth:
+            raise ValueError("dt is the input of InferStep(frames=..., smooth=(min_cutoff, beta))")
         if images is not None:
             self.images.copy_(images, non_blocking=True)
-        for dst, src in ((self.frames, frames), (self.boxes, boxes), (self.frame_index, frame_index)):
+        for dst, src in ((self.frames, frames), (self.boxes, boxes), (self.frame_index, frame_index), (self.rot, rot), (self.mirror, mirror)):
             if src is not None:
                 dst.copy_(src, non_blocking=True)
+        if dt is not None:
+            self.dt.copy_(dt, non_blocking=True) if torch.is_tensor(dt) else self.dt.fill_(float(dt))
         if not self._packed:
             self.refresh_weights()
         if not self.use_graph:
@@ -592,6 +682,8 @@ class InferStep:
                 self._enqueue()
             torch.cuda.current_stream().wait_stream(warm)
             torch.cuda.synchronize()
+            if self.smooth:
+                self._seen.zero_()                                  # the warm-up run is not a frame: the first replay starts the filter
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._enqueue()
@@ -607,6 +699,8 @@ class InferPipeline:
     ``flip_test`` / ``shift_heatmap`` / ``post_process`` / ``blur_kernel`` / ``soft_argmax_beta``: as InferStep's, for every slot.
     ``frames`` / ``box_padding`` / ``track`` / ``track_min_*``: as InferStep's; every slot owns its frame buffer and boxes, and
     ``submit(frames=, boxes=, frame_index=)`` fills them (``steps[i]`` gives a slot's ``valid`` / ``next_boxes`` / ``lost``).
+    ``oriented`` / ``track_axis`` / ``track_min_axis`` / ``smooth``: as InferStep's; every slot owns its ROIs and its filter state
+    (one slot is one video stream: ``submit(rot=, mirror=, dt=)``, ``steps[i].smooth_preds`` / ``next_rot`` / ``reset_filter()``).
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -615,14 +709,16 @@ class InferPipeline:
 
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
                  blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
-                 track_min_joints=8, track_min_side=16.0):
+                 track_min_joints=8, track_min_side=16.0, oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side)
+        _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side), oriented,
+                   track_axis, track_min_axis, smooth)
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
                                 shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
                                 soft_argmax_beta=soft_argmax_beta, frames=frames, box_padding=box_padding, track=track,
-                                track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side)
+                                track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side,
+                                oriented=oriented, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth)
                       for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
@@ -633,17 +729,17 @@ class InferPipeline:
         for s in self.steps:
             s._packed = False
 
-    def submit(self, images=None, frames=None, boxes=None, frame_index=None):
+    def submit(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None):
         i = self.count % len(self.steps)
         st = self.streams[i]
         st.wait_stream(torch.cuda.current_stream())          # the caller's copy of `images` into place is ordered before
-        for t in (images, frames, boxes, frame_index):
-            if t is not None and t.is_cuda:
+        for t in (images, frames, boxes, frame_index, rot, mirror, dt):
+            if torch.is_tensor(t) and t.is_cuda:
                 # the slot's copy of an input runs on `st`: tell the caching allocator, or a caller that drops the batch right
                 # after submit() gets the same block back for the next batch while this copy is still queued
                 t.record_stream(st)
         with torch.cuda.stream(st):
-            self.steps[i](images, frames, boxes, frame_index)
+            self.steps[i](images, frames, boxes, frame_index, rot, mirror, dt)
             self.events[i] = st.record_event()
         self.count += 1
         return self.count - 1
@@ -657,7 +753,7 @@ class InferPipeline:
 
     def map(self, batches):
         """Yields (preds, maxvals) clones for every batch of the iterable, in order, keeping `depth` batches in flight.  A batch is
-        an image tensor, or a dict of submit()'s keyword arguments (frames / boxes / frame_index)."""
+        an image tensor, or a dict of submit()'s keyword arguments (frames / boxes / frame_index / rot / mirror / dt)."""
         pending = []
         for images in batches:
             pending.append(self.submit(**images) if isinstance(images, dict) else self.submit(images))

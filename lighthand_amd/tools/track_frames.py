@@ -4,6 +4,7 @@ decoded and taken back to frame coordinates, and the next frame's boxes are the 
 captured graph plus one device-to-device copy per frame, no host arithmetic in between (runtime.InferStep(frames=..., track=True)).
 
     track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
+                    [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -11,7 +12,13 @@ captured graph plus one device-to-device copy per frame, no host arithmetic in b
 (frame, hand) slots that were lost (too few confident joints: the box is kept), and the options.  The weights
 are seeded random ones, so the keypoints mean nothing and their confidences are far below InferStep's default ``track_min_score``:
 the tool sets the threshold to the median confidence of the first frame (a replay of a probe step), so about half of the joints count,
-the boxes move from frame to frame and some slots are lost -- the loop runs as it would with a trained model."""
+the boxes move from frame to frame and some slots are lost -- the loop runs as it would with a trained model.
+
+``--oriented`` follows oriented ROIs (InferStep(oriented=True): the crop is turned so that wrist -> middle-finger MCP points up),
+``--mirror`` marks every second hand as a left one (its crop is mirrored; needs ``--oriented``), ``--one_euro MIN_CUTOFF BETA``
+filters the keypoints (InferStep(smooth=...)); the line then also gives the mean distance between ``preds`` and ``smooth_preds``.
+``--spin DEG_PER_FRAME`` turns every synthetic constellation about its centre.  With none of the four the sequence and the line are
+what they were; the new keys appear only with the new options."""
 import argparse
 import json
 import time
@@ -37,13 +44,17 @@ def build_parser():
     ap.add_argument("--flip_test", action="store_true", help="average with the flipped-back heat-maps of the mirrored crop")
     ap.add_argument("--dark_decode", action="store_true", help="DARK decode in place of the plain arg-max")
     ap.add_argument("--seed", default=0, type=int)
+    ap.add_argument("--oriented", action="store_true", help="oriented ROIs: the crop follows the hand's rotation in the image plane")
+    ap.add_argument("--mirror", action="store_true", help="every second hand is a left one: its crop is mirrored (needs --oriented)")
+    ap.add_argument("--one_euro", nargs=2, type=float, default=None, metavar=("MIN_CUTOFF", "BETA"), help="One-Euro filter of the keypoints")
+    ap.add_argument("--spin", default=0.0, type=float, metavar="DEG_PER_FRAME", help="turn each synthetic constellation about its centre")
     return ap
 
 
-def synthetic_sequence(n, hs, ws, hands, seed=0):
+def synthetic_sequence(n, hs, ws, hands, seed=0, spin=0.0):
     """n frames uint8 [n][hs][ws][3] and the first frame's hand boxes fp32 [hands][4] (pixel-index coordinates, the bounds of each
     hand's 21 joints).  Every hand is a fixed constellation of 21 discs, about a fifth of the frame's short side across, whose
-    centre drifts on a seeded smooth path that stays inside the frame."""
+    centre drifts on a seeded smooth path that stays inside the frame; ``spin`` degrees per frame turn it about that centre."""
     rng = np.random.RandomState(seed)
     span = max(8.0, min(hs, ws) / 5.0)
     frames = rng.randint(0, 32, size=(n, hs, ws, 3)).astype(np.uint8)
@@ -56,7 +67,11 @@ def synthetic_sequence(n, hs, ws, hands, seed=0):
     boxes = np.zeros((hands, 4), np.float32)
     for t in range(n):
         drift = 0.5 * span * np.sin(phase + speed * t) - 0.5 * span * np.sin(phase)
-        joints = shape + np.clip(start + drift, [span, span], [ws - span, hs - span])[:, None, :]
+        turned = shape
+        if spin:
+            c, s = np.cos(np.deg2rad(spin * t)), np.sin(np.deg2rad(spin * t))
+            turned = shape @ np.array([[c, s], [-s, c]])
+        joints = turned + np.clip(start + drift, [span, span], [ws - span, hs - span])[:, None, :]
         if t == 0:
             boxes[:, :2], boxes[:, 2:] = joints.min(1), joints.max(1)
         for x, y in np.rint(joints.reshape(-1, 2)).astype(int):
@@ -79,33 +94,56 @@ def main(argv=None):
         raise SystemExit("camera footage is not shipped: pass --synthetic N")
     if args.hands < 1:
         ap.error("--hands must be >= 1")
+    if args.mirror and not args.oriented:
+        ap.error("--mirror needs --oriented")
     hs, ws = args.frame_size
-    frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed)
+    frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed, spin=args.spin)
     torch.manual_seed(args.seed)
     model = get_pose_net(default_config(args.depth), is_train=True).cuda().set_precision(args.precision)
     model.eval()
     options = dict(frames=(1, hs, ws), flip_test=args.flip_test, post_process="dark" if args.dark_decode else False)
+    if args.oriented:
+        options["oriented"] = True
+    mirror = torch.arange(args.hands, dtype=torch.int32) % 2 if args.mirror else None
     seq = torch.from_numpy(frames).pin_memory()
     probe = InferStep(model, args.hands, args.size, args.size, **options)
-    probe(frames=seq[:1], boxes=torch.from_numpy(boxes))
+    probe(frames=seq[:1], boxes=torch.from_numpy(boxes), mirror=mirror)
     score = float(probe.maxvals.median())                          # random weights: see the module docstring
     del probe
+    if args.one_euro:
+        options["smooth"] = tuple(args.one_euro)
     step = InferStep(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
     step.boxes.copy_(torch.from_numpy(boxes))
     lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
-    step(frames=seq[:1])                                           # capture; the loop below starts from the first frame's boxes again
+    moved = torch.zeros((), dtype=torch.float64, device=step.lost.device)
+    step(frames=seq[:1], mirror=mirror)                            # capture; the loop below starts from the first frame's boxes again
     step.boxes.copy_(torch.from_numpy(boxes))
+    if args.oriented:
+        step.rot.copy_(torch.tensor([1.0, 0.0]).expand(args.hands, 2))
+    if args.one_euro:
+        step.reset_filter()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(args.synthetic):
         step(frames=seq[t:t + 1])
         lost += step.lost
+        if args.one_euro:
+            moved += (step.smooth_preds - step.preds).norm(dim=-1).mean().double()
         step.advance()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     result = {"frames_per_s": round(args.synthetic / dt, 2), "frames": args.synthetic, "slots": args.synthetic * args.hands,
               "slots_lost": int(lost.sum()), "frame_size": [hs, ws], "hands": args.hands, "depth": args.depth,
               "precision": args.precision, "size": args.size, "track_min_score": score, "flip_test": args.flip_test, "dark_decode": args.dark_decode, "seed": args.seed}
+    if args.oriented:
+        result["oriented"] = True
+    if args.mirror:
+        result["mirror"] = mirror.tolist()
+    if args.one_euro:
+        result["one_euro"] = list(args.one_euro)
+        result["smooth_mean_dist"] = float(moved) / args.synthetic
+    if args.spin:
+        result["spin"] = args.spin
     print(json.dumps(result))
     return result
 

@@ -5,7 +5,12 @@ Coordinates are pixel indices (pixel centres on the integers, an image spans [-0
 the box that encloses pixels i0..i1 is (i0-0.5, i1+0.5).  The matrix of a box takes a CROP pixel index to a FRAME pixel index: the
 crop kernel (lh_frames_crop_to_nhwc4) samples through it and lh_affine_points takes the decoded keypoints back to the frame through
 it.  The ``*_host`` functions follow the kernels operation by operation in fp32 (the library is built with -ffp-contract=off): the CPU
-tests check the geometry on them, the GPU tests check the kernels against them."""
+tests check the geometry on them, the GPU tests check the kernels against them.
+
+Oriented, mirrored ROIs and the One-Euro filter (lh_roi_affine / lh_keypoints_to_rois / lh_one_euro, InferStep(oriented=True, smooth=...))
+follow the same pattern: ``roi_affine`` / ``rois_from_keypoints`` / ``one_euro`` on device tensors, ``*_host`` in numpy, ``one_euro_host64``
+the filter's recurrence in fp64.  An orientation is a direction vector -- the frame direction of the crop's +x axis, (1, 0) = upright --
+never an angle: the kernels use + - * /, sqrt, abs and comparisons only, which numpy rounds as the device does."""
 import numpy as np
 
 F = np.float32
@@ -62,6 +67,127 @@ def boxes_from_keypoints_host(preds, maxvals, boxes, src_frame, min_score=0.1, m
     return out, lost.astype(np.int32)
 
 
+def rot_from_angle(radians):
+    """The orientation (cos, sin) of a crop turned by ``radians`` in the image plane (x to the right, y down: a positive angle turns
+    the crop's +x axis towards the frame's +y).  The kernels take the direction, never the angle."""
+    import math
+    return (math.cos(radians), math.sin(radians))
+
+
+def roi_affine_host(boxes, rot, mirror, frame_index, n_frames, size, padding):
+    """boxes [b][4], rot [b][2] (frame direction of the crop's +x axis, any length), mirror [b], frame_index [b], size = (h, w) of the
+    crop -> (mat fp32 [b][6], src_frame int32 [b]); lh_roi_affine in numpy."""
+    h, w = F(size[0]), F(size[1])
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    rot = np.asarray(rot, np.float32).reshape(-1, 2)
+    g = np.where(np.asarray(mirror).reshape(-1) != 0, F(-1), F(1)).astype(np.float32)
+    fi = np.asarray(frame_index, np.int32).reshape(-1)
+    pad = F(padding)
+    x0, y0, x1, y1 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    rx, ry = rot[:, 0], rot[:, 1]
+    with np.errstate(all="ignore"):
+        bw, bh = x1 - x0, y1 - y0
+        n = np.sqrt(rx * rx + ry * ry)
+        ok = (fi >= 0) & (fi < n_frames) & np.isfinite(boxes).all(1) & (bw > 0) & (bh > 0) & np.isfinite(rot).all(1) & (n > 0)
+        cx, cy = (x0 + x1) * F(0.5), (y0 + y1) * F(0.5)
+        sw = pad * np.maximum(bw, bh * w / h)
+        a = sw / w
+        c, s = rx / n, ry / n
+        ac, as_ = a * c, a * s
+        m0, m1, m3, m4 = g * ac, -as_, g * as_, ac
+        hx, hy = (w - F(1)) * F(0.5), (h - F(1)) * F(0.5)
+        mat = np.stack([m0, m1, cx - (m0 * hx + m1 * hy), m3, m4, cy - (m3 * hx + m4 * hy)], 1).astype(np.float32)
+    mat[~ok] = 0
+    return mat, np.where(ok, fi, -1).astype(np.int32)
+
+
+def rois_from_keypoints_host(preds, maxvals, boxes, rot, src_frame, axis=(0, 9), min_score=0.1, min_joints=8, min_side=16.0, min_axis=4.0):
+    """preds [b][j][2] (frame coordinates), maxvals [b][j] or [b][j][1], boxes [b][4], rot [b][2], src_frame [b] -> (next_boxes fp32
+    [b][4], next_rot fp32 [b][2], lost int32 [b]); lh_keypoints_to_rois in numpy, the joints walked in order."""
+    preds = np.asarray(preds, np.float32)
+    b, j = preds.shape[:2]
+    mv = np.asarray(maxvals, np.float32).reshape(b, j)
+    boxes = np.asarray(boxes, np.float32).reshape(b, 4)
+    rot = np.asarray(rot, np.float32).reshape(b, 2)
+    src = np.asarray(src_frame, np.int32).reshape(b)
+    k0, k1 = axis
+    score, side = F(min_score), F(min_side)
+    with np.errstate(all="ignore"):
+        rx, ry = rot[:, 0], rot[:, 1]
+        rn = np.sqrt(rx * rx + ry * ry)
+        c, s = rx / rn, ry / rn
+        dx, dy = preds[:, k1, 0] - preds[:, k0, 0], preds[:, k1, 1] - preds[:, k0, 1]
+        d = np.sqrt(dx * dx + dy * dy)
+        turn = (mv[:, k0] >= score) & (mv[:, k1] >= score) & (d >= F(min_axis))
+        c, s = np.where(turn, -(dy / d), c).astype(np.float32), np.where(turn, dx / d, s).astype(np.float32)
+        lo_p, lo_q, hi_p, hi_q = (np.zeros(b, np.float32) for _ in range(4))
+        n = np.zeros(b, np.int64)
+        for k in range(j):
+            take = mv[:, k] >= score
+            x, y = preds[:, k, 0], preds[:, k, 1]
+            u, v = x * c + y * s, y * c - x * s
+            first = take & (n == 0)
+            lo_p, hi_p = np.where(first, u, lo_p), np.where(first, u, hi_p)
+            lo_q, hi_q = np.where(first, v, lo_q), np.where(first, v, hi_q)
+            lo_p, hi_p = np.where(take & (u < lo_p), u, lo_p), np.where(take & (u > hi_p), u, hi_p)
+            lo_q, hi_q = np.where(take & (v < lo_q), v, lo_q), np.where(take & (v > hi_q), v, hi_q)
+            n += take
+        half = side * F(0.5)
+        for lo, hi in ((lo_p, hi_p), (lo_q, hi_q)):
+            narrow = hi - lo < side
+            m = (lo + hi) * F(0.5)
+            lo[:], hi[:] = np.where(narrow, m - half, lo), np.where(narrow, m + half, hi)
+        cp, cq, hp, hq = (lo_p + hi_p) * F(0.5), (lo_q + hi_q) * F(0.5), (hi_p - lo_p) * F(0.5), (hi_q - lo_q) * F(0.5)
+        fx, fy = cp * c - cq * s, cp * s + cq * c
+        out = np.stack([fx - hp, fy - hq, fx + hp, fy + hq], 1).astype(np.float32)
+    lost = (n < min_joints) | (src < 0) | ~(np.isfinite(c) & np.isfinite(s))
+    nrot = np.stack([c, s], 1).astype(np.float32)
+    out[lost], nrot[lost] = boxes[lost], rot[lost]
+    return out, nrot, lost.astype(np.int32)
+
+
+TWO_PI = F(6.2831855)
+
+
+def one_euro_host(x, dt, state=None, src_frame=None, lost=None, min_cutoff=1.0, beta=0.007, d_cutoff=1.0, dtype=np.float32):
+    """One frame of the One-Euro filter, lh_one_euro in numpy: x [b][j][2], dt [b] (or a scalar) in seconds, state = (xhat, dxhat, init)
+    of the previous frame (None: nothing seen yet), src_frame / lost [b] (None: every slot is live) -> (out [b][j][2], new state).
+    The inputs are not modified."""
+    T = np.dtype(dtype).type
+    x = np.asarray(x, dtype)
+    b = x.shape[0]
+    dt = np.broadcast_to(np.asarray(dt, dtype), (b,)).reshape((b,) + (1,) * (x.ndim - 1))
+    if state is None:
+        state = (np.zeros_like(x), np.zeros_like(x), np.zeros(b, np.int32))
+    xhat, dxhat, init = np.asarray(state[0], dtype), np.asarray(state[1], dtype), np.asarray(state[2], np.int32).reshape(b)
+    away = np.zeros(b, bool)
+    if src_frame is not None:
+        away |= np.asarray(src_frame).reshape(b) < 0
+    if lost is not None:
+        away |= np.asarray(lost).reshape(b) != 0
+    shape = (b,) + (1,) * (x.ndim - 1)
+    with np.errstate(all="ignore"):
+        fresh = ((init == 0).reshape(shape) | ~(dt > 0) | ~np.isfinite(dt))
+        rd = (T(TWO_PI) * T(d_cutoff)) * dt
+        ad = rd / (rd + T(1))
+        dx = (x - xhat) / dt
+        dxh = ad * dx + (T(1) - ad) * dxhat
+        fc = T(min_cutoff) + T(beta) * np.abs(dxh)
+        r = (T(TWO_PI) * fc) * dt
+        al = r / (r + T(1))
+        nx = al * x + (T(1) - al) * xhat
+    aw = away.reshape(shape)
+    new_xhat = np.where(aw, xhat, np.where(fresh, x, nx)).astype(dtype)
+    new_dxhat = np.where(aw, dxhat, np.where(fresh, T(0), dxh)).astype(dtype)
+    out = np.where(aw | fresh, x, nx).astype(dtype)
+    return out, (new_xhat, new_dxhat, np.where(away, 0, 1).astype(np.int32))
+
+
+def one_euro_host64(x, dt, state=None, src_frame=None, lost=None, min_cutoff=1.0, beta=0.007, d_cutoff=1.0):
+    """one_euro_host's recurrence in fp64: what the fp32 order of operations is measured against."""
+    return one_euro_host(x, dt, state, src_frame, lost, min_cutoff, beta, d_cutoff, dtype=np.float64)
+
+
 def _stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
@@ -107,3 +233,78 @@ def boxes_from_keypoints(preds, maxvals, boxes, src_frame, min_score=0.1, min_jo
                                                      float(min_score), int(min_joints), float(min_side), nxt.data_ptr(), lost.data_ptr(),
                                                      _stream()), "lh_keypoints_to_boxes")
     return nxt, lost
+
+
+def roi_affine(boxes, rot, mirror, frame_index, n_frames, size, padding=1.25):
+    """Device tensors boxes fp32 [b][4], rot fp32 [b][2], mirror int32 [b], frame_index int32 [b] -> (mat fp32 [b][6], src_frame int32
+    [b]) for an h x w = ``size`` crop (one lh_roi_affine launch on the current stream)."""
+    import torch
+    from . import _lib
+    if not padding > 0:
+        raise ValueError(f"padding must be > 0, not {padding!r}")
+    boxes = boxes.to(torch.float32).contiguous()
+    rot = rot.to(torch.float32).contiguous()
+    mirror = mirror.to(torch.int32).contiguous()
+    frame_index = frame_index.to(torch.int32).contiguous()
+    b = boxes.shape[0]
+    if (tuple(boxes.shape) != (b, 4) or tuple(rot.shape) != (b, 2) or tuple(mirror.shape) != (b,) or tuple(frame_index.shape) != (b,)
+            or not boxes.is_cuda or any(t.device != boxes.device for t in (rot, mirror, frame_index))):
+        raise _lib.LightHandError(f"roi_affine: boxes [b, 4], rot [b, 2], mirror [b] and frame_index [b] on one device, got "
+                                  f"{tuple(boxes.shape)} / {tuple(rot.shape)} / {tuple(mirror.shape)} / {tuple(frame_index.shape)}")
+    mat = torch.empty(b, 6, dtype=torch.float32, device=boxes.device)
+    src = torch.empty(b, dtype=torch.int32, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        _lib.check(_lib.load().lh_roi_affine(boxes.data_ptr(), rot.data_ptr(), mirror.data_ptr(), frame_index.data_ptr(), b, int(n_frames),
+                                             int(size[0]), int(size[1]), float(padding), mat.data_ptr(), src.data_ptr(), _stream()),
+                   "lh_roi_affine")
+    return mat, src
+
+
+def rois_from_keypoints(preds, maxvals, boxes, rot, src_frame, axis=(0, 9), min_score=0.1, min_joints=8, min_side=16.0, min_axis=4.0):
+    """Device tensors preds fp32 [b][j][2] (frame coordinates), maxvals [b][j] or [b][j][1], boxes [b][4], rot [b][2], src_frame int32
+    [b] -> (next_boxes fp32 [b][4], next_rot fp32 [b][2], lost int32 [b]) (one lh_keypoints_to_rois launch on the current stream)."""
+    import torch
+    from . import _lib
+    preds = preds.to(torch.float32).contiguous()
+    b, j = preds.shape[:2]
+    maxvals = maxvals.to(torch.float32).reshape(b, j).contiguous()
+    boxes = boxes.to(torch.float32).contiguous()
+    rot = rot.to(torch.float32).contiguous()
+    src_frame = src_frame.to(torch.int32).contiguous()
+    if (tuple(preds.shape) != (b, j, 2) or tuple(boxes.shape) != (b, 4) or tuple(rot.shape) != (b, 2) or tuple(src_frame.shape) != (b,)
+            or not preds.is_cuda):
+        raise _lib.LightHandError(f"rois_from_keypoints: preds [b, j, 2], boxes [b, 4], rot [b, 2], src_frame [b] on the device, got "
+                                  f"{tuple(preds.shape)} / {tuple(boxes.shape)} / {tuple(rot.shape)} / {tuple(src_frame.shape)}")
+    nxt = torch.empty(b, 4, dtype=torch.float32, device=preds.device)
+    nrot = torch.empty(b, 2, dtype=torch.float32, device=preds.device)
+    lost = torch.empty(b, dtype=torch.int32, device=preds.device)
+    with torch.cuda.device(preds.device):
+        _lib.check(_lib.load().lh_keypoints_to_rois(preds.data_ptr(), maxvals.data_ptr(), boxes.data_ptr(), rot.data_ptr(), src_frame.data_ptr(),
+                                                    b, j, int(axis[0]), int(axis[1]), float(min_score), int(min_joints), float(min_side),
+                                                    float(min_axis), nxt.data_ptr(), nrot.data_ptr(), lost.data_ptr(), _stream()),
+                   "lh_keypoints_to_rois")
+    return nxt, nrot, lost
+
+
+def one_euro(x, dt, state, src_frame, lost=None, min_cutoff=1.0, beta=0.007, d_cutoff=1.0, out=None):
+    """One frame of the One-Euro filter on device tensors: x fp32 [b][j][2], dt fp32 [b], state = (xhat, dxhat fp32 [b][j][2], init int32
+    [b]) UPDATED IN PLACE (fresh state: zeros), src_frame int32 [b], lost int32 [b] or None -> out fp32 [b][j][2] (one lh_one_euro
+    launch on the current stream)."""
+    import torch
+    from . import _lib
+    xhat, dxhat, init = state
+    b, j = x.shape[:2]
+    good = (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (b, j, 2)
+            and all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape and t.device == x.device for t in (xhat, dxhat))
+            and all(t is None or (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (b,) and t.device == x.device)
+                    for t in (init, src_frame, lost))
+            and dt.dtype == torch.float32 and dt.is_contiguous() and tuple(dt.shape) == (b,) and dt.device == x.device)
+    if not good or init is None or src_frame is None:
+        raise _lib.LightHandError("one_euro: x, xhat, dxhat contiguous fp32 [b, j, 2], dt fp32 [b], init / src_frame / lost int32 [b], on one device")
+    if out is None:
+        out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().lh_one_euro(x.data_ptr(), src_frame.data_ptr(), lost.data_ptr() if lost is not None else None, dt.data_ptr(),
+                                           b, j, float(min_cutoff), float(beta), float(d_cutoff), xhat.data_ptr(), dxhat.data_ptr(),
+                                           init.data_ptr(), out.data_ptr(), _stream()), "lh_one_euro")
+    return out

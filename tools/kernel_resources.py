@@ -2,13 +2,14 @@
 """Scratch memory and spilled registers of every kernel in the built library, read from the metadata notes of its gfx950 code objects.
 
 usage: tools/kernel_resources.py [--write] [filter]
-  prints  <scratch bytes> <spilled VGPRs> <kernel symbol>  per kernel; --write regenerates tests/golden/kernel_ceilings.json
-  (the ceilings tests/test_kernel_resources.py holds every kernel to) from the library as built.
+  prints  <scratch bytes> <spilled VGPRs> <kernel symbol>  per kernel; --write regenerates the table in force, GOLDEN below
+  (the ceilings tests/test_kernel_resources.py holds every kernel to), from the library as built.
 
-Two tables: tests/golden/kernel_resources.json is the first table, frozen as committed (a change that adds kernels adds test files and
-leaves the existing ones alone); kernel_ceilings.json is the table in force.  It may only extend the frozen one -- every entry of
-kernel_resources.json is in it with figures no higher (tests/test_kernel_ceilings.py) -- so a kernel can gain an entry or earn a lower
-one, never a higher one.
+Tables: tests/golden/kernel_resources.json is the first table, frozen as committed; kernel_ceilings.json extended it by the kernels of
+top-down inference on full frames and is the fixture of tests/test_kernel_ceilings.py; GOLDEN = kernel_ceilings_roi.json is the table
+in force: kernel_ceilings.json, entry for entry, plus the oriented-ROI and One-Euro kernels (both earlier files are fixtures of tests
+that stay as committed, so the new entries went into a file of their own).  The table in force only extends the earlier ones
+(tests/test_kernel_ceilings.py, tests/test_roi_host.py): a kernel can gain an entry or earn a lower one, never a higher one.
 
 The library carries one clang offload bundle per translation unit in its .hip_fatbin section; each bundle holds the gfx950 code object
 whose NT_AMDGPU_METADATA note lists .private_segment_fixed_size and .vgpr_spill_count per kernel (llvm-readelf --notes prints it)."""
@@ -24,7 +25,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "lighthand_amd", "liblighthand_hip.so")
 FROZEN = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_ceilings.json")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_ceilings_roi.json")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 

@@ -3,7 +3,11 @@
 the crops already exist -- against InferStep(frames=(32, 1080, 1920)) with two hand boxes per frame and against the same with
 track=True, alternated in ONE process on R50 64 x 256^2 bf16.  The frame legs add lh_box_affine, lh_affine_points [and
 lh_keypoints_to_boxes] and swap the uint8 input kernel for lh_frames_crop_to_nhwc4, which writes the same bytes but gathers them from
-199 MB of frames.  Device events around `steps` replays, after a warm-up; median over the rounds.
+199 MB of frames.  Two more legs price the oriented ROIs and the One-Euro filter against the track=True leg of the same run:
+oriented + track swaps lh_box_affine / lh_keypoints_to_boxes for lh_roi_affine / lh_keypoints_to_rois (seeded directions, every second
+box mirrored), oriented + track + smooth adds the lh_one_euro launch; the upright leg runs the oriented kernels with rot = (1, 0) and
+no mirror, which separates the cost of the two sibling launches from that of gathering along turned rows.  Device events around `steps` replays, after a warm-up; median
+over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
 import statistics
@@ -40,13 +44,22 @@ def main():
     half = rng.uniform(75, 250, size=(batch, 1))
     boxes = torch.from_numpy(np.concatenate([centre - half, centre + half], 1).astype(np.float32)).cuda()
     index = (torch.arange(batch, dtype=torch.int32) // 2).cuda()
+    rot = torch.from_numpy(rng.normal(size=(batch, 2)).astype(np.float32)).cuda()
+    mirror = (torch.arange(batch, dtype=torch.int32) % 2).cuda()
 
     forms = {"uint8 crops": InferStep(model, batch, size, size, input_u8=(size, size)),
              "frames": InferStep(model, batch, size, size, frames=(n_frames, hs, ws)),
-             "frames+track": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True)}
+             "frames+track": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True),
+             "oriented+track": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True),
+             "oriented upright": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True),
+             "oriented+track+smooth": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True,
+                                                smooth=(1.0, 0.007))}
     forms["uint8 crops"](crops)
     for tag in ("frames", "frames+track"):
         forms[tag](frames=frames, boxes=boxes, frame_index=index)
+    for tag in ("oriented+track", "oriented+track+smooth"):
+        forms[tag](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
+    forms["oriented upright"](frames=frames, boxes=boxes, frame_index=index)
     for step in forms.values():
         timed(step, 10)                                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
@@ -56,8 +69,8 @@ def main():
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
     for tag, v in ms.items():
-        print(f"  {tag:14s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops; rounds: "
-              f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
+        print(f"  {tag:21s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops, "
+              f"{med[tag] - med['frames+track']:+.3f} vs frames+track; rounds: {', '.join(f'{x:.3f}' for x in v)})", flush=True)
 
 
 if __name__ == "__main__":
