@@ -1,0 +1,121 @@
+"""Preconditions of the exact-arithmetic GPU tests (tests/exact_data.py), proved on the CPU for every case and precision those tests run:
+(a) every sum of magnitudes, in units of the product quantum, is below 2^24 -- so an fp32 accumulator is exact in any order;
+(b) no expected fp16 value overflows;
+(c) out and dx together hold at least 10 exact ties and at least 100 values that need rounding -- so a wrong rounding mode cannot pass.
+Plus: the hand-written tap loop that serves as the epilogue test's host side agrees with F.conv2d / F.conv_transpose2d in fp64."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import exact_data as E
+
+_PLAN_CASES = [(c, False, None) for c in E.CONV_CASES] + [(c, True, b) for c in E.DECONV_CASES for b in (False, True)]
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16", "fp32"])
+@pytest.mark.parametrize("case,transposed,bias", _PLAN_CASES)
+def test_plan_level_cases_meet_the_preconditions(case, transposed, bias, precision):
+    x, w, b, dy = E.conv_data(case, precision, bias=bias, transposed=transposed)
+    ax, aw = E.ranges(case, precision)
+    assert ax >= E.RANGES[precision][0] and aw >= E.RANGES[precision][1]                # widened, never narrowed
+    dt = E.DTYPES[precision]
+    for t in (x, w, dy) + ((b,) if b is not None else ()):
+        assert torch.equal(t.to(dt).float(), t) and torch.equal(t, t.round())         # integers the type holds exactly
+    worst = E.check_exact(x, w, b, dy, case, transposed)                                # (a)
+    r = E.reference(x, w, b, dy, case, transposed)
+    if precision == "fp32":
+        for k in ("out", "dx", "dw"):
+            assert torch.equal(r[k].float().double(), r[k])
+        return
+    peak = max(float(r["out"].abs().max()), float(r["dx"].abs().max()))
+    if precision == "fp16":
+        assert peak <= E.FP16_MAX                                                       # (b)
+        assert bool(torch.isfinite(E.expected_16(r["out"], dt)).all()) and bool(torch.isfinite(E.expected_16(r["dx"], dt)).all())
+    (ro, to), (rd, td) = E.rounding_counts(r["out"], dt), E.rounding_counts(r["dx"], dt)
+    print(case, precision, f"largest sum of magnitudes {worst:.0f}, peak {peak:.0f}, need rounding {ro + rd}, ties {to + td}")
+    assert to + td >= 10 and ro + rd >= 100, (ro + rd, to + td)                         # (c)
+
+
+def test_strided_1x1_data_gradient_leaves_the_other_phases_zero():
+    """(64, 136, 1, 2, 0, 2, 9, 7): the data gradient writes pixels (2a, 2b) only; the host's dx is exactly zero elsewhere, and the
+    GPU comparison is exact -- this states the property on the host reference so that it cannot go unnoticed."""
+    case = E.CONV_CASES[3]
+    x, w, b, dy = E.conv_data(case, "bf16")
+    dx = E.reference(x, w, b, dy, case)["dx"]
+    off = torch.ones_like(dx, dtype=torch.bool)
+    off[:, :, 0::2, 0::2] = False
+    assert float(dx[off].abs().max()) == 0.0 and float((dx[~off] != 0).double().mean()) > 0.9
+
+
+def test_rounding_counts_agree_with_the_conversion():
+    """rounding_counts against the type conversion itself, on every integer of a range with known ties."""
+    v = torch.arange(-5000, 5001, dtype=torch.float64)
+    for dt, first in ((torch.bfloat16, 257), (torch.float16, 2049)):
+        need, ties = E.rounding_counts(v, dt)
+        assert need == int((v.float().to(dt).double() != v).sum())
+        assert E.rounding_counts(torch.tensor([float(first)]), dt) == (1, 1) and E.rounding_counts(torch.tensor([float(first - 1)]), dt) == (0, 0)
+        assert E.rounding_counts(torch.tensor([float(2 * first + 1)]), dt) == (1, 0)
+        # a tie goes to the even neighbour: 257 -> 256 and 259 -> 260 in bf16, 2049 -> 2048 and 2051 -> 2052 in fp16
+        assert float(E.expected_16(torch.tensor([float(first)]), dt)) == first - 1 and float(E.expected_16(torch.tensor([first + 2.0]), dt)) == first + 3
+        assert ties > 100
+
+
+@pytest.mark.parametrize("flavour", list(E.EPILOGUE_RANGES))
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", list(E.EPILOGUE_CASES))
+def test_epilogue_cases_meet_the_preconditions(case, precision, flavour):
+    d = E.epilogue_data(case, precision, flavour)
+    dt = E.DTYPES[precision]
+    for k in ("x", "w", "addend", "gx"):
+        assert torch.equal(d[k].to(dt).float(), d[k]) and torch.equal(d[k], d[k].round()), k
+    assert set(d["invstd"].tolist()) <= {0.5, 1.0, 2.0} and set(d["scale"].abs().tolist()) <= {0.5, 1.0, 2.0} and bool((d["scale"] < 0).any())
+    worst = E.check_exact_epilogue(case, d)
+    ho, wo, taps = E.EPILOGUE_CASES[case][4], E.EPILOGUE_CASES[case][5], E.EPILOGUE_CASES[case][13]
+    acc = E.tap_conv(d["x"], d["w"], taps, ho, wo, torch.float64)
+    assert float(acc.abs().max()) + float(d["addend"].abs().max()) <= E.FP16_MAX
+    need, ties = E.rounding_counts(acc, dt)
+    print(case, precision, flavour, f"largest sum of magnitudes {worst:.0f}, accumulators that need rounding {need}, ties {ties}")
+    if flavour == "exact":
+        assert need >= 100 and ties >= 10
+    else:
+        # the flavour whose statistics rows are exact: sums of squares of the (rounded) accumulators, the largest term of any mode's rows
+        sq = E.expected_16(acc, dt).double().reshape(-1, acc.shape[-1]) ** 2
+        assert E.check_exact_rows(sq)[0]
+
+
+def test_tap_loop_equals_conv2d_and_conv_transpose2d():
+    """The tap loop of the epilogue test's host side (exact_data.tap_conv) in fp64 against torch: the 3 x 3 tap list is F.conv2d with
+    padding 1, and the four taps of the 'phase' case are output pixels (2a + 1, 2b) of F.conv_transpose2d(kernel 4, stride 2, padding 1),
+    with tap (dh, dw) reading kernel element (ky, kx) = (2 - 2 dh, 1 - 2 dw)."""
+    g = torch.Generator().manual_seed(100)
+    n, hi, wi, cin, cout = 2, 5, 4, 8, 16
+    x = E.ints((n, hi, wi, cin), 8, g)
+    taps3 = E.EPILOGUE_CASES["c72"][13]
+    w3 = E.ints((cout, 9, cin), 4, g)
+    got = E.tap_conv(x, w3, taps3, hi, wi, torch.float64)
+    want = F.conv2d(x.double().permute(0, 3, 1, 2), w3.double().view(cout, 3, 3, cin).permute(0, 3, 1, 2), None, 1, 1)
+    assert torch.equal(got, want.permute(0, 2, 3, 1))
+    taps = E.EPILOGUE_CASES["phase"][13]
+    wd = E.ints((cin, cout, 4, 4), 4, g)                            # ConvTranspose2d layout
+    wt = torch.stack([wd[:, :, 2 - 2 * dh, 1 - 2 * dw].t() for dh, dw in taps], 1)      # [cout][taps][cin]
+    got = E.tap_conv(x, wt, taps, hi, wi, torch.float64)
+    full = F.conv_transpose2d(x.double().permute(0, 3, 1, 2), wd.double(), None, 2, 1, 0)
+    assert full.shape[2:] == (2 * hi, 2 * wi)
+    assert torch.equal(got, full[:, :, 1::2, 0::2].permute(0, 2, 3, 1))
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_chain_meets_the_preconditions(precision):
+    """The chain of the table-launch test: check_exact per layer with that layer's quanta (inside chain_reference), weights in
+    {-1, 0, 1} * 2^-s, and magnitudes that stay level and inside the type."""
+    x, params, dy = E.chain_data()
+    for name, *_rest, nz, sh in E.CHAIN_LAYERS:
+        w = params[name + ".weight"]
+        assert set((w * 2.0 ** sh).unique().tolist()) <= {-1.0, 0.0, 1.0}
+    out, dx, grads, worst = E.chain_reference(x, params, dy, precision)
+    print(precision, "largest sums of magnitudes per layer, in quanta:", [(n, f"{m:.0f}") for n, m in worst])
+    assert max(m for _, m in worst) < E.LIMIT
+    assert float(out.abs().max()) <= E.FP16_MAX and float(dx.abs().max()) <= E.FP16_MAX
+    for k, g in grads.items():
+        assert torch.equal(g.float().double(), g), k                  # fp32 holds every expected gradient exactly
+        assert float((g != 0).double().mean()) > 0.5, k               # and the gradients are dense: every pixel counts

@@ -15,11 +15,21 @@ other phases keep what the buffer held.
 
 Statistics rows: a launch writes one row per pixel tile, so forms with different tile pixels write different row COUNTS and cannot be
 compared row by row; forms that share the pixel tile (256 x 256 and 128 x 256) are compared bit for bit, and every form's column totals are
-held to the stored values as tests/test_gpu_ops.py's gate test does (rtol = 2e-3, atol = 2e-3 x the largest column's sum of magnitudes)."""
+held to the stored values as tests/test_gpu_ops.py's gate test does (rtol = 2e-3, atol = 2e-3 x the largest column's sum of magnitudes).
+
+Data flavours.  "random": normal operands, the assertions above.  "exact" and "exact_small" (tests/exact_data.py): integer x, w, addend and
+BN input, integer mean and shift, invstd and scale from {0.5, 1, 2} -- every accumulator and every epilogue sum is exact in fp32, so the
+stored outputs must equal _host(...) BIT FOR BIT (compared as int16) in every mode on every form: the accumulator rounded to 16 bits, the
+addend added in fp32, the sum rounded again, then ReLU, then the gate (igemm_epilogue.h).  A statistics row is exact as well wherever the
+sums of magnitudes of its terms stay below 2^24: then the fp64 sum of the slab rows EQUALS the fp64 sums over the stored values.  That
+holds for every row of "exact_small" (asserted) and for the rows of "exact" whose bound holds on the host values (sums: always; sums of
+squares of values that need rounding cannot stay below 2^24, see exact_data.EPILOGUE_RANGES -- those rows keep the rtol check)."""
 import ctypes as C
 
 import pytest
 import torch
+
+import exact_data as E
 
 pytestmark = pytest.mark.gpu
 
@@ -62,30 +72,33 @@ def _desc(case, form):
 _DATA = {}
 
 
-def _data(case, precision):
+def _data(case, precision, flavour="random"):
     """Operands (on the device, rounded to the run precision) and the host fp32 accumulator of one case: made once, never changed."""
-    key = (case, precision)
+    key = (case, precision, flavour)
     if key in _DATA:
         return _DATA[key]
     n, hi, wi, cin, ho, wo, cout, OH, OW, osh, osw, ooh, oow, taps, _ = CASES[case]
     td = _TD[precision]
-    g = torch.Generator().manual_seed(1234 + len(case))
-    x = torch.randn(n, hi, wi, cin, generator=g).to(td)
-    w = (torch.randn(cout, len(taps), cin, generator=g) / (len(taps) * cin) ** 0.5).to(td)
     P = OH * OW * n
-    addend = torch.randn(P, cout, generator=g).to(td)
-    gx = torch.randn(P, cout, generator=g).to(td)
-    amask = torch.randint(0, 256, (P * cout // 8,), generator=g, dtype=torch.uint8)
-    gmask = torch.randint(0, 256, (P * cout // 8,), generator=g, dtype=torch.uint8)
-    mean, shift = torch.randn(cout, generator=g) * 0.3, torch.randn(cout, generator=g) * 0.3
-    invstd, scale = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
+    if flavour == "random":
+        g = torch.Generator().manual_seed(1234 + len(case))
+        x = torch.randn(n, hi, wi, cin, generator=g).to(td)
+        w = (torch.randn(cout, len(taps), cin, generator=g) / (len(taps) * cin) ** 0.5).to(td)
+        addend = torch.randn(P, cout, generator=g).to(td)
+        gx = torch.randn(P, cout, generator=g).to(td)
+        amask = torch.randint(0, 256, (P * cout // 8,), generator=g, dtype=torch.uint8)
+        gmask = torch.randint(0, 256, (P * cout // 8,), generator=g, dtype=torch.uint8)
+        mean, shift = torch.randn(cout, generator=g) * 0.3, torch.randn(cout, generator=g) * 0.3
+        invstd, scale = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
+    else:
+        assert CASES[case][:14] == E.EPILOGUE_CASES[case]
+        d = E.epilogue_data(case, precision, flavour)
+        E.check_exact_epilogue(case, d)                  # every sum of magnitudes below 2^24: the accumulator is exact in any order
+        x, w, addend, gx = (d[k].to(td) for k in ("x", "w", "addend", "gx"))
+        assert all(torch.equal(t.float(), d[k]) for t, k in ((x, "x"), (w, "w"), (addend, "addend"), (gx, "gx")))
+        amask, gmask, mean, shift, invstd, scale = (d[k] for k in ("amask", "gmask", "mean", "shift", "invstd", "scale"))
     # host fp32: acc[n][a][b][co] = sum_t sum_k x[n][a + dh_t][b + dw_t][k] * w[co][t][k], zero outside the image
-    pad = 2
-    xp = torch.zeros(n, hi + 2 * pad, wi + 2 * pad, cin)
-    xp[:, pad:pad + hi, pad:pad + wi] = x.float()
-    acc = torch.zeros(n, ho, wo, cout)
-    for t, (dh, dw) in enumerate(taps):
-        acc += xp[:, pad + dh:pad + dh + ho, pad + dw:pad + dw + wo] @ w[:, t].float().t()
+    acc = E.tap_conv(x.float(), w.float(), taps, ho, wo)
     # the weight pack: [rows padded to 128][taps][K padded to 128 bytes], zero padding
     kpad = (cin * 2 + 127) // 128 * 64
     pack = torch.zeros((cout + 127) // 128 * 128, len(taps), kpad, dtype=td)
@@ -102,9 +115,9 @@ def _data(case, precision):
     return _DATA[key]
 
 
-def _host(case, precision, mode):
+def _host(case, precision, mode, flavour="random"):
     """(expected stored values of the launch's pixels, gate-on mask or None) in fp32 with the epilogue's roundings."""
-    h, _ = _data(case, precision)
+    h, _ = _data(case, precision, flavour)
     td, pos = _TD[precision], h["pos"]
     v = h["acc"].to(td).float()
     if mode in ("addend", "addend_mask", "gate_addend"):
@@ -124,11 +137,11 @@ def _host(case, precision, mode):
     return v, on
 
 
-def _launch(case, precision, mode, form):
+def _launch(case, precision, mode, form, flavour="random"):
     """One launch -> (whole output buffer, slab rows or None), on the host."""
     from lighthand_amd import _lib
     lib = _lib.load()
-    _, dv = _data(case, precision)
+    _, dv = _data(case, precision, flavour)
     d = _desc(case, form)
     d.relu = 1 if mode == "relu" else 0
     n, cout, OH, OW = CASES[case][0], CASES[case][6], CASES[case][7], CASES[case][8]
@@ -158,17 +171,36 @@ def _launch(case, precision, mode, form):
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
 @pytest.mark.parametrize("case", list(CASES))
 def test_epilogue_mode_on_every_tile_form(case, precision, mode):
-    h, _ = _data(case, precision)
-    want, on = _host(case, precision, mode)
+    _check(case, precision, mode, "random")
+
+
+@pytest.mark.parametrize("flavour", ["exact", "exact_small"])
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", list(CASES))
+def test_epilogue_mode_exact_on_every_tile_form(case, precision, mode, flavour):
+    """Integer data: the stored bits equal the host's in every mode on every form, and the statistics rows equal the sums of the stored
+    values wherever the 2^24 bound holds (module docstring)."""
+    _check(case, precision, mode, flavour)
+
+
+def _check(case, precision, mode, flavour):
+    exact = flavour != "random"
+    h, _ = _data(case, precision, flavour)
+    want, on = _host(case, precision, mode, flavour)
     pos, cout = h["pos"], CASES[case][6]
     M = pos.numel()
     untouched = torch.ones(CASES[case][0] * CASES[case][7] * CASES[case][8], dtype=torch.bool)
     untouched[pos] = False
     first, slabs = None, {}
     for form in CASES[case][14]:
-        out, slab = _launch(case, precision, mode, form)
+        out, slab = _launch(case, precision, mode, form, flavour)
         stored = out[pos].float()
         assert bool((out[untouched].float() == SENTINEL).all()), (form, "a pixel outside the launch was written")
+        if exact:
+            same = out[pos].view(torch.int16) == want.to(_TD[precision]).view(torch.int16)
+            assert bool(same.all()), (form, f"{int((~same).sum())} of {same.numel()} stored values differ from the host's bits, first at "
+                                            f"{tuple(int(v) for v in (~same).nonzero()[0])}")
         err = rel_err(stored, want)
         print(f"{case} {precision} {mode} {form}: rel err vs host fp32 {err:.3e}")
         assert err < TOL[precision], (form, err)
@@ -189,7 +221,15 @@ def test_epilogue_mode_on_every_tile_form(case, precision, mode):
             second = sd * (h["gx"][pos].double() - h["mean"].double()) * h["invstd"].double()
         got = slab.double().sum(0)
         for which, term in ((0, sd), (1, second)):
-            assert torch.allclose(got[which], term.sum(0), rtol=2e-3, atol=2e-3 * float(term.abs().sum(0).max())), (form, which)
+            # exact flavours: every term is a multiple of the quantum (integers; the gate's second row carries invstd's halves), so a row
+            # whose sums of magnitudes stay below 2^24 quanta is exact in fp32 in any order
+            holds, worst = E.check_exact_rows(term, 0.5 if (on is not None and which == 1) else 1.0) if exact else (False, 0.0)
+            if exact and (which == 0 or flavour == "exact_small"):      # the sums row is exact in every exact flavour, both rows in "exact_small"
+                assert holds, (form, which, worst)
+            if holds:
+                assert torch.equal(got[which], term.sum(0)), (form, which, "a statistics row differs from the sums of the stored values")
+            else:
+                assert torch.allclose(got[which], term.sum(0), rtol=2e-3, atol=2e-3 * float(term.abs().sum(0).max())), (form, which)
         # the rows of forms that share the pixel tile: same rows of the same stored values, summed in the same order
         if bp in slabs:
             assert torch.equal(slab, slabs[bp][1]), f"{form} and {slabs[bp][0]} write different statistics rows"

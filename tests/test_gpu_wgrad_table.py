@@ -145,3 +145,48 @@ def test_table_run_is_bit_stable_and_capturable(monkeypatch):
         assert torch.isfinite(snaps[0][k]).all(), k
         assert torch.equal(snaps[0][k], snaps[1][k]), k
         assert torch.equal(snaps[0][k], plan.grads[k]), k
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_table_launch_is_exact_on_integer_data(precision, monkeypatch):
+    """Integer input and upstream gradient, weights in {-1, 0, 1} * 2^-s (tests/exact_data.py: every partial sum of every layer, in any
+    order, stays below 2^24 quanta -- tests/test_exact_host.py proves it layer by layer): every weight and bias gradient of the chain
+    must EQUAL the host's, which mirrors what the engine stores (each activation rounded to 16 bits once after its layer, each
+    activation gradient once after its data-gradient launch; the gradients themselves are fp32 sums of exact products) -- on the
+    per-layer path, the static and the measured table and every forced table configuration.  Each run is held to the host, not to
+    another run: a pixel split that loses a pixel cannot hide behind a tolerance or behind a path that loses the same pixel.  The
+    input has 720 pixels (22.5 stages of 32 rows, 11.25 of 64): the forced tables with short work items and the static table split
+    their 720-pixel members in two -- unequal halves with a ragged last stage --, which is asserted; "free" runs split-free."""
+    import exact_data as E
+    ChainNet = _chain()
+    proto = ChainNet()
+    x, params, dy = E.chain_data()
+    named = dict(proto.named_parameters())
+    assert set(named) == set(params) and [n for n, *_ in E.CHAIN_LAYERS] == [n for n, _ in proto.named_children()]
+    with torch.no_grad():
+        for k, v in params.items():
+            named[k].copy_(v)
+    qt = {"bf16": torch.bfloat16, "fp16": torch.float16}[precision]
+    want_out, want_dx, want, worst = E.chain_reference(x, params, dy, precision)          # check_exact per layer inside
+    print(precision, "largest sums of magnitudes per layer, in quanta:", [(n, f"{m:.0f}") for n, m in worst])
+    monkeypatch.setenv("LH_WGRAD_GROUP", "100")                # every layer in one deferred group
+    runs = {"per-layer": _grads(proto, x, dy, precision, {"LH_WGRAD_TABLE": "0"}, monkeypatch),
+            "measured": _grads(proto, x, dy, precision, {"LH_WGRAD_TABLE_TUNE_MIN": "0"}, monkeypatch),
+            "static": _grads(proto, x, dy, precision, {"LH_AUTOTUNE": "0"}, monkeypatch)}
+    for tag, force in (("free", "128,128,64,3,100000"), ("short", "128,128,32,4,8"), ("small", "64,64,64,2,6")):
+        runs[tag] = _grads(proto, x, dy, precision, {"LH_WGRAD_TABLE_FORCE": force, "LH_WGRAD_TABLE_BIG": "0"}, monkeypatch)
+    runs["big"] = _grads(proto, x, dy, precision, {"LH_WGRAD_TABLE_FORCE": "256,256,32,3,4"}, monkeypatch)
+    assert runs["per-layer"][3] == []
+    for tag, (out, dx, grads, tables) in runs.items():
+        if tag != "per-layer":
+            assert len({n for t in tables for n in t[5]}) >= 4, (tag, tables)
+        print(tag, tables)
+        if tag in ("static", "short", "small", "big"):
+            assert max(t[3] for t in tables) >= 2, (tag, "no member of any table is split", tables)
+        if tag == "free":
+            assert all(t[3] == 1 for t in tables), tables
+        assert torch.equal(out.float(), want_out.float()) and torch.equal(dx, want_dx.float().to(qt).float()), tag
+        assert set(grads) == set(want)
+        for k in grads:
+            bad = grads[k] != want[k].float()
+            assert not bool(bad.any()), (tag, k, f"{int(bad.sum())} of {bad.numel()} gradient elements differ from the exact sums")
