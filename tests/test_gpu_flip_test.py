@@ -84,9 +84,11 @@ def _maps(bj, h, w, seed):
     return a, m
 
 
-@pytest.mark.parametrize("h,w", [(64, 64), (17, 23)])
+@pytest.mark.parametrize("h,w", [(64, 64), (17, 23), (5, 7), (8, 9)])
 @pytest.mark.parametrize("shift", [True, False])
 def test_flip_merge_equals_numpy_merge_and_argmax(h, w, shift):
+    """5 x 7 = 35 elements: three of the workgroup's four waves hold no candidate and the first is partly filled; 8 x 9 = 72: one
+    full wave, eight lanes of the second, two empty waves; from 17 x 23 on every wave has one."""
     from lighthand_amd.heatmap import flip_merge_device, max_preds_device
     from oracle.heatmap import get_max_preds
     b, j = (2, 21) if w == 64 else (1, 6)

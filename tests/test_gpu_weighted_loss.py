@@ -201,6 +201,42 @@ def test_unit_weights_reproduce_the_plain_loss():
         assert loss1 == loss and np.array_equal(_bits(grad1), _bits(grad))
 
 
+@pytest.mark.parametrize("scale", [None, 1024.0])
+@pytest.mark.parametrize("numel", [3, 7, 1029])
+def test_plain_loss_tail_and_tiny_sizes_exact(numel, scale):
+    """lh_mse_heatmap where numel is no multiple of 4: 3 = the scalar tail alone, 7 = one 16-byte vector and the tail, 1029 = two
+    workgroups of vectors and a tail of one that workgroup 0 adds.  pred and target are multiples of 2^-6 in [-4, 4], so d is a
+    multiple of 2^-6 below 2^3, (float)(d * d) a multiple of 2^-12 below 2^6 (18 significant bits) and every fp64 partial sum exact in
+    any order: the loss is float32(0.5 * sum / numel) formed in float64 as the kernel forms it, the gradient d * (float32(gs) /
+    float32(numel)) in float32, both compared bit for bit, with a gradient buffer and without; the gradient buffer's four elements past
+    numel stay as they were."""
+    from lighthand_amd import _lib
+    lib = _lib.load()
+    rng = np.random.RandomState(500 + numel)
+    p = (rng.randint(-256, 257, size=numel) / 64.0).astype(F32)
+    g = (rng.randint(-256, 257, size=numel) / 64.0).astype(F32)
+    d = (p - g).astype(F32)
+    assert np.array_equal(d.astype(np.float64), p.astype(np.float64) - g.astype(np.float64)) and d.any()
+    total = (d * d).astype(F32).astype(np.float64).sum()
+    assert total == (d.astype(np.float64) ** 2).sum() and total * 4096 == np.floor(total * 4096)
+    want_loss = F32(0.5 * total / np.float64(numel))
+    want_grad = (d * (F32(1.0 if scale is None else scale) / F32(numel))).astype(F32)
+    pt, gt = torch.from_numpy(p).cuda(), torch.from_numpy(g).cuda()
+    ws = torch.empty(lib.lh_mse_workspace_bytes(numel), dtype=torch.uint8, device="cuda")
+    gs = None if scale is None else torch.tensor([scale], dtype=torch.float32, device="cuda")
+    for with_grad in (True, False):
+        loss = torch.full((), float("nan"), device="cuda")
+        grad = torch.full((numel + 4,), float("nan"), device="cuda") if with_grad else None
+        _lib.check(lib.lh_mse_heatmap(pt.data_ptr(), gt.data_ptr(), numel, loss.data_ptr(), None if grad is None else grad.data_ptr(),
+                                      None if gs is None else gs.data_ptr(), ws.data_ptr(), _stream()), "lh_mse_heatmap")
+        torch.cuda.synchronize()
+        assert np.array_equal(_bits(loss.cpu().numpy()), _bits(want_loss)), (numel, scale, with_grad)
+        if with_grad:
+            got = grad.cpu().numpy()
+            assert np.array_equal(_bits(got[:numel]), _bits(want_grad))
+            assert np.isnan(got[numel:]).all()
+
+
 def _ohkm_case():
     """b = 32, j = 21, 32 x 32 planes; samples 0..3 have 0, 3, 5 and 7 weighted joints (fewer than topk = 8)."""
     b, j, h = 32, 21, 32
