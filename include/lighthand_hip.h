@@ -408,9 +408,10 @@ typedef struct {
     const lh_bn_finalize_call* fin[4];
                                 /* optional, per term: the BatchNorm finalize of that term (batch statistics -> scale / shift /
                                  * saved mean / invstd / running statistics: what lh_bn_finalize does) has NOT run yet and is part
-                                 * of this call.  Small tensors fold the statistics slab inside the elementwise launch itself
-                                 * (one launch instead of two on the dependency chain of every BatchNorm); otherwise the call
-                                 * launches the finalize first.  fin[t]->scale / ->shift must equal scale[t] / shift[t].
+                                 * of this call: the call launches the finalize first (all pending finalizes of a call, or of every
+                                 * call of lh_fuse_fwd_multi, as ONE launch), then the elementwise kernel.  (Folding the statistics
+                                 * inside the elementwise launch was measured slower and removed in round 6.)
+                                 * fin[t]->scale / ->shift must equal scale[t] / shift[t].
                                  * ZERO-INITIALISE the descriptor (memset / = {0}): a caller compiled against the round-3 layout, or
                                  * one that fills the fields one by one, would otherwise pass garbage pointers here. */
     const void* l2_touch;       /* optional (round 5): l2_touch_bytes of device memory the NEXT launch on the stream reads first -- the

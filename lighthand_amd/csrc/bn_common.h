@@ -142,9 +142,21 @@ template <int EPC> __device__ __forceinline__ void fill_vec(float* dst, float v)
     for (int e = 0; e < EPC; ++e) dst[e] = v;
 }
 
+// The flat passes of fuse_fwd.hip / fuse_bwd.hip keep ONE channel chunk per thread: the chunks of a pixel must divide the
+// 256 threads of a workgroup.
+static inline bool bn_flat_chunks(int nchunk) { return (nchunk & (nchunk - 1)) == 0 && nchunk <= 256; }
+
 // streaming grid of the flat passes: one workgroup per 4 x 256 chunks, at most 2048 workgroups (re-measured in round 3:
 // 1024 / 4096 workgroups, 2 / 8 chunks per thread: 9.60-9.66 ms against 9.61, 8 chunks 9.72)
 static int flat_grid(long total) {
     const long g = (total + 1023) / 1024;
     return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
 }
+// grid of the generic (grid-stride) passes: one chunk per thread, at most 4096 workgroups
+static int generic_grid(long total) {
+    const long g = (total + 255) / 256;
+    return (int)(g > 4096 ? 4096 : g);
+}
+
+// the bytes lh_l2_touch takes from a descriptor's l2_touch / l2_touch_bytes: a 32-bit count, 0 = nothing to warm
+static inline unsigned lh_touch_bytes(const void* p, size_t bytes) { return p && bytes < (1UL << 31) ? (unsigned)bytes : 0u; }

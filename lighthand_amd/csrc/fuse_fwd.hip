@@ -124,9 +124,9 @@ struct FwdLaunch {
     FuseArgs a;
 };
 
-// pre_fin (out): bit t set when term t carries a BatchNorm finalize (lh_fuse_desc.fin) that the planned kernel does NOT run
-// itself -- the caller launches it first.
-static int plan_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, int dtype, FwdLaunch& r, int* pre_fin = nullptr) {
+// pre_fin (out): bit t set when term t carries a BatchNorm finalize (lh_fuse_desc.fin) that has not run yet: the caller
+// launches it first (no kernel of this file folds statistics).
+static int plan_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, int dtype, FwdLaunch& r, int& pre_fin) {
     LH_REQUIRE(d && out && d->nterms >= 1 && d->nterms <= 4, "lh_fuse_fwd: bad descriptor");
     const int es = lh_dtype_size(dtype);
     LH_REQUIRE(es > 0 && c % (16 / es) == 0, "lh_fuse_fwd: c %d not a multiple of the 16-byte chunk", c);
@@ -144,31 +144,28 @@ static int plan_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w, 
         }
     }
     a.nterms = d->nterms; a.relu = d->relu; a.out = (unsigned char*)out; a.mask = (unsigned char*)d->relu_mask; a.n = n; a.h = h; a.w = w; a.c = c;
-    const long total = (long)n * h * w * (c / (16 / es));
+    const int nchunk = c / (16 / es);
+    const long total = (long)n * h * w * nchunk;
     LH_REQUIRE(total < (1L << 31), "lh_fuse_fwd: tensor too large for 32-bit chunk indices");
     a.total = total;
     a.exp = bn_exp_flags() >> 2;
-    a.touch = (const unsigned char*)d->l2_touch;
-    a.touch_bytes = d->l2_touch && d->l2_touch_bytes < (1UL << 31) ? (unsigned)d->l2_touch_bytes : 0u;
-    if (!a.touch_bytes) a.touch = nullptr;
-    const int nchunk = c / (16 / es);
-    bool flat = d->nterms <= 2 && (nchunk & (nchunk - 1)) == 0 && nchunk <= 256;
+    a.touch_bytes = lh_touch_bytes(d->l2_touch, d->l2_touch_bytes);
+    a.touch = a.touch_bytes ? (const unsigned char*)d->l2_touch : nullptr;
+    bool flat = d->nterms <= 2 && bn_flat_chunks(nchunk);
     for (int t = 0; t < d->nterms; ++t) flat = flat && a.log2up[t] == 0;
-    int fin_mask = 0;
+    pre_fin = 0;
     for (int t = 0; t < d->nterms; ++t) {
         const lh_bn_finalize_call* f = d->fin[t];
         if (!f) continue;
-        LH_REQUIRE(pre_fin, "lh_fuse_fwd: this entry point does not take a descriptor with a pending finalize");
         LH_REQUIRE(f->stats && f->rows > 0 && f->count > 0 && f->c == c && f->scale == d->scale[t] && f->shift == d->shift[t] && f->scale && f->shift,
                    "lh_fuse_fwd: term %d: the pending finalize must produce this term's scale / shift (c %d vs %d)", t, f->c, c);
-        fin_mask |= 1 << t;
+        pre_fin |= 1 << t;
     }
-    if (pre_fin) *pre_fin = fin_mask;
     if (flat) {
         r.grid = flat_grid(total);      // >= 4 chunks per thread
         r.kind = d->nterms == 1 ? K_FF_FLAT1 : K_FF_FLAT2;
     } else {
-        r.grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+        r.grid = generic_grid(total);
         r.kind = K_FF_GEN;
     }
     return LH_OK;
@@ -187,44 +184,10 @@ static int bn_run(const FwdLaunch* const* L, int n, int dtype, hipStream_t s) {
     return LH_OK;
 }
 
-// Runs the records of n planned calls: position by position as multi-problem launches when every call planned the same
-// sequence of kinds (the parallel branches of an HRNet module do), else call by call.
-static int bn_run_calls(const std::vector<std::vector<FwdLaunch>>& plans, int dtype, hipStream_t s) {
-    const int n = (int)plans.size();
-    bool same = n > 1;
-    for (int i = 1; i < n && same; ++i) {
-        same = plans[i].size() == plans[0].size();
-        for (size_t k = 0; same && k < plans[0].size(); ++k) same = plans[i][k].kind == plans[0][k].kind;
-    }
-    const FwdLaunch* L[LH_MULTI_MAX];
-    if (!same) {
-        for (int i = 0; i < n; ++i)
-            for (const FwdLaunch& r : plans[i]) {
-                L[0] = &r;
-                const int rc = bn_run(L, 1, dtype, s);
-                if (rc) return rc;
-            }
-        return LH_OK;
-    }
-    for (size_t k = 0; k < plans[0].size(); ++k)
-        for (int i0 = 0; i0 < n; i0 += LH_MULTI_MAX) {
-            const int m = n - i0 < LH_MULTI_MAX ? n - i0 : LH_MULTI_MAX;
-            for (int i = 0; i < m; ++i) L[i] = &plans[i0 + i][k];
-            const int rc = bn_run(L, m, dtype, s);
-            if (rc) return rc;
-        }
-    return LH_OK;
-}
-
-// the pending finalizes of a descriptor that the planned kernel does not run itself: launched first (one multi-problem launch)
-static int run_pending_finalizes(const std::vector<lh_bn_finalize_call>& fins, void* stream) {
-    return fins.empty() ? LH_OK : lh_bn_finalize_multi(fins.data(), (int)fins.size(), stream);
-}
-
 extern "C" int lh_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, int dtype, void* stream) {
     FwdLaunch r;
     int pre = 0;
-    int rc = plan_fuse_fwd(d, out, n, h, w, c, dtype, r, &pre);
+    int rc = plan_fuse_fwd(d, out, n, h, w, c, dtype, r, pre);
     if (rc) return rc;
     lh_bn_finalize_call fins[4];                  // at most one pending finalize per term: no heap allocation on the launch path
     int nf = 0;
@@ -236,27 +199,32 @@ extern "C" int lh_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w
     return bn_run(L, 1, dtype, (hipStream_t)stream);
 }
 
+// n independent calls: their pending finalizes first, as one multi-problem launch; then the calls LH_MULTI_MAX per launch
+// when all of them planned the same kind (the parallel branches of an HRNet module do), else one by one.
 extern "C" int lh_fuse_fwd_multi(const lh_fuse_fwd_call* calls, int n, int dtype, void* stream) {
     LH_REQUIRE(calls && n >= 1, "lh_fuse_fwd_multi: bad arguments");
-    std::vector<std::vector<FwdLaunch>> plans(n, std::vector<FwdLaunch>(1));
+    std::vector<FwdLaunch> plans(n);
     std::vector<lh_bn_finalize_call> fins;
-    // the calls merge into one launch only when they plan the SAME kernel: the in-launch finalize is used when every call
-    // takes it, else none does (their finalizes then run first, as one multi-problem launch)
-    for (int pass = 0; pass < 2; ++pass) {
-        fins.clear();
-        bool same = true;
-        for (int i = 0; i < n; ++i) {
-            FwdLaunch& r = plans[i][0];
-            int pre = 0;
-            const int rc = plan_fuse_fwd(calls[i].d, calls[i].out, calls[i].n, calls[i].h, calls[i].w, calls[i].c, dtype, r, &pre);
-            if (rc) return rc;
-            for (int t = 0; t < calls[i].d->nterms; ++t)
-                if ((pre >> t) & 1) fins.push_back(*calls[i].d->fin[t]);
-            same = same && r.kind == plans[0][0].kind;
-        }
-        if (same || pass == 1) break;
+    bool same = true;
+    for (int i = 0; i < n; ++i) {
+        int pre = 0;
+        const int rc = plan_fuse_fwd(calls[i].d, calls[i].out, calls[i].n, calls[i].h, calls[i].w, calls[i].c, dtype, plans[i], pre);
+        if (rc) return rc;
+        for (int t = 0; t < calls[i].d->nterms; ++t)
+            if ((pre >> t) & 1) fins.push_back(*calls[i].d->fin[t]);
+        same = same && plans[i].kind == plans[0].kind;
     }
-    const int rc = run_pending_finalizes(fins, stream);
-    if (rc) return rc;
-    return bn_run_calls(plans, dtype, (hipStream_t)stream);
+    if (!fins.empty()) {
+        const int rc = lh_bn_finalize_multi(fins.data(), (int)fins.size(), stream);
+        if (rc) return rc;
+    }
+    const int per = same ? LH_MULTI_MAX : 1;
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const FwdLaunch* L[LH_MULTI_MAX];
+        const int m = n - i0 < per ? n - i0 : per;
+        for (int i = 0; i < m; ++i) L[i] = &plans[i0 + i];
+        const int rc = bn_run(L, m, dtype, (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    return LH_OK;
 }

@@ -197,7 +197,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, unsigned char
         }
         if constexpr (GATE) {
             // the stored value is the gradient of relu(BN(x)): gate it with the activation's sign (recomputed from x as the
-            // BN-backward kernels do, fuse_bwd.hip fuse_bwd_reduce_flat<T, MASK_X>) and take its share of the BatchNorm-backward sums
+            // BN-backward kernels do, fuse_bwd_kernel.h fuse_bwd_reduce_flat<T, MASK_X>) and take its share of the BatchNorm-backward sums
             float g[EPC], xv[EPC];
             unpack16<T>(u, g);
             unpack16<T>(gt.xd[k], xv);

@@ -17,7 +17,7 @@
 // s1 / s2: running per-lane sums of the stored values / their squares, [BM / 64][8] (STATS).
 // GATE (lh_igemm_gated, a data gradient whose output is the gradient of a = relu(BN(gx)) or of a residual tail a = relu(BN(gx) + r)):
 // the value stored is g = v * (a > 0) -- the sign recomputed from gx * scale + shift, or read from the mask bits lh_fuse_fwd stored for a
-// tail (p.gmask) -- and s1 / s2 take { g, g * (gx - mean) * invstd }: the first half of that BatchNorm's backward pass (fuse_bwd.hip
+// tail (p.gmask) -- and s1 / s2 take { g, g * (gx - mean) * invstd }: the first half of that BatchNorm's backward pass (fuse_bwd_kernel.h
 // fuse_bwd_reduce_flat) on the tile the wave holds.  cst = mean[BM], invstd[BM], scale[BM], shift[BM]; no affine on the accumulator.
 // GATE = 2: the tail's other term is a projection shortcut r = BN2(gx2): s3 takes g * (gx2 - mean2) * invstd2 (cst continues with mean2[BM],
 // invstd2[BM]); the sign comes from the mask bits (lh_igemm_gated refuses x2 without mask), so scale / shift are never fetched: their 16
