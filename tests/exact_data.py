@@ -165,13 +165,98 @@ EPILOGUE_CASES = {
 #            2^24 -- the statistics' second row is exact only on values that need no rounding.
 EPILOGUE_RANGES = {"exact": {"bf16": (8, 4, 255), "fp16": (32, 8, 2047)}, "exact_small": {"bf16": (4, 2, 64), "fp16": (4, 2, 64)}}
 
+# ---- the persistent kernels (tests/test_gpu_persistent_epilogue.py): pointwise (igemm_pw_kernel.h) and direct 3x3 (conv3x3_direct_kernel.h).
+# The compiled pointwise configurations (BM, KC, PT) = channels of the resident weight panel, padded K of the panel, 16-pixel sub-tiles a
+# wave takes per step: a copy of LH_PW_CFGS (igemm_pw_cfgs.h), held against lh_igemm_candidates by the GPU test.
+PW_CFGS = [(256, 64, 1), (128, 64, 2), (64, 64, 2), (64, 64, 4), (256, 128, 1), (128, 128, 2), (64, 128, 2),
+           (256, 256, 1), (128, 256, 1), (128, 256, 2), (64, 256, 1), (64, 256, 2), (128, 512, 1), (64, 512, 1)]
+PW_K = {64: 40, 128: 72, 256: 136, 512: 264}        # panel K -> the K run of its cases: ragged against the panel (136: kpad 192 of 256, 264: 320 of 512)
+PERSISTENT_COUT = 136      # a 256-channel panel part-filled, a second 128-channel block of 8 channels, a third 64-channel block of 8
+
+
+def _same(n, h, w, cin, taps, cout=PERSISTENT_COUT):
+    """A stride-1, same-size, dense case in the layout of EPILOGUE_CASES."""
+    return (n, h, w, cin, h, w, cout, h, w, 1, 1, 0, 0, taps)
+
+
+# Short cases: 286 pixels (ragged against 16, 32 and 64 pixels per wave step) for the pointwise kernel, 21 x 19 (ragged against 16 x 16 tiles,
+# every border) for the direct one.
+EPILOGUE_CASES.update({f"pw{k}": _same(2, 13, 11, k, [(0, 0)]) for k in PW_K.values()})
+EPILOGUE_CASES.update({f"d{c}": _same(2, 21, 19, c, _T3) for c in (32, 64)})
+EPILOGUE_SHORT = ["c72", "c136", "phase"] + [f"pw{k}" for k in PW_K.values()] + ["d32", "d64"]
+# "exact" ranges widened where the default ones leave too few accumulators that need rounding (one tap, short K): (case, precision) ->
+# (a for x and gx, a for w).  From the failures of tests/test_exact_host.py; never narrower.
+EPILOGUE_WIDER = {("pw40", "bf16"): (16, 8), ("pw40", "fp16"): (64, 16), ("pw72", "fp16"): (64, 16)}
+
+
+# Long cases: enough pixels that EVERY wave of a pointwise launch (workgroup of a direct one) walks its tile loop at least twice and some
+# three times, at any occupancy the library may pick.  Pointwise: the grid has at most G = 1024 / cb / 8 * 8 workgroups per channel block
+# (occupancy <= 4: pw_occupancy; cb channel blocks), four waves each, so 8 G + 5 wave tiles of 16 PT pixels do it; + 3 pixels keep the
+# last tile ragged.  One image of width 61; the cases of one K class are row prefixes of the class's largest (EPILOGUE_BASE).
+# Direct: at most g = 512 / cb / 8 * 8 = 168 workgroups per channel block; 2 x 197 x 211 is 2 x 13 x 14 = 364 >= 2 g + 5 tiles of 16 x 16.
+def pw_long_grid_cap(bm, cout=PERSISTENT_COUT):
+    return 1024 // ((cout + bm - 1) // bm) // 8 * 8
+
+
+def _pw_long_rows(bm, pt, wo=61):
+    need = 16 * pt * (8 * pw_long_grid_cap(bm) + 5) + 3
+    ho = (need + wo - 1) // wo
+    while (ho * wo) % 16 == 0:
+        ho += 1
+    return ho
+
+
+EPILOGUE_BASE = {}
+for _kc, _k in PW_K.items():
+    _rows = {(bm, pt): _pw_long_rows(bm, pt) for bm, kc, pt in PW_CFGS if kc == _kc}
+    EPILOGUE_CASES[f"long_pw{_k}"] = _same(1, max(_rows.values()), 61, _k, [(0, 0)])
+    for (_bm, _pt), _ho in _rows.items():
+        EPILOGUE_CASES[f"long_pw{_k}_{_bm}x{_pt}"] = _same(1, _ho, 61, _k, [(0, 0)])
+        EPILOGUE_BASE[f"long_pw{_k}_{_bm}x{_pt}"] = f"long_pw{_k}"
+EPILOGUE_CASES.update({f"long_d{c}": _same(2, 197, 211, c, _T3) for c in (32, 64)})
+EPILOGUE_LONG = [f"long_pw{k}" for k in PW_K.values()] + ["long_d32", "long_d64"]      # the cases that own data; EPILOGUE_BASE's are prefixes
+
+
+def epilogue_ranges(case, precision, flavour):
+    ax, aw, aa = EPILOGUE_RANGES[flavour][precision]
+    if flavour == "exact":
+        ax, aw = EPILOGUE_WIDER.get((case, precision), (ax, aw))
+    return ax, aw, aa
+
+
+def _epilogue_seed(case):
+    return 100 + len(case) if case in ("c72", "c136", "phase") else 1000 + sum(ord(c) * (i + 1) for i, c in enumerate(case))
+
 
 def epilogue_data(case, precision, flavour):
-    """Integer operands of an epilogue-mode case (host tensors, float32 holding values the 16-bit type holds exactly; masks uint8)."""
+    """Integer operands of an epilogue-mode case (host tensors, float32 holding values the 16-bit type holds exactly; masks uint8).
+    bias: integers; gx2, mean2, invstd2: the second BatchNorm term of lh_bn_bwd_gate (x2).  A case of EPILOGUE_BASE takes the first rows
+    of its base's image (views: nothing is drawn twice)."""
+    n, hi, wi, cin, ho, wo, cout, OH, OW = EPILOGUE_CASES[case][:9]
+    if case in EPILOGUE_LONG:                   # tens of MB each: the latest one is kept for its prefixes
+        key = (case, precision, flavour)
+        if key not in _LONG:
+            _LONG.clear()
+            _LONG[key] = _epilogue_draw(case, precision, flavour)
+        return _LONG[key]
+    if case in EPILOGUE_BASE:
+        b = epilogue_data(EPILOGUE_BASE[case], precision, flavour)
+        P = OH * OW * n
+        assert n == 1 and EPILOGUE_CASES[EPILOGUE_BASE[case]][1] >= hi
+        cut = dict(x=b["x"][:, :hi], amask=b["amask"][:P * cout // 8], gmask=b["gmask"][:P * cout // 8])
+        cut.update({k: b[k][:P] for k in ("addend", "gx", "gx2")})
+        return {**b, **cut}
+    return _epilogue_draw(case, precision, flavour)
+
+
+_LONG = {}
+
+
+def _epilogue_draw(case, precision, flavour):
     n, hi, wi, cin, ho, wo, cout, OH, OW = EPILOGUE_CASES[case][:9]
     taps = EPILOGUE_CASES[case][13]
-    ax, aw, aa = EPILOGUE_RANGES[flavour][precision]
-    g = torch.Generator().manual_seed(100 + len(case))
+    ax, aw, aa = epilogue_ranges(case, precision, flavour)
+    g = torch.Generator().manual_seed(_epilogue_seed(case))
     P = OH * OW * n
     half = torch.tensor([0.5, 1.0, 2.0])
     d = dict(x=ints((n, hi, wi, cin), ax, g), w=ints((cout, len(taps), cin), aw, g), addend=ints((P, cout), aa, g), gx=ints((P, cout), ax, g),
@@ -179,15 +264,18 @@ def epilogue_data(case, precision, flavour):
              gmask=torch.randint(0, 256, (P * cout // 8,), generator=g, dtype=torch.uint8),
              mean=ints((cout,), 4, g), shift=ints((cout,), 4, g), invstd=half[torch.randint(0, 3, (cout,), generator=g)],
              scale=half[torch.randint(0, 3, (cout,), generator=g)] * (2.0 * torch.randint(0, 2, (cout,), generator=g) - 1.0))
+    d.update(bias=ints((cout,), 16, g), gx2=ints((P, cout), ax, g), mean2=ints((cout,), 4, g), invstd2=half[torch.randint(0, 3, (cout,), generator=g)])
     return d
 
 
 def check_exact_epilogue(case, d):
     """The accumulator's precondition for an epilogue-mode case: the tap-list convolution of |x| and |w| below 2^24 everywhere; the
-    second-rounding sum |acc| + |addend| too.  Returns the largest sum of magnitudes."""
+    second-rounding sum |acc| + |addend| too, and the affine acc * scale + (bias * scale + shift) in its quantum 0.5 (|scale| <= 2).
+    Returns the largest sum of magnitudes."""
     ho, wo, taps = EPILOGUE_CASES[case][4], EPILOGUE_CASES[case][5], EPILOGUE_CASES[case][13]
-    mag = tap_conv(d["x"].abs(), d["w"].abs(), taps, ho, wo, torch.float64)
-    worst = float(mag.max()) + float(d["addend"].abs().max())
+    mag = float(tap_conv(d["x"].abs(), d["w"].abs(), taps, ho, wo, torch.float64).max())
+    affine = 2.0 * (2.0 * (mag + float(d["bias"].abs().max())) + float(d["shift"].abs().max()))
+    worst = max(mag + float(d["addend"].abs().max()), affine)
     assert worst < LIMIT, f"{case}: sum of magnitudes {worst:.0f} >= 2^24"
     return worst
 

@@ -62,25 +62,76 @@ def test_rounding_counts_agree_with_the_conversion():
 
 @pytest.mark.parametrize("flavour", list(E.EPILOGUE_RANGES))
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
-@pytest.mark.parametrize("case", list(E.EPILOGUE_CASES))
+@pytest.mark.parametrize("case", E.EPILOGUE_SHORT)
 def test_epilogue_cases_meet_the_preconditions(case, precision, flavour):
     d = E.epilogue_data(case, precision, flavour)
     dt = E.DTYPES[precision]
-    for k in ("x", "w", "addend", "gx"):
+    for k in ("x", "w", "addend", "gx", "gx2", "bias", "shift", "mean", "mean2"):
         assert torch.equal(d[k].to(dt).float(), d[k]) and torch.equal(d[k], d[k].round()), k
     assert set(d["invstd"].tolist()) <= {0.5, 1.0, 2.0} and set(d["scale"].abs().tolist()) <= {0.5, 1.0, 2.0} and bool((d["scale"] < 0).any())
+    assert set(d["invstd2"].tolist()) <= {0.5, 1.0, 2.0}
+    ax, aw, _ = E.epilogue_ranges(case, precision, flavour)
+    assert ax >= E.EPILOGUE_RANGES[flavour][precision][0] and aw >= E.EPILOGUE_RANGES[flavour][precision][1]       # widened, never narrowed
     worst = E.check_exact_epilogue(case, d)
     ho, wo, taps = E.EPILOGUE_CASES[case][4], E.EPILOGUE_CASES[case][5], E.EPILOGUE_CASES[case][13]
     acc = E.tap_conv(d["x"], d["w"], taps, ho, wo, torch.float64)
-    assert float(acc.abs().max()) + float(d["addend"].abs().max()) <= E.FP16_MAX
+    peak = float(acc.abs().max())
+    assert peak + float(d["addend"].abs().max()) <= E.FP16_MAX
+    # "bias" and "affine_relu": |acc * scale + (bias * scale + shift)| with |scale| <= 2 stays inside fp16 as well
+    assert 2.0 * (peak + float(d["bias"].abs().max())) + float(d["shift"].abs().max()) <= E.FP16_MAX
     need, ties = E.rounding_counts(acc, dt)
-    print(case, precision, flavour, f"largest sum of magnitudes {worst:.0f}, accumulators that need rounding {need}, ties {ties}")
+    biased = E.rounding_counts(acc + d["bias"].double(), dt)
+    affine = E.rounding_counts(acc * d["scale"].double() + (d["bias"] * d["scale"] + d["shift"]).double(), dt)
+    print(case, precision, flavour, f"largest sum of magnitudes {worst:.0f}, peak {peak:.0f}, accumulators that need rounding {need}, ties {ties}; "
+          f"with the bias {biased}, with the affine {affine}")
     if flavour == "exact":
         assert need >= 100 and ties >= 10
+        assert biased[0] >= 100 and biased[1] >= 10 and affine[0] >= 100 and affine[1] >= 10
     else:
         # the flavour whose statistics rows are exact: sums of squares of the (rounded) accumulators, the largest term of any mode's rows
         sq = E.expected_16(acc, dt).double().reshape(-1, acc.shape[-1]) ** 2
         assert E.check_exact_rows(sq)[0]
+
+
+def test_long_cases_walk_the_tile_loop_for_every_grid_the_library_may_pick():
+    """The arithmetic of the long cases on the shapes alone: a pointwise grid has at most G = 1024 / cb / 8 * 8 workgroups per channel
+    block (lh_pw_grid with occupancy 4), four waves each, a direct grid at most 512 / cb / 8 * 8 workgroups (lh_d3_rows with occupancy
+    2); every such unit takes at least two tiles and some take three, and the pixel count is no multiple of 16."""
+    seen = set()
+    for case, base in E.EPILOGUE_BASE.items():
+        k, (bm, pt) = int(base[len("long_pw"):]), map(int, case.rsplit("_", 1)[1].split("x"))
+        n, hi, wi, cin = E.EPILOGUE_CASES[case][:4]
+        kc = next(kc for kc, kk in E.PW_K.items() if kk == k)
+        assert (bm, kc, pt) in E.PW_CFGS and cin == k and n == 1 and hi <= E.EPILOGUE_CASES[base][1]
+        seen.add((bm, kc, pt))
+        M, units = hi * wi, 4 * E.pw_long_grid_cap(bm)
+        ntile = (M + 16 * pt - 1) // (16 * pt)
+        assert M % 16 != 0 and ntile >= 2 * units + 1 and M * E.PERSISTENT_COUT * 2 <= 70e6 and M * cin * 2 <= 70e6, (case, M, ntile, units)
+    assert seen == set(E.PW_CFGS)
+    for c in (32, 64):
+        n, hi, wi = E.EPILOGUE_CASES[f"long_d{c}"][:3]
+        assert n * ((hi + 15) // 16) * ((wi + 15) // 16) >= 2 * (512 // 3 // 8 * 8) + 1 and (n * hi * wi) % 16 != 0
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", E.EPILOGUE_LONG)
+def test_long_epilogue_cases_meet_the_preconditions(case, precision):
+    """"exact_small" data at up to 172 000 pixels: the accumulator is exact, and the sums row of every statistics slab -- plain, with the
+    masked addend, gated -- is exact in any grouping: the columns' sums of magnitudes of |stored value| <= |round16(acc)| + |addend| stay
+    below 2^24.  The prefixes of a base case (exact_data.EPILOGUE_BASE) sum fewer of the same terms."""
+    d = E.epilogue_data(case, precision, "exact_small")
+    dt = E.DTYPES[precision]
+    for k in ("x", "w", "addend", "gx", "gx2"):
+        assert torch.equal(d[k].to(dt).float(), d[k]) and torch.equal(d[k], d[k].round()), k
+    worst = E.check_exact_epilogue(case, d)
+    ho, wo, cout, taps = E.EPILOGUE_CASES[case][4], E.EPILOGUE_CASES[case][5], E.EPILOGUE_CASES[case][6], E.EPILOGUE_CASES[case][13]
+    acc = E.tap_conv(d["x"], d["w"], taps, ho, wo, torch.float64).reshape(-1, cout)
+    assert float(acc.abs().max()) + float(d["addend"].abs().max()) <= E.FP16_MAX
+    plain, plain_worst = E.check_exact_rows(E.expected_16(acc, dt).double())
+    both, both_worst = E.check_exact_rows(E.expected_16(acc, dt).double().abs() + d["addend"].double().abs())
+    print(case, precision, f"{acc.shape[0]} pixels, largest sum of magnitudes of an accumulator {worst:.0f}; largest column sum of magnitudes of "
+          f"the stored values {plain_worst:.4g}, with the addend {both_worst:.4g}")
+    assert plain and both
 
 
 def test_tap_loop_equals_conv2d_and_conv_transpose2d():

@@ -983,7 +983,7 @@ def test_gated_pool_backward_equals_plain_backward_then_gate(shape, dtype):
     assert torch.allclose(got[1], (g64 * xhat).sum((0, 1, 2)), rtol=2e-3, atol=2e-2)
 
 
-@pytest.mark.parametrize("kernel", ["pw", "tiled"])
+@pytest.mark.parametrize("kernel", ["pw", "tiled", "direct"])
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
 def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, precision, forced_plans, monkeypatch):
     """Round 6 (verdict item 2): lh_igemm_gated on the persistent pointwise kernel, and for residual tails a = relu(BN(x) + r)
@@ -993,11 +993,15 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
     is the FIRST writer of its gradient and takes the second tail's identity gradient as a masked addend, and that tail itself.  With the gate
     that data gradient stores g = dz * mask and the partial sums of BN-backward; the tail's backward runs without its reduce pass.  Gate on /
     off: the gated launches appear (the tail's AND the single-term nodes' in front of a 1x1 data gradient), every gradient agrees to the
-    rounding of the 16-bit activation gradients, and with PyTorch within the precision's tolerance."""
+    rounding of the 16-bit activation gradients, and with PyTorch within the precision's tolerance.
+    kernel "direct": the blocks are bottlenecks -- a 3x3 / stride 1 / padding 1 convolution at 64 channels between the two 1x1 ones --, so the
+    gradient of the first 1x1 convolution's activation is first written by the data gradient of a 3x3 convolution: the gated direct kernel
+    (conv3x3_direct_kernel<T, 64, true, true>), which the tuning database selects for the benchmark plan."""
     import copy
     from lighthand_amd import _lib
     from lighthand_amd.module import HipModule
     C4, Cq, n, h, w = 128, 64, 3, 12, 20
+    mid = kernel == "direct"
 
     class Net(HipModule):
         def __init__(self):
@@ -1006,6 +1010,8 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
             for k in (0, 1, 2):
                 setattr(self, f"a{k}", nn.Conv2d(C4, Cq, 1, bias=False)); setattr(self, f"an{k}", nn.BatchNorm2d(Cq))
                 setattr(self, f"b{k}", nn.Conv2d(Cq, C4, 1, bias=False)); setattr(self, f"bn{k}", nn.BatchNorm2d(C4))
+                if mid:
+                    setattr(self, f"m{k}", nn.Conv2d(Cq, Cq, 3, 1, 1, bias=False)); setattr(self, f"mn{k}", nn.BatchNorm2d(Cq))
             self.p = nn.Conv2d(C4, C4, 1, bias=False); self.pn = nn.BatchNorm2d(C4)       # block 0: projection shortcut (pose_resnet.py:93-94)
             self.out = nn.Conv2d(C4, 8, 1, bias=False)
 
@@ -1014,6 +1020,8 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
             for k in (0, 1, 2):
                 r = (gb.conv(z, "p", 1, 1, 0), "pn") if k == 0 else z
                 a = gb.fuse([(gb.conv(z, f"a{k}", 1, 1, 0), f"an{k}")])
+                if mid:
+                    a = gb.fuse([(gb.conv(a, f"m{k}", 3, 1, 1), f"mn{k}")])
                 z = gb.fuse([(gb.conv(a, f"b{k}", 1, 1, 0), f"bn{k}"), r])
             gb.output(gb.conv(z, "out", 1, 1, 0))
 
@@ -1022,6 +1030,8 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
             for k in (0, 1, 2):
                 r = self.pn(self.p(z)) if k == 0 else z
                 a = F.relu(getattr(self, f"an{k}")(getattr(self, f"a{k}")(z)))
+                if mid:
+                    a = F.relu(getattr(self, f"mn{k}")(getattr(self, f"m{k}")(a)))
                 z = F.relu(getattr(self, f"bn{k}")(getattr(self, f"b{k}")(a)) + r)
             return self.out(z)
 
@@ -1035,6 +1045,8 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
     x = torch.randn(n, 16, h, w).to(td).float()
     if kernel == "pw":
         forced_plans.force_cfg = lambda cands: max([c for c in cands if c[2] == 1] or cands[:1], key=lambda c: (c[2] == 1, c[0], c[1]))
+    elif kernel == "direct":            # the direct 3x3 kernel where it is offered, the largest pointwise configuration elsewhere
+        forced_plans.force_cfg = lambda cands: max([c for c in cands if c[2] in (1, 100)] or cands[:1], key=lambda c: (c[2] == 100, c[2] == 1, c[0], c[1]))
     else:
         forced_plans.force_cfg = lambda cands: next(c for c in cands if c[2] not in (1, 100))
     res, gated = {}, {}
@@ -1051,6 +1063,9 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
         # sum g and sum g * xhat of what was stored (fp64 on the host), for one and for two BatchNorm terms
         gates = [k for k in plan.keep if isinstance(k, _lib.BnBwdGate)]
         assert len(gates) == len(calls)
+        names = [nm for _, c, nm, _, _ in plan.profile_meta if c in calls]
+        if mid and gate == "1":         # the data gradients of m0 / m1 / m2 run the gated instantiation of the direct kernel
+            assert sum(nm.startswith("conv3x3_direct_kernel<") and nm.endswith("true, true>") for nm in names) == 3, names
         hip = C.CDLL("libamdhip64.so")
 
         def dev(ptr, numel, dtype):
@@ -1084,7 +1099,10 @@ def test_bn_backward_gate_on_the_pointwise_kernel_and_on_residual_tails(kernel, 
     # gated: the tails (mask bits) -- block 0's has a projection shortcut (two BatchNorm terms: the pointwise kernel only), block 1's the
     # next tail as its second consumer, block 2's the output convolution as its only one -- and the single-term nodes an0 / an1 / an2
     # (their only consumer is a 1x1 data gradient)
-    assert gated["1"] == ((6, 3) if kernel == "pw" else (5, 2)), gated
+    # "direct": those six and the single-term nodes mn0 / mn1 / mn2 (the 3x3 convolutions' activations, whose only consumer is a 1x1 data
+    # gradient); an0 / an1 / an2 are now gated by the data gradients of the 3x3 convolutions, on the direct kernel
+    print(f"{kernel} {precision}: gated launches {gated['1']}")
+    assert gated["1"] == {"pw": (6, 3), "tiled": (5, 2), "direct": (9, 3)}[kernel], gated
     a, b = res["0"], res["1"]
     assert torch.equal(a[0], b[0])
     assert rel_err(a[1], b[1]) < 2e-2, rel_err(a[1], b[1])
