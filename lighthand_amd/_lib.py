@@ -16,6 +16,13 @@ class LightHandError(RuntimeError):
     pass
 
 
+def conv_kind(depth):
+    """The kernel that lh_igemm_desc.cfg[2] (the third value of lh_igemm_config / lh_igemm_candidates) names -- lh_conv_kind of
+    csrc/igemm_args.h: 'staged' | 'pointwise' | 'tiled' | 'dense' | 'direct', or None for a code no kernel carries."""
+    return ("staged" if depth == 0 else "pointwise" if depth == 1 else "tiled" if 2 <= depth < 10 else "dense" if 20 <= depth < 30
+            else "direct" if depth == 100 else None)
+
+
 class IgemmDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("hi", C.c_int), ("wi", C.c_int), ("in_pix_stride", C.c_int),
                 ("k_run", C.c_int), ("ho", C.c_int), ("wo", C.c_int), ("sh", C.c_int), ("sw", C.c_int),

@@ -44,12 +44,13 @@ class BnGate:
         rounds 4-6: beyond it the epilogue's read of raw costs a tile-per-workgroup launch more than the reduce pass it replaces), the
         persistent kernels (pointwise, direct 3x3: streams of independent waves, the extra read rides with the others) up to
         LH_BN_GATE_PW_MAX_MB; tails up to LH_BN_GATE_TAIL_MAX_MB on either."""
-        pw, tiled = cfg[2] in (1, 100), (2 <= cfg[2] < 10 or 20 <= cfg[2] < 40)
+        kernel = _lib.conv_kind(cfg[2])
+        pw, tiled = kernel in ("pointwise", "direct"), kernel in ("tiled", "dense")
         opt, mb = self.opt, nbytes / (1 << 20)
         if not (tiled or (pw and opt.bn_gate_pw)):
             return False
         if kind == "mask2":                # two BatchNorm terms (a projection shortcut): the pointwise kernel only
-            return cfg[2] == 1 and opt.bn_gate_tail2 and mb <= opt.bn_gate_tail_max_mb
+            return kernel == "pointwise" and opt.bn_gate_tail2 and mb <= opt.bn_gate_tail_max_mb
         if kind == "mask":
             return mb <= (opt.bn_gate_tail_max_mb if pw else min(opt.bn_gate_tail_max_mb, opt.bn_gate_tiled_tail_max_mb))
         return mb <= (opt.bn_gate_pw_max_mb if pw else opt.bn_gate_max_mb)

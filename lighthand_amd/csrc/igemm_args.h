@@ -1,6 +1,13 @@
-// Kernel-argument block shared by the two implicit-GEMM kernels (igemm.hip, igemm_ring.hip).
+// Shared by the host layer of the forward / data-gradient convolution and its five kernels: the kernel-argument block (IgemmArgs), a
+// kernel configuration (RingCfg) with the ONE rule that says which kernel a configuration runs on (lh_conv_kind), a resolved launch
+// (ConvPlan), and what the layer's files offer each other:
+//   igemm.hip         the launching entry points (lh_igemm, _gated, _multi, _phases, _phases_head): validate, fill, attach, launch
+//   igemm_plan.hip    host arithmetic only: configuration tables, what fits a launch, default, resolve, candidates, slab rows, the queries
+//   igemm_ring.hip    device pages and the dispatch into the per-type instantiation files of the LDS-DMA, pointwise and direct kernels
+//   igemm_staged.hip  the register-staged fallback kernel (igemm_staged_kernel.h), its tile choice and launch
 #pragma once
 #include "common.h"
+#include "igemm_ring_cfgs.h"
 
 struct IgemmArgs {
     const unsigned char* in;
@@ -49,12 +56,37 @@ struct IgemmArgs {
     signed char dw[64];
 };
 
-// One configuration of the LDS-DMA kernel: tile (output channels x pixels), ring depth, K bytes per stage
-// (igemm_ring_kernel.h).  depth == 100 selects the direct 3x3 kernel (conv3x3_direct_kernel.h): bm = 64, bp = 256 (a 16 x 16
-// output tile), kb = input channels per tap (32 | 64);  depth == 1 selects the persistent pointwise kernel (igemm_pw_kernel.h): bm = channels of the
-// resident weight panel, bp = pixels a wave takes per step (16 * PT), kb = padded K of the panel in elements.
+// One kernel configuration = lh_igemm_desc.cfg[0..3].  `depth` names the kernel (lh_conv_kind):
+//   0        register-staged fallback (igemm_staged_kernel.h): bm x bp tile, kb = 0
+//   1        persistent pointwise kernel (igemm_pw_kernel.h): bm = channels of the resident weight panel, bp = pixels a wave takes per
+//            step (16 * PT), kb = padded K of the panel in elements
+//   2..9     LDS-DMA kernel (igemm_ring_kernel.h): tile (output channels x pixels), ring depth, kb = K bytes per stage
+//   20..29   its dense-wave forms: ring depth + LH_DENSE_DEPTH (igemm_ring_cfgs.h)
+//   100      direct 3x3 kernel (conv3x3_direct_kernel.h): bm = 64, bp = 256 (a 16 x 16 output tile), kb = input channels per tap (32 | 64)
+// No kernel carries another code: lh_igemm_config refuses it.
 struct RingCfg {
     int bm, bp, depth, kb;
+};
+
+enum LhConvKind { LH_CONV_NONE, LH_CONV_STAGED, LH_CONV_POINTWISE, LH_CONV_TILED, LH_CONV_DENSE, LH_CONV_DIRECT };
+enum { LH_POINTWISE_DEPTH = 1, LH_DIRECT_DEPTH = 100 };
+
+static inline LhConvKind lh_conv_kind(int depth) {
+    return depth == 0 ? LH_CONV_STAGED : depth == LH_POINTWISE_DEPTH ? LH_CONV_POINTWISE : depth >= 2 && depth < 10 ? LH_CONV_TILED
+         : depth >= LH_DENSE_DEPTH && depth < LH_DENSE_DEPTH + 10 ? LH_CONV_DENSE : depth == LH_DIRECT_DEPTH ? LH_CONV_DIRECT : LH_CONV_NONE;
+}
+// ring depth of a tiled or dense-wave configuration
+static inline int lh_ring_depth(const RingCfg& c) { return lh_conv_kind(c.depth) == LH_CONV_DENSE ? c.depth - LH_DENSE_DEPTH : c.depth; }
+// pointwise and direct: one workgroup walks many tiles (single launches only; statistics rows per workgroup, not per pixel tile)
+static inline bool lh_kind_persistent(LhConvKind k) { return k == LH_CONV_POINTWISE || k == LH_CONV_DIRECT; }
+// kernels with a BatchNorm-backward gate (lh_igemm_gated, 16-bit types), and the one that gates two BatchNorm terms
+static inline bool lh_kind_gated(LhConvKind k) { return k != LH_CONV_STAGED && k != LH_CONV_NONE; }
+static inline bool lh_kind_gates_two(LhConvKind k) { return k == LH_CONV_POINTWISE; }
+
+// A resolved launch: the kernel and its configuration (lh_conv_plan)
+struct ConvPlan {
+    LhConvKind kind;
+    RingCfg cfg;
 };
 
 // workgroups per channel block of a pointwise launch: every CU holds `occ` workgroups for the whole launch (occ = what the
@@ -75,17 +107,17 @@ static inline void lh_pw_grid(int bm, int kc, int pt, long M, int cout, int occ,
 }
 
 
-// igemm_ring.hip
-bool lh_ring_supported(const lh_igemm_desc* d, int dtype);
+// igemm_plan.hip
 bool lh_tap_grid(const lh_igemm_desc* d, int* tw, int* dh0, int* dhs, int* dw0, int* dws);
-int lh_ring_resolve(const lh_igemm_desc* d, int dtype, RingCfg* out);
-void lh_ring_default_cfg(const lh_igemm_desc* d, int dtype, RingCfg* out);
-int lh_ring_candidates(const lh_igemm_desc* d, int dtype, int* out, int max);
-int lh_igemm_ring_launch(const IgemmArgs& a, const RingCfg& c, int dtype, hipStream_t s);
+bool lh_ring_supported(const lh_igemm_desc* d, int dtype);
+int lh_conv_plan(const lh_igemm_desc* d, int dtype, ConvPlan* out);     // supported -> resolve (explicit cfg validated, else the default); else the staged tile
+int lh_pw_occupancy(const RingCfg& c, int dtype, int mode);      // mode: 0 plain, 1 statistics, 2 / 3 BatchNorm-backward gate of one / two terms
+bool lh_phases_ok(const lh_igemm_desc* const* descs, int nphase);
+int lh_phase_lead(const lh_igemm_desc* const* descs, int nphase);
+// igemm_staged.hip
+void lh_staged_tile(const lh_igemm_desc* d, int dtype, RingCfg* out);
+int lh_staged_launch(const IgemmArgs& a, const RingCfg& c, int dtype, hipStream_t s);
+// igemm_ring.hip
+int lh_conv_launch(const IgemmArgs& a, const ConvPlan& p, int dtype, hipStream_t s);
 template <typename A> struct LhMulti;
 int lh_igemm_ring_multi_launch(LhMulti<IgemmArgs>& m, const RingCfg& c, int dtype, hipStream_t s);
-bool lh_pw_supported(const lh_igemm_desc* d, int dtype);
-bool lh_d3_supported(const lh_igemm_desc* d, int dtype);
-int lh_d3_rows(const lh_igemm_desc* d);
-int lh_pw_rows(const lh_igemm_desc* d, const RingCfg& c, int dtype, int gate = 0);
-int lh_pw_occupancy(const RingCfg& c, int dtype, int mode);      // mode: 0 plain, 1 statistics, 2 / 3 BatchNorm-backward gate of one / two terms

@@ -6,7 +6,7 @@
 // ds_read_b64_tr_b16 from row-major [pixel][channel] LDS images (16-bit types); the fp32
 // path reads its one-k-per-lane fragments with plain ds_read_b32.
 //  * tile BO x BI output, K step = 32 pixels (16-bit) / 16 pixels (fp32), 4 waves,
-//    double-buffered register staging with one barrier per step (as igemm.hip);
+//    double-buffered register staging with one barrier per step (as igemm_staged_kernel.h);
 //  * LDS rows are padded so that the 8 pixel rows a half-wave touches per transposed read
 //    land on distinct bank groups; the k order inside a step is {4g..4g+3, 16+4g..16+4g+3}
 //    for lane group g -- the same permutation for both operands, so the sum is unchanged;

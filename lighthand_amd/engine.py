@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import FuseBwdDesc, FuseDesc, IgemmDesc, check
+from ._lib import FuseBwdDesc, FuseDesc, IgemmDesc, check, conv_kind
 from .batch_groups import BatchGroups
 from .bn_gate import BnGate
 from .graph import BN_EPS, BN_MOMENTUM, PRECISIONS, Act, GraphBuilder, _Call, _Marker, _desc, _ptr, _taps_array  # noqa: F401 (re-exported)
@@ -269,17 +269,18 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             cfg = (C.c_int * 5)()
             check(self.lib.lh_igemm_config(C.byref(d), self.dt, cfg), "lh_igemm_config")
             bm, bp, depth, kb = cfg[0], cfg[1], cfg[2], cfg[3]
-            if depth == 1:
+            kind = conv_kind(depth)
+            if kind == "pointwise":
                 return f"igemm_pw_kernel<{t}, {bm}, {kb}, {bp // 16}, {'true' if stats else 'false'}>"
-            if depth == 100:
+            if kind == "direct":
                 return f"conv3x3_direct_kernel<{t}, {kb}, {'true' if stats else 'false'}>"
             wc, wp = {(256, 256): (2, 4), (128, 256): (2, 2), (256, 128): (4, 2), (128, 128): (2, 2), (128, 64): (4, 1), (64, 128): (1, 4), (64, 64): (2, 2)}[(bm, bp)]
-            if 20 <= depth < 30:                # the dense-wave forms (eight waves on the 4-wave tiles, igemm_ring_cfgs.h)
+            if kind == "dense":                 # eight waves on the 4-wave tiles; the code is ring depth + 20 (igemm_ring_cfgs.h)
                 wc, wp = {(128, 128): (2, 4), (128, 64): (4, 2), (64, 128): (2, 4), (64, 64): (2, 4), (128, 256): (2, 4), (256, 128): (4, 2)}[(bm, bp)]
                 depth -= 20
-            if depth:
-                return f"igemm_ring_kernel<{t}, {bm}, {bp}, {wc}, {wp}, {depth}, {kb}>"
-            return f"igemm_kernel<{t}, {bm}, {bp}, {wc}, {wp}>"
+            if kind == "staged":
+                return f"igemm_kernel<{t}, {bm}, {bp}, {wc}, {wp}>"
+            return f"igemm_ring_kernel<{t}, {bm}, {bp}, {wc}, {wp}, {depth}, {kb}>"
         r = C.c_int(0)
         check(self.lib.lh_wgrad_tile(C.byref(d), wgrad[0], wgrad[1], self.dt, C.byref(a), C.byref(b), C.byref(c), C.byref(r)), "lh_wgrad_tile")
         wo, wi = {(256, 256): (2, 4), (128, 128): (2, 2), (128, 64): (4, 1), (64, 128): (1, 4), (64, 64): (2, 2)}[(a.value, b.value)]
@@ -463,7 +464,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
                 if nxt is None or nxt.fn is not lib.lh_igemm or nxt.slane != c.slane or nxt.mtag is not None:
                     continue
                 d = nxt.keep
-                if (d.cfg[2] in (1, 100) and not touch_all) or not nxt.args[ig["pack"]]:    # pointwise / direct kernels fetch their panel once per workgroup
+                if (conv_kind(d.cfg[2]) in ("pointwise", "direct") and not touch_all) or not nxt.args[ig["pack"]]:    # pointwise / direct kernels fetch their panel once per workgroup
                     continue
                 kstep = 128 // self.es
                 nbytes = (d.cout + 127) // 128 * 128 * d.ntaps * ((d.k_run + kstep - 1) // kstep * kstep) * self.es

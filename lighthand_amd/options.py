@@ -19,7 +19,7 @@ and the switches the C library reads with getenv() itself:
   LH_POOL_BLOCK        pool.hip: 0 runs the gated max-pool backward on the pixel-per-thread kernel.
   LH_BN_EXP            bn_common.h: bit flags of the cache-policy / traversal experiments of the streaming BatchNorm passes.
   LH_FOLD_IN_APPLY     fuse_bwd_plan.h: set (to anything), the backward apply pass no longer folds the partial sums itself.
-  LH_DENSE_TILES       igemm_ring.hip: 0 withdraws the dense tile configurations from the candidates.
+  LH_DENSE_TILES       igemm_plan.hip: 0 withdraws the dense tile configurations from the candidates.
   LH_PW_OCC            igemm_pw_kernel.h: cap on the pointwise kernel's workgroups per compute unit (default 4).
   LH_WGRAD_TABLE_XCD   wgrad_table.hip: 0 orders a table's work items longest first without dealing them over the XCDs.
 """

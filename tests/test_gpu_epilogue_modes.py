@@ -8,7 +8,7 @@ same descriptor.
 
 Shapes: batch 2, 3x3 stride 1, 40 -> 72 channels at 13 x 11 (286 pixels: a ragged second 256-pixel tile; 72 channels fill neither a 128 nor
 a 256 tile).  The library refuses the 256-channel tile for 72 channels (weight packs are padded to 128 rows: one block, a 256-row tile would
-read past it -- cfg_safe, igemm_ring.hip), so that shape runs on the other three forms, the refusal is asserted, and the same convolution
+read past it -- cfg_safe, igemm_plan.hip), so that shape runs on the other three forms, the refusal is asserted, and the same convolution
 with 136 channels (two blocks; still fills neither tile) runs on all four.  The third case is one sub-pixel phase of a stride-2 transposed
 convolution: 2 x 2 taps, output pixel (2a + 1, 2b) of an 18 x 14 image -- the epilogue's strided (non-dense) placement; the pixels of the
 other phases keep what the buffer held.

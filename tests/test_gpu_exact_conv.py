@@ -22,27 +22,25 @@ pytestmark = pytest.mark.gpu
 # What a case must be offered AND run on (16-bit precisions; fp32 has the tiled kernel only), by case index of E.CONV_CASES: the families
 # of the forward launch, those of the data-gradient launch (each direction has its own candidate list and is asserted on its own), and
 # the least number of pixel splits among the weight-gradient plans.  The data gradient of 128 -> 256 has 128 output channels: one
-# 128-row block of the weight pack, so the 256-row tile is not legal there (cfg_safe, igemm_ring.hip).
+# 128-row block of the weight pack, so the 256-row tile is not legal there (cfg_safe, igemm_plan.hip).
 _NEEDS = {2: ({"pointwise"}, {"pointwise"}, 1), 5: ({"direct"}, {"direct"}, 1), 6: ({"direct"}, {"direct"}, 1), 8: ({"256x256"}, set(), 1),
           9: ({"pointwise"}, {"pointwise"}, 1), 11: (set(), set(), 3)}
 
 
 def _family(c):
-    if c[2] == 1:
-        return "pointwise"
-    if c[2] == 100:
-        return "direct"
-    return "dense" if 20 <= c[2] < 30 else "tiled"
+    from lighthand_amd._lib import conv_kind
+    return conv_kind(c[2])
 
 
 def _kernel_of(c):
     """(start, middle, end) of what Plan._kname prints for a forced configuration (engine.py) -- kernel, tile, ring depth and stage bytes:
     the library resolved the launch to exactly this configuration."""
-    if c[2] == 1:
+    kind = _family(c)
+    if kind == "pointwise":
         return "igemm_pw_kernel<", f" {c[0]}, {c[3]}, {c[1] // 16},", ">"
-    if c[2] == 100:
+    if kind == "direct":
         return "conv3x3_direct_kernel<", f" {c[3]},", ">"
-    return "igemm_ring_kernel<", f" {c[0]}, {c[1]},", f", {c[2] - 20 if 20 <= c[2] < 30 else c[2]}, {c[3]}>"
+    return "igemm_ring_kernel<", f" {c[0]}, {c[1]},", f", {c[2] - 20 if kind == 'dense' else c[2]}, {c[3]}>"
 
 
 def _wgrad_plans_of(plan):

@@ -75,5 +75,5 @@ for cfg in cands:
 res.sort()
 print(f"1x1 {cin}->{cout} s{stride} on {n}x{h}x{w} stats={stats}: {flops / 1e9:.2f} GFLOP, {nbytes / 1e6:.1f} MB (roof {nbytes / 6.3e6:.1f} us @6.3 TB/s)  lib={os.environ.get('LH_LIB_PATH', 'default')}")
 for tcold, twarm, cfg in res:
-    kind = "pw  " if cfg[2] == 1 else "ring"
+    kind = "pw  " if _lib.conv_kind(cfg[2]) == "pointwise" else "ring"
     print(f"   {kind} {str(cfg):22s} cold {tcold:7.1f} us   back-to-back {twarm:7.1f} us")
