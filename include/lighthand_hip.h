@@ -427,6 +427,12 @@ int lh_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, in
  * that do not plan the same kernels (e.g. an upsampled term beside plain ones) run one by one: always legal, same results. */
 typedef struct { const lh_fuse_desc* d; void* out; int n, h, w, c; } lh_fuse_fwd_call;
 int lh_fuse_fwd_multi(const lh_fuse_fwd_call* calls, int n, int dtype, void* stream);
+/* The planned route of a lh_fuse_fwd call with the same arguments, without launching anything (host arithmetic, no device
+ * needed): *kind = the kernel (LH_FF_*), *grid = its workgroups.  For tests and tools that must know which kernel a shape takes. */
+enum { LH_FF_GEN = 0,           /* any terms: up to four, upsampled ones, any chunk count */
+       LH_FF_FLAT1 = 1,         /* one term, no upsampling, a power-of-two number <= 256 of 16-byte chunks per pixel */
+       LH_FF_FLAT2 = 2 };       /* two such terms */
+int lh_fuse_fwd_plan(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, int dtype, int* kind, int* grid);
 
 /* Backward of lh_fuse_fwd, two launches per BN term:
  *  reduce: sums[t] = { sum g_t, sum g_t * xhat_t } with g = dout * (out > 0), g_t = g summed over
@@ -466,6 +472,22 @@ int lh_fuse_bwd(const lh_fuse_bwd_desc* d, int n, int h, int w, int c, void* wor
 /* n independent nodes, each with its OWN workspace: their reduce / coefficient-fold / apply kernels as three launches. */
 typedef struct { const lh_fuse_bwd_desc* d; int n, h, w, c; void* workspace; } lh_fuse_bwd_call;
 int lh_fuse_bwd_multi(const lh_fuse_bwd_call* calls, int n, int dtype, void* stream);
+/* The launch records a lh_fuse_bwd call with the same arguments consists of, in recorded order, without launching anything (host
+ * arithmetic, no device needed; the pointers of the descriptor and the workspace are only tested for NULL).  Returns the number of
+ * records (< 0: LH_ERR_*) and fills the first `cap` of them: kinds[i] = LH_FB_*, grids[i] = workgroups (a reduce record: its strips =
+ * the rows of the term's partial-sum slab; an LH_FB_APPLY2 record is one kind and one grid for both terms), fold_rows[i] = the slab
+ * rows the record's term folds inside its apply pass (0: a separate LH_FB_COEF record folds them; always 0 for LH_FB_COEF and
+ * LH_FB_APPLY2 records -- the reduce records before an LH_FB_APPLY2 tell).  kinds / grids / fold_rows may be NULL. */
+enum { LH_FB_REDUCE_GEN = 0,    /* partial sums of g, g * xhat: any chunk count, upsampled terms */
+       LH_FB_REDUCE_FLAT = 1,   /* the same for l = 0 and a power-of-two number <= 256 of chunks per pixel */
+       LH_FB_REDUCE_FLAT_X = 2, /* ... with the ReLU gate recomputed from x * scale + shift */
+       LH_FB_COEF = 3,          /* coefficient fold of a slab: grid c / 16, or c / 4 from 256 rows on */
+       LH_FB_APPLY_GEN = 4,
+       LH_FB_APPLY_FLAT = 5,
+       LH_FB_APPLY_FLAT_X = 6,
+       LH_FB_APPLY2 = 7 };      /* both gradients of a two-term node without upsampling in one pass */
+int lh_fuse_bwd_plan(const lh_fuse_bwd_desc* d, int n, int h, int w, int c, void* workspace, int dtype, int* kinds, int* grids,
+                     int* fold_rows, int cap);
 
 /* The inference stem of SimpleBaseline-ResNet as ONE launch: maxpool(relu(bn1(conv1(x)))) -- conv1 = nn.Conv2d(3, 64, 7, 2, 3),
  * bn1 in eval mode (running statistics folded into scale / shift), nn.MaxPool2d(3, 2, 1): src/modeling/simplebaseline/

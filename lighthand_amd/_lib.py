@@ -10,6 +10,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LH_LIB_PATH") or os.path.join(_HERE, "liblighthand_hip.so")   # override: kernel experiments only
 
 LH_F32, LH_BF16, LH_F16 = 0, 1, 2
+# launch-record kinds of lh_fuse_bwd_plan / lh_fuse_fwd_plan (LH_FB_* / LH_FF_* of the header)
+LH_FB_REDUCE_GEN, LH_FB_REDUCE_FLAT, LH_FB_REDUCE_FLAT_X, LH_FB_COEF, LH_FB_APPLY_GEN, LH_FB_APPLY_FLAT, LH_FB_APPLY_FLAT_X, LH_FB_APPLY2 = range(8)
+LH_FF_GEN, LH_FF_FLAT1, LH_FF_FLAT2 = range(3)
 
 
 class LightHandError(RuntimeError):
@@ -163,9 +166,11 @@ SIGNATURES = {
     "lh_bn_eval_affine": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P]),
     "lh_fuse_fwd": (_I, [C.POINTER(FuseDesc), _P, _I, _I, _I, _I, _I, _P]),
     "lh_fuse_fwd_multi": (_I, [C.POINTER(FuseFwdCall), _I, _I, _P]),
+    "lh_fuse_fwd_plan": (_I, [C.POINTER(FuseDesc), _P, _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "lh_fuse_bwd_multi": (_I, [C.POINTER(FuseBwdCall), _I, _I, _P]),
     "lh_fuse_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "lh_fuse_bwd": (_I, [C.POINTER(FuseBwdDesc), _I, _I, _I, _I, _P, _I, _P]),
+    "lh_fuse_bwd_plan": (_I, [C.POINTER(FuseBwdDesc), _I, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I]),
     "lh_stem_pool": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "lh_bottleneck_infer": (_I, [C.POINTER(BottleneckDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "lh_stem_conv_rows": (_I, [_I, _I, _I]),

@@ -121,6 +121,30 @@ extern "C" int lh_fuse_bwd(const lh_fuse_bwd_desc* d, int n, int h, int w, int c
     return bn_run_phases(plans, dtype, (hipStream_t)stream);
 }
 
+// the published kind values (include/lighthand_hip.h) are the planner's
+static_assert(LH_FB_REDUCE_GEN == K_FB_REDUCE_GEN, "LH_FB_REDUCE_GEN");
+static_assert(LH_FB_REDUCE_FLAT == K_FB_REDUCE_FLAT, "LH_FB_REDUCE_FLAT");
+static_assert(LH_FB_REDUCE_FLAT_X == K_FB_REDUCE_FLAT_X, "LH_FB_REDUCE_FLAT_X");
+static_assert(LH_FB_COEF == K_FB_COEF, "LH_FB_COEF");
+static_assert(LH_FB_APPLY_GEN == K_FB_APPLY_GEN, "LH_FB_APPLY_GEN");
+static_assert(LH_FB_APPLY_FLAT == K_FB_APPLY_FLAT, "LH_FB_APPLY_FLAT");
+static_assert(LH_FB_APPLY_FLAT_X == K_FB_APPLY_FLAT_X, "LH_FB_APPLY_FLAT_X");
+static_assert(LH_FB_APPLY2 == K_FB_APPLY2, "LH_FB_APPLY2");
+
+// What lh_fuse_bwd would launch for these arguments, in recorded order; nothing is launched (host arithmetic only).
+extern "C" int lh_fuse_bwd_plan(const lh_fuse_bwd_desc* d, int n, int h, int w, int c, void* workspace, int dtype, int* kinds,
+                                int* grids, int* fold_rows, int cap) {
+    std::vector<BwdLaunch> v;
+    const int rc = plan_fuse_bwd(d, n, h, w, c, workspace, dtype, v);
+    if (rc) return rc;
+    for (int i = 0; i < (int)v.size() && i < cap; ++i) {
+        if (kinds) kinds[i] = v[i].kind;
+        if (grids) grids[i] = v[i].grid;
+        if (fold_rows) fold_rows[i] = v[i].kind == K_FB_COEF || v[i].kind == K_FB_APPLY2 ? 0 : v[i].fb.fold_rows;
+    }
+    return (int)v.size();
+}
+
 // n independent nodes (each with its OWN workspace): reduce / coefficient fold / apply of all of them as three launches.
 extern "C" int lh_fuse_bwd_multi(const lh_fuse_bwd_call* calls, int n, int dtype, void* stream) {
     LH_REQUIRE(calls && n >= 1, "lh_fuse_bwd_multi: bad arguments");

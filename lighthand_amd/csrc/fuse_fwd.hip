@@ -199,6 +199,22 @@ extern "C" int lh_fuse_fwd(const lh_fuse_desc* d, void* out, int n, int h, int w
     return bn_run(L, 1, dtype, (hipStream_t)stream);
 }
 
+// the published kind values (include/lighthand_hip.h) are the planner's
+static_assert(LH_FF_GEN == K_FF_GEN, "LH_FF_GEN");
+static_assert(LH_FF_FLAT1 == K_FF_FLAT1, "LH_FF_FLAT1");
+static_assert(LH_FF_FLAT2 == K_FF_FLAT2, "LH_FF_FLAT2");
+
+// The kernel lh_fuse_fwd would launch for these arguments and its grid; nothing is launched (host arithmetic only).
+extern "C" int lh_fuse_fwd_plan(const lh_fuse_desc* d, void* out, int n, int h, int w, int c, int dtype, int* kind, int* grid) {
+    FwdLaunch r;
+    int pre = 0;
+    const int rc = plan_fuse_fwd(d, out, n, h, w, c, dtype, r, pre);
+    if (rc) return rc;
+    if (kind) *kind = r.kind;
+    if (grid) *grid = r.grid;
+    return LH_OK;
+}
+
 // n independent calls: their pending finalizes first, as one multi-problem launch; then the calls LH_MULTI_MAX per launch
 // when all of them planned the same kind (the parallel branches of an HRNet module do), else one by one.
 extern "C" int lh_fuse_fwd_multi(const lh_fuse_fwd_call* calls, int n, int dtype, void* stream) {

@@ -5,7 +5,9 @@ stored 16-bit value must equal ONE round-to-nearest-even of the exact result: th
 
 The bound is derived, not measured: |any partial sum| <= sum of the magnitudes of its terms <= the same convolution of |x|, |w|, |dy|
 (check_exact computes exactly that, in fp64, on the reference alone).  The reference is torch.nn.functional in float64 on the CPU: sums of
-integers below 2^53 are exact there in any order too."""
+integers below 2^53 are exact there in any order too.
+
+The second half of the file ("The BatchNorm grid") does the same for the BatchNorm / fused elementwise / pooling kernels."""
 import torch
 import torch.nn.functional as F
 
@@ -352,3 +354,348 @@ def chain_reference(x, params, dy, precision):
             grads[name + ".bias"] = r["db"]
         gcur, qg = r16(r["dx"]), qg * 2.0 ** -sh
     return acts[-1], gcur, grads, worst[::-1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The BatchNorm grid (tests/test_gpu_exact_bn.py): data on which the BatchNorm statistics, the fused affine / upsample / ReLU op (forward and
+# backward) and the stem's pooling are exact in fp32, so that a stored 16-bit value must be ONE round-to-nearest-even of the fp64 result.
+#   x, dout, addends: multiples of 1/2, |v| <= 4;  saved mean, beta: multiples of 1/2, |v| <= 2;  invstd in {1/2, 1, 2};  gamma in
+#   {1/2, 1, 3/2, 2};  scale = gamma * invstd and shift = beta - mean * scale (both exact);  pixel counts that are powers of two, so the
+#   division of a column sum by the count only moves the exponent.
+# Nothing here is exact by decree: check_bn_exact walks every intermediate either apply form can produce, on the fp64 reference alone.
+BN_A = 8                      # x and dout are k / 2 with k drawn uniformly from the integers [-BN_A, BN_A]
+BN_DX_FILL = 0.5              # what a gradient buffer holds before the call: the addend of an accumulating term (on the grid)
+_INVSTD = torch.tensor([0.5, 1.0, 2.0])
+_GAMMA = torch.tensor([0.5, 1.0, 1.5, 2.0])
+_B, _I = (True, 0, 0, None), (False, 0, 0, None)        # a term: (BatchNorm?, log2 of its upsampling, accumulate, writes the dx of term #)
+
+# Backward cases with power-of-two pixel counts.  shape (n, h, w); c for the 16-bit types (c32: the fp32 form of the case, where there is
+# one); relu: the source of the ReLU gate -- "out" (stored activation), "mask" (mask bits), "shift" (recomputed from x * scale + shift);
+# cap: lh_fuse_bwd_desc.strips_cap; env: planned and run under LH_FOLD_IN_APPLY=0; pre: rows of the caller's partial-sum slab(s);
+# route: the launch records lh_fuse_bwd_plan must return, (kind, grid, fold_rows) -- RG / RF / RFX reduce (generic, flat, flat with the
+# gate from x), CO coefficient fold, AG / AF / AFX apply, A2 the two-term apply.  How each route follows from the shape is worked out in
+# the comments; the planner is csrc/fuse_bwd_plan.h.
+BN_BWD_CASES = {
+    # 512 pixels, 4 chunks: strips of 16 rows -> 32; 32 * 64 floats is far below the 16 Ki the apply pass folds itself
+    "flat_out": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="out", route=[("RF", 32, 32), ("AF", 2, 32)]),
+    "flat_mask": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="mask", route=[("RF", 32, 32), ("AF", 2, 32)]),
+    "flat_shift": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="shift", route=[("RFX", 32, 32), ("AFX", 2, 32)]),
+    # ceil(512 / 17) = 31 rows per strip: 16 strips of 31 and one of 16
+    "cap17": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="out", cap=17, route=[("RF", 17, 17), ("AF", 2, 17)]),
+    # the fold launch: 32 rows = two per row lane of slab_lane16, neither unrolled loop
+    "coef32": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="out", env=True, route=[("RF", 32, 0), ("CO", 2, 0), ("AF", 2, 0)]),
+    # 128 rows: one trip of the 8-deep loop of slab_lane16 in every row lane
+    "coef128": dict(shape=(2, 32, 32), c=32, terms=[_B], relu="out", env=True, route=[("RF", 128, 0), ("CO", 2, 0), ("AF", 8, 0)]),
+    # 512 rows: the wide fold (c / 4 workgroups), one trip of its 8-deep loop
+    "coef512": dict(shape=(8, 32, 32), c=32, terms=[_B], relu="out", env=True, route=[("RF", 512, 0), ("CO", 8, 0), ("AF", 32, 0)]),
+    # 256 rows: the wide fold, its 4-deep loop only
+    "coef256": dict(shape=(4, 32, 32), c=32, terms=[_B], relu="mask", env=True, route=[("RF", 256, 0), ("CO", 8, 0), ("AF", 16, 0)]),
+    # 256 rows * 64 = 16 Ki floats: the largest slab an apply pass folds itself
+    "fold256": dict(shape=(4, 32, 32), c=32, terms=[_B], relu="out", route=[("RF", 256, 256), ("AF", 16, 256)]),
+    # 2c = 512 columns: two columns per thread, every row; the strips are capped at 16 Ki / 512 = 32
+    "fold_2c512": dict(shape=(2, 16, 16), c=256, terms=[_B], relu="out", route=[("RF", 32, 32), ("AF", 16, 32)]),
+    # c > 256: flat kernels, but the fold is a launch
+    "c512": dict(shape=(2, 16, 16), c=512, terms=[_B], relu="mask", route=[("RF", 32, 0), ("CO", 32, 0), ("AF", 32, 0)]),
+    # 6 chunks: no power of two -> generic kernels
+    "gen48": dict(shape=(2, 16, 16), c=48, terms=[_B], relu="out", route=[("RG", 32, 0), ("CO", 3, 0), ("AG", 12, 0)]),
+    # 257 chunks: a second trip of the generic reduce's chunk loop with ONE chunk; 32 pixels = 2 strips
+    "gen257": dict(shape=(1, 4, 8), c=2056, c32=1028, terms=[_B], relu="out", route=[("RG", 2, 0), ("CO", 129, 0), ("AG", 33, 0)],
+                   route32=[("RG", 2, 0), ("CO", 65, 0), ("AG", 33, 0)]),
+    "pair_out": dict(shape=(2, 16, 16), c=32, terms=[_B, _I], relu="out", route=[("RF", 32, 32), ("A2", 2, 0)]),
+    "pair_mask": dict(shape=(2, 16, 16), c=32, terms=[_B, _I], relu="mask", route=[("RF", 32, 32), ("A2", 2, 0)]),
+    # two coefficient blocks in one apply pass; the second term adds into its buffer
+    "pair_bnbn": dict(shape=(2, 16, 16), c=32, terms=[_B, (True, 0, 1, None)], relu="out", route=[("RF", 32, 32), ("RF", 32, 32), ("A2", 2, 0)]),
+    # flat and generic records of one call: the l = 1 term has 128 cells = 8 strips (and accumulates), the l = 2 identity term 32 cells
+    "mixed3": dict(shape=(2, 16, 16), c=32, terms=[_B, (True, 1, 1, None), (False, 2, 0, None)], relu="mask",
+                   route=[("RF", 32, 32), ("AF", 2, 32), ("RG", 8, 0), ("CO", 2, 0), ("AG", 2, 0), ("AG", 1, 0)]),
+    # two identity terms that write ONE buffer, the second adding: the passes keep their recorded order
+    "acc_same": dict(shape=(2, 16, 16), c=32, terms=[_I, (False, 0, 1, 0)], relu="mask", route=[("A2", 2, 0)]),
+    # dout is the gated gradient already and its partial sums come with it: no reduce record.  3 rows fold in the apply pass, 300 rows
+    # (300 * 64 floats > 16 Ki) take the wide fold launch
+    "pre3": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="out", pre=3, route=[("AF", 2, 3)]),
+    "pre300": dict(shape=(2, 16, 16), c=32, terms=[_B], relu="out", pre=300, route=[("CO", 8, 0), ("AF", 2, 0)]),
+    "pre3_pair": dict(shape=(2, 16, 16), c=32, terms=[_B, _I], relu="out", pre=3, route=[("A2", 2, 0)]),
+    "pre300_pair": dict(shape=(2, 16, 16), c=32, terms=[_B, _I], relu="out", pre=300, route=[("CO", 8, 0), ("A2", 2, 0)]),
+    "pre3_bnbn": dict(shape=(2, 16, 16), c=32, terms=[_B, _B], relu="out", pre=3, route=[("A2", 2, 0)]),
+    "pre300_bnbn": dict(shape=(2, 16, 16), c=32, terms=[_B, _B], relu="out", pre=300, route=[("CO", 8, 0), ("CO", 8, 0), ("A2", 2, 0)]),
+}
+# Ragged pixel counts (180, 35, 663: the division by the count is inexact, see bn_dx_bound): c = 32 flat, c = 40 generic (5 chunks).
+BN_RAGGED_CASES = {f"{n}x{h}x{w}x{c}": dict(shape=(n, h, w), c=c, terms=[_B], relu=relu, kinds=("RF", "AF") if c == 32 else ("RG", "CO", "AG"))
+                   for (n, h, w) in ((3, 6, 10), (1, 5, 7), (3, 13, 17)) for c, relu in ((32, "out"), (40, "mask"))}
+# (case, precision) the GPU test runs: every case in both 16-bit types, fp32 where the case names its fp32 form
+BN_BWD_RUNS = [(k, p) for k, v in BN_BWD_CASES.items() for p in ("bf16", "fp16", "fp32") if p != "fp32" or "c32" in v]
+# Ranges widened where the default one leaves the rounding condition of tests/test_exact_host.py unmet: (case, precision) -> BN_A.
+BN_WIDER = {("gen257", "fp16"): 16}          # 32 pixels: the coefficients have few fraction bits
+# The stem chain: (n, h, w, c); x on the grid, integer gradients of the pooled map drawn from [-a, a] (large enough that a sum of up to four
+# window gradients needs a rounding, small enough that the BatchNorm backward behind it stays exact: check_bn_exact decides)
+STEM_CASES = [(2, 16, 16, 64), (1, 9, 7, 64)]
+STEM_DOUT = {"bf16": 96, "fp16": 96}
+POOL_DOUT = {"bf16": 255, "fp16": 2047}          # the pool passes alone, gated or not: every integer the type holds exactly
+
+# Forward cases: (name, (n, h, w), c, terms (BatchNorm?, log2 of the upsampling), kind lh_fuse_fwd_plan must return).  c = 48 is 6 (fp32:
+# 12) chunks -- no power of two -- and c = 8 one (two) chunks; 35 and 180 pixels leave a ragged last workgroup.
+BN_FWD_CASES = [
+    ("flat1", (2, 16, 16), 32, [(True, 0)], "FLAT1"), ("flat1_35px", (1, 5, 7), 8, [(True, 0)], "FLAT1"),
+    ("flat2_bn_id", (2, 16, 16), 32, [(True, 0), (False, 0)], "FLAT2"), ("flat2_bn_bn", (2, 16, 16), 32, [(True, 0), (True, 0)], "FLAT2"),
+    ("flat2_bn_id_35px", (1, 5, 7), 8, [(True, 0), (False, 0)], "FLAT2"),
+    ("gen_6chunks", (3, 6, 10), 48, [(True, 0)], "GEN"), ("gen_6chunks_two", (3, 6, 10), 48, [(True, 0), (False, 0)], "GEN"),
+    ("gen_three", (2, 16, 16), 32, [(True, 0), (True, 0), (False, 0)], "GEN"), ("gen_four", (1, 5, 7), 8, [(True, 0), (False, 0), (True, 0), (True, 0)], "GEN"),
+    ("gen_up1", (2, 16, 16), 32, [(True, 0), (True, 1)], "GEN"), ("gen_up2", (2, 16, 16), 32, [(True, 2), (False, 0)], "GEN"),
+    ("gen_up1_up2", (2, 16, 16), 32, [(True, 0), (True, 1), (False, 2)], "GEN"), ("gen_up1_6chunks", (3, 6, 10), 48, [(False, 0), (True, 1)], "GEN"),
+]
+# forward x = k / 2 with |k| <= this, the widest range whose values the type holds exactly: on the backward grid (|k| <= 8) a sum of terms has
+# too few significant bits to need a rounding
+BN_FWD_A = {"bf16": 128, "fp16": 2048, "fp32": 2048}
+
+
+def halves(shape, a, gen):
+    """k / 2 with k drawn uniformly from the integers [-a, a], as float32."""
+    return ints(shape, a, gen) / 2
+
+
+def bn_params(c, gen):
+    """gamma, beta, saved mean, invstd of one BatchNorm on the grid, and scale = gamma * invstd, shift = beta - mean * scale (exact)."""
+    mean, beta = halves((c,), 4, gen), halves((c,), 4, gen)
+    invstd = _INVSTD[torch.randint(0, 3, (c,), generator=gen)]
+    gamma = _GAMMA[torch.randint(0, 4, (c,), generator=gen)]
+    scale = gamma * invstd
+    return dict(gamma=gamma, beta=beta, mean=mean, invstd=invstd, scale=scale, shift=beta - mean * scale)
+
+
+def upsample(t, l):
+    return t.repeat_interleave(1 << l, 1).repeat_interleave(1 << l, 2) if l else t
+
+
+def cell_sum(t, l):
+    """[n][h][w][c] summed over the 2^l x 2^l cells of a nearest-neighbour upsampling."""
+    if not l:
+        return t
+    n, h, w, c = t.shape
+    f = 1 << l
+    return t.reshape(n, h // f, f, w // f, f, c).sum((2, 4))
+
+
+def mask_bits(stored, epc):
+    """lh_fuse_fwd's relu_mask of a stored activation: one byte per 16-byte chunk, bit e = (element e > 0)."""
+    pos = (stored.double() > 0).reshape(-1, epc).to(torch.int32)
+    return (pos << torch.arange(epc, dtype=torch.int32)).sum(1).to(torch.uint8)
+
+
+def store(v, dtype):
+    """What a kernel must store for the exact fp64 value v (which fp32 holds exactly): v itself in fp32, one RNE of it in a 16-bit type."""
+    return v.float().to(dtype)
+
+
+def uneven_groups(count, rows, gen):
+    """Group index of each of `count` pixels: `rows` consecutive groups of uneven, non-zero length."""
+    assert 1 <= rows <= count
+    cuts = (torch.randperm(count - 1, generator=gen)[:rows - 1] + 1).sort().values
+    return torch.searchsorted(cuts, torch.arange(count), right=True)
+
+
+def group_slab(cols, gid, rows):
+    """[rows][len(cols)][c] float32: the totals of every column tensor ([pixels][c], fp64) over each pixel group."""
+    slab = torch.zeros(rows, len(cols), cols[0].shape[1], dtype=torch.float64)
+    for k, v in enumerate(cols):
+        slab[:, k].index_add_(0, gid, v)
+    assert torch.equal(slab.float().double(), slab)
+    return slab.float()
+
+
+def bn_case_c(spec, precision):
+    return spec.get("c32", spec["c"]) if precision == "fp32" else spec["c"]
+
+
+def bn_case_route(spec, precision):
+    return spec.get("route32", spec["route"]) if precision == "fp32" else spec["route"]
+
+
+def bn_node(name, spec, precision, seed=None):
+    """Data and fp64 reference of one lh_fuse_bwd node: dict(shape, c, dout, x[], prm[] (bn_params or None), stored (the forward result as
+    stored), gate, terms[] = dict(g (gated gradient summed over the term's cell), dx (exact, before the old value is added), old (what an
+    accumulating term adds: fp64 tensor or None), total (dx + old), xhat, s0, s1, count), slabs[] (float32 [pre][2][c] per BatchNorm term)).
+    With `pre` dout is the gated gradient itself (no gate is applied)."""
+    dt = DTYPES[precision]
+    n, h, w = spec["shape"]
+    c = bn_case_c(spec, precision)
+    a = BN_WIDER.get((name, precision), spec.get("a", BN_A))
+    gen = torch.Generator().manual_seed(seed if seed is not None else 500 + sum(ord(ch) * (i + 1) for i, ch in enumerate(name)))
+    d = dict(name=name, shape=(n, h, w), c=c, a=a, dout=halves((n, h, w, c), a, gen), x=[], prm=[], terms=[], slabs=[])
+    pre_act = torch.zeros(n, h, w, c, dtype=torch.float64)
+    for bn, l, acc, same in spec["terms"]:
+        x = halves((n, h >> l, w >> l, c), a, gen)
+        p = bn_params(c, gen) if bn else None
+        d["x"].append(x)
+        d["prm"].append(p)
+        pre_act += upsample(x.double() * p["scale"].double() + p["shift"].double() if bn else x.double(), l)
+    relu, pre = spec["relu"], spec.get("pre", 0)
+    d["stored"] = store(torch.relu(pre_act) if relu != "off" else pre_act, dt)
+    d["gate"] = torch.ones_like(pre_act) if (pre or relu == "off") else (d["stored"].double() > 0).double()
+    gg = d["dout"].double() * d["gate"]
+    for i, (bn, l, acc, same) in enumerate(spec["terms"]):
+        g = cell_sum(gg, l)
+        t = dict(g=g, count=g.shape[0] * g.shape[1] * g.shape[2], old=None)
+        if bn:
+            p = {k: v.double() for k, v in d["prm"][i].items()}
+            t["xhat"] = (d["x"][i].double() - p["mean"]) * p["invstd"]
+            t["s0"], t["s1"] = g.sum((0, 1, 2)), (g * t["xhat"]).sum((0, 1, 2))
+            t["dx"] = p["scale"] * (g - t["s0"] / t["count"] - t["xhat"] * (t["s1"] / t["count"]))
+            if pre:
+                gid = uneven_groups(t["count"], pre, gen)
+                d["slabs"].append(group_slab([g.reshape(-1, c), (g * t["xhat"]).reshape(-1, c)], gid, pre))
+        else:
+            t["dx"] = g
+        if acc:         # what the buffer holds: its fill, or -- two terms that write one buffer -- the earlier term's stored result
+            t["old"] = store(d["terms"][same]["total"], dt).double() if same is not None else torch.full_like(g, BN_DX_FILL)
+        t["total"] = t["dx"] + t["old"] if acc else t["dx"]
+        d["terms"].append(t)
+    return d
+
+
+def _fits(v, what):
+    """fp32 holds the fp64 value v exactly: v = k * q with q the largest power of two that divides it and |k| < 2^24 -- which is
+    float32(v) == v -- and the fp64 evaluation that produced it was exact itself (multiples of 2^-32 below 2^20: 52 bits)."""
+    v = v.double()
+    scaled = v * 2.0 ** 32
+    assert bool((scaled == torch.round(scaled)).all()) and float(v.abs().max()) < 2.0 ** 20, f"{what}: outside the range the fp64 evaluation is exact on"
+    bad = v.float().double() != v
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} values need more than 24 significant bits"
+    return v
+
+
+def _sum_fits(terms, q, what):
+    """Column sums over ANY subset of the rows of terms ([..][c]) in any order: every term a multiple of q, the column's sum of magnitudes
+    below 2^24 q.  Returns the largest column, in quanta."""
+    terms = terms.double().reshape(-1, terms.shape[-1])
+    assert bool((terms / q == torch.round(terms / q)).all()), f"{what}: a term is no multiple of {q}"
+    ok, m = check_exact_rows(terms, q)
+    assert ok, f"{what}: sum of magnitudes {m:.0f} quanta >= 2^24"
+    return m
+
+
+def check_bn_exact(d, spec, precision):
+    """The proof obligation of the BatchNorm grid, on the fp64 reference alone (bn_node): every intermediate any kernel form can produce is
+    an integer multiple of a power-of-two quantum below 2^24 quanta (_fits, _sum_fits), and no fp16 value overflows.  Walks, per term:
+    the gated gradient summed over its cell; x - mean, xhat, g * (x - mean), g * xhat; the column sums over any subset of rows; with a
+    power-of-two count c0, c1 and both apply forms -- scale * ((g - c0) - xhat * c1) and A g + B x + C with B = -(A invstd) c1,
+    C = -(A c0) - B mean -- product by product and sum by sum; the sum with the old dx.  Returns the largest column sum, in quanta."""
+    dt = DTYPES[precision]
+    worst = 0.0
+    _fits(d["dout"], "dout")
+    assert torch.equal(d["dout"].to(dt).float(), d["dout"])
+    for i, t in enumerate(d["terms"]):
+        tag = f"{d['name']} term {i}"
+        g = _fits(t["g"], tag + " g")
+        assert torch.equal(d["x"][i].to(dt).float(), d["x"][i])
+        if d["prm"][i] is not None:
+            p = {k: v.double() for k, v in d["prm"][i].items()}
+            x = d["x"][i].double()
+            assert torch.equal(p["scale"], p["gamma"] * p["invstd"]) and torch.equal(p["shift"], p["beta"] - p["mean"] * p["scale"])
+            xm = _fits(x - p["mean"], tag + " x - mean")
+            xhat = _fits(xm * p["invstd"], tag + " xhat")
+            assert torch.equal(xhat, t["xhat"])
+            gxm = _fits(g * xm, tag + " g * (x - mean)")
+            gxh = _fits(gxm * p["invstd"], tag + " g * xhat")
+            assert torch.equal(gxh, g * xhat)
+            worst = max(worst, _sum_fits(g, 0.5, tag + " sum g"), _sum_fits(gxh, 0.125, tag + " sum g * xhat"))
+            _fits(t["s0"], tag + " dbeta")
+            _fits(t["s1"], tag + " dgamma")
+            cnt = t["count"]
+            if cnt & (cnt - 1) == 0:
+                c0, c1 = _fits(t["s0"] / cnt, tag + " c0"), _fits(t["s1"] / cnt, tag + " c1")
+                A = p["scale"]
+                # scale * (g - c0 - xhat * c1): fuse_bwd_apply
+                f1 = _fits(A * _fits(_fits(g - c0, tag + " g - c0") - _fits(xhat * c1, tag + " xhat * c1"), tag + " g - c0 - xhat * c1"), tag + " dx")
+                # A g + B x + C: term_coefs and the flat applies
+                B = _fits(-_fits(A * p["invstd"], tag + " A * invstd") * c1, tag + " B")
+                C = _fits(-_fits(A * c0, tag + " A * c0") - _fits(B * p["mean"], tag + " B * mean"), tag + " C")
+                f2 = _fits(_fits(_fits(A * g, tag + " A * g") + _fits(B * x, tag + " B * x"), tag + " A g + B x") + C, tag + " dx (flat)")
+                assert torch.equal(f1, f2) and torch.equal(f1, t["dx"]), tag + ": the two apply forms disagree"
+        if t["count"] & (t["count"] - 1) == 0 or d["prm"][i] is None:
+            _fits(t["total"], tag + " dx + old")
+        if precision == "fp16":
+            assert float(t["total"].abs().max()) <= FP16_MAX and bool(torch.isfinite(store(t["total"], dt)).all())
+    if precision == "fp16":
+        assert float(d["stored"].double().abs().max()) <= FP16_MAX
+    return worst
+
+
+def bn_dx_bound(d, i):
+    """Per-element bound E on |stored fp32 dx - exact dx| of BatchNorm term i when the pixel count is no power of two, from the fp64
+    operands: E = 8 * 2^-24 * M with M = |scale| (|g| + |c0| + |invstd c1| (|x| + |mean|)), the sum of the magnitudes of the terms of the
+    formula.  Derivation, with u = 2^-24 (one fp32 rounding, first order; the column sums are exact, so c0 = fl(s0 / N) and c1 = fl(s1 / N)
+    carry u each, everything else on the grid is exact):
+      scale * ((g - c0) - xhat * c1):  fl(xhat c1) 2u |xhat c1|;  fl(g - c0) u (|g| + 2 |c0|);  their difference u (2 |g| + 3 |c0| +
+        3 |xhat c1|);  times scale: u |scale| (3 |g| + 4 |c0| + 4 |xhat c1|), and |xhat| <= invstd (|x| + |mean|).
+      A g + B x + C:  B = fl((A invstd) c1) 2u |B|;  C = fl(fl(A c0) - fl(B mean)) u (3 |A c0| + 4 |B mean|);  fl(B x) 3u |B x|;
+        fl(A g + B x) u (|A g| + 4 |B x|);  the last sum u (2 |A g| + 5 |B x| + 4 |A c0| + 5 |B mean|).
+    Both stay below 5u M; the factor 8 leaves room for the second-order terms and the fp64 roundings of the fold."""
+    t, p = d["terms"][i], {k: v.double() for k, v in d["prm"][i].items()}
+    c0, c1 = t["s0"] / t["count"], t["s1"] / t["count"]
+    M = p["scale"].abs() * (t["g"].abs() + c0.abs() + (p["invstd"] * c1).abs() * (d["x"][i].double().abs() + p["mean"].abs()))
+    return 8.0 * 2.0 ** -24 * M
+
+
+def interval_16(ref, E, dtype):
+    """(low, high, strict): the closed interval [RNE(ref - E), RNE(ref + E)] a stored value must lie in, and where its ends coincide."""
+    lo, hi = store(ref - E, dtype), store(ref + E, dtype)
+    return lo, hi, lo == hi
+
+
+def bn_fwd_data(case, precision, relu):
+    """x[], prm[], exact fp64 result and the partial sums of one forward case (term order: the kernels add in it)."""
+    name, (n, h, w), c, terms, _ = case
+    gen = torch.Generator().manual_seed(700 + sum(ord(ch) * (i + 1) for i, ch in enumerate(name)))
+    d = dict(x=[], prm=[], parts=[])
+    acc = torch.zeros(n, h, w, c, dtype=torch.float64)
+    for bn, l in terms:
+        x = halves((n, h >> l, w >> l, c), BN_FWD_A[precision], gen)
+        p = bn_params(c, gen) if bn else None
+        v = _fits(x.double() * p["scale"].double(), name + " x * scale") + p["shift"].double() if bn else x.double()
+        acc = acc + upsample(_fits(v, name + " term"), l)
+        d["x"].append(x)
+        d["prm"].append(p)
+        d["parts"].append(_fits(acc, name + " partial sum"))
+    d["exact"] = torch.relu(acc) if relu else acc
+    return d
+
+
+def stem_data(case, precision, seed=900):
+    """The stem chain's inputs: x on the grid, one BatchNorm, integer gradients of the pooled map (for the chain / for the plain pool)."""
+    n, h, w, c = case
+    gen = torch.Generator().manual_seed(seed + h)
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return dict(x=halves((n, h, w, c), BN_A, gen), prm=bn_params(c, gen), dout=ints((n, ho, wo, c), STEM_DOUT[precision], gen),
+                dout_pool=ints((n, ho, wo, c), POOL_DOUT[precision], gen))
+
+
+def stem_reference(s, precision, which="dout"):
+    """fp64 reference of bn + relu + maxpool and its backward: a (the activation as it would be stored), pooled, the pool's input gradient
+    (exact sum of up to four window gradients) and a bn_node-style dict of the BatchNorm backward behind it, whose `dout` is the ROUNDED,
+    gated pool gradient and whose gate is all ones (lh_fuse_bwd's pre_partial form)."""
+    dt = DTYPES[precision]
+    p = {k: v.double() for k, v in s["prm"].items()}
+    x = s["x"].double()
+    pre_act = x * p["scale"] + p["shift"]
+    a = store(torch.relu(pre_act), dt).double().permute(0, 3, 1, 2).requires_grad_(True)
+    pooled = F.max_pool2d(a, 3, 2, 1)
+    pooled.backward(s[which].double().permute(0, 3, 1, 2))
+    gpool = a.grad.permute(0, 2, 3, 1).contiguous()
+    g = store(gpool, dt).double() * (pre_act > 0)             # rounded as the ungated pass stores it, then gated by the ReLU
+    xhat = (x - p["mean"]) * p["invstd"]
+    cnt = x.shape[0] * x.shape[1] * x.shape[2]
+    t = dict(g=g, count=cnt, old=None, xhat=xhat, s0=g.sum((0, 1, 2)), s1=(g * xhat).sum((0, 1, 2)))
+    t["dx"] = t["total"] = p["scale"] * (g - t["s0"] / cnt - xhat * (t["s1"] / cnt))
+    node = dict(name=f"stem{x.shape[1]}", shape=tuple(x.shape[:3]), c=x.shape[3], dout=g.float(), x=[s["x"]], prm=[s["prm"]], terms=[t], slabs=[],
+                stored=store(torch.relu(pre_act), dt))
+    return dict(a=a.detach().permute(0, 2, 3, 1), pooled=pooled.detach().permute(0, 2, 3, 1).contiguous(), gpool=gpool, node=node)
+
+
+def bn_planned_route(lib, desc, n, h, w, c, workspace, dtype_code):
+    """[(kind, grid, fold_rows)] of lh_fuse_bwd_plan for a descriptor (ctypes); raises on an error status."""
+    import ctypes as C
+    cap = 16
+    kinds, grids, folds = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+    nrec = lib.lh_fuse_bwd_plan(C.byref(desc), n, h, w, c, workspace, dtype_code, kinds, grids, folds, cap)
+    assert 0 < nrec <= cap, (nrec, lib.lh_last_error())
+    return [(kinds[i], grids[i], folds[i]) for i in range(nrec)]

@@ -170,3 +170,163 @@ def test_chain_meets_the_preconditions(precision):
     for k, g in grads.items():
         assert torch.equal(g.float().double(), g), k                  # fp32 holds every expected gradient exactly
         assert float((g != 0).double().mean()) > 0.5, k               # and the gradients are dense: every pixel counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The BatchNorm grid of tests/test_gpu_exact_bn.py: its proof obligation, its rounding shares, the interval condition of the ragged
+# cases, and the route table pinned through lh_fuse_bwd_plan / lh_fuse_fwd_plan (host arithmetic: no GPU).
+@pytest.mark.parametrize("name,precision", E.BN_BWD_RUNS)
+def test_bn_backward_cases_are_exact_and_need_rounding(name, precision):
+    """check_bn_exact on every case and precision the GPU test runs; and, in the spirit of (c): at least 10 % of the BatchNorm terms' dx
+    elements differ from their 16-bit rounding and at least one is an exact tie.  (A node of identity terms only has dx = g or g + g,
+    which the type of dout always holds: there the condition cannot be met by any data and the exact comparison is about order.)"""
+    spec = E.BN_BWD_CASES[name]
+    d = E.bn_node(name, spec, precision)
+    assert d["a"] >= E.BN_A                                                              # widened, never narrowed
+    worst = E.check_bn_exact(d, spec, precision)
+    assert float(d["gate"].mean()) > 0.2 and (spec.get("pre") or spec["relu"] == "off" or float(d["gate"].mean()) < 0.8)
+    dt = E.DTYPES[precision]
+    tot = torch.cat([t["total"].reshape(-1) for t, p in zip(d["terms"], d["prm"]) if p is not None] or [torch.zeros(0, dtype=torch.float64)])
+    if precision == "fp32":
+        assert torch.equal(tot.float().double(), tot)
+        return
+    if tot.numel() == 0:
+        return
+    need, ties = E.rounding_counts(tot, dt)
+    print(name, precision, f"largest column sum {worst:.0f} quanta, dx elements that need rounding {need} of {tot.numel()} "
+          f"({100.0 * need / tot.numel():.1f} %), ties {ties}")
+    assert need >= 0.1 * tot.numel() and ties >= 1, (need, ties, tot.numel())
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("name", list(E.BN_RAGGED_CASES))
+def test_bn_ragged_cases_pin_all_but_two_percent_of_the_elements(name, precision):
+    """Pixel counts 180, 35, 663: the sums stay exact (check_bn_exact), the division by the count does not, and a stored dx must lie in
+    [RNE(ref - E), RNE(ref + E)] (E: exact_data.bn_dx_bound).  Condition: the two ends differ for at most 2 % of the elements, so at
+    least 98 % of them are held to one value."""
+    spec = E.BN_RAGGED_CASES[name]
+    d = E.bn_node(name, spec, precision)
+    E.check_bn_exact(d, spec, precision)
+    ref, bound = d["terms"][0]["dx"], E.bn_dx_bound(d, 0)
+    lo, hi, strict = E.interval_16(ref, bound, E.DTYPES[precision])
+    want = E.store(ref, E.DTYPES[precision])
+    assert bool((lo.double() <= want.double()).all()) and bool((want.double() <= hi.double()).all())
+    loose = 1.0 - float(strict.double().mean())
+    need, ties = E.rounding_counts(ref, E.DTYPES[precision])
+    print(name, precision, f"ends differ for {100 * loose:.2f} % of {ref.numel()} elements; {need} need rounding")
+    assert loose <= 0.02 and need >= 0.1 * ref.numel()
+    assert float((bound / ref.abs().clamp_min(1e-30)).median()) < 2.0 ** -18            # the bound is a few fp32 ulps, not a tolerance
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16", "fp32"])
+@pytest.mark.parametrize("case", E.BN_FWD_CASES, ids=[c[0] for c in E.BN_FWD_CASES])
+def test_bn_forward_cases_are_exact_and_need_rounding(case, precision):
+    """Every term, and every partial sum in term order, is held by fp32 exactly (bn_fwd_data asserts it as it goes); in the 16-bit types
+    at least 2 % of the results need a rounding (behind the ReLU: at least one), one is a tie, and none overflows."""
+    dt = E.DTYPES[precision]
+    for relu in (0, 1):
+        d = E.bn_fwd_data(case, precision, relu)
+        for x in d["x"]:
+            assert torch.equal(x.to(dt).float(), x)
+        if precision == "fp32":
+            continue
+        assert float(d["exact"].abs().max()) <= E.FP16_MAX
+        need, ties = E.rounding_counts(d["exact"], dt)
+        print(case[0], precision, "relu" if relu else "no relu", f"need rounding {need} of {d['exact'].numel()}, ties {ties}")
+        assert need >= (1 if relu else 0.02 * d["exact"].numel()) and ties >= 1
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", E.STEM_CASES, ids=["x".join(map(str, c)) for c in E.STEM_CASES])
+def test_stem_chain_is_exact(case, precision):
+    """The pool's input gradient is a sum of up to four integers (exact; with the wide range some need a rounding), the slab rows of the
+    gated pass sum exactly in any grouping with either range, and with the narrow range the BatchNorm backward behind the rounded, gated
+    gradient passes check_bn_exact; the 63-pixel shape meets the 2 % condition."""
+    dt = E.DTYPES[precision]
+    s = E.stem_data(case, precision)
+    for which in ("dout", "dout_pool"):
+        r = E.stem_reference(s, precision, which)
+        need, _ = E.rounding_counts(r["gpool"], dt)
+        t = r["node"]["terms"][0]
+        assert float(r["gpool"].abs().max()) <= E.FP16_MAX and (need >= 10 or which == "dout")
+        worst = max(E._sum_fits(t["g"], 1.0, "sum g"), E._sum_fits(t["g"] * t["xhat"], 0.25, "sum g * xhat"))
+        print(case, precision, which, f"pool gradients that need rounding: {need}; largest column sum {worst:.0f} quanta")
+    r = E.stem_reference(s, precision)
+    E.check_bn_exact(r["node"], None, precision)
+    need, ties = E.rounding_counts(r["node"]["terms"][0]["dx"], dt)
+    assert need >= 0.1 * r["node"]["terms"][0]["dx"].numel()
+    cnt = case[0] * case[1] * case[2]
+    if cnt & (cnt - 1):
+        _, _, strict = E.interval_16(r["node"]["terms"][0]["dx"], E.bn_dx_bound(r["node"], 0), dt)
+        assert 1.0 - float(strict.double().mean()) <= 0.02
+
+
+_FAKE = 1 << 20           # a non-null address the planners never dereference
+
+
+def _fake_bwd_desc(spec):
+    from lighthand_amd import _lib
+    d = _lib.FuseBwdDesc()
+    relu, terms, pre = spec["relu"], spec["terms"], spec.get("pre", 0)
+    d.dout, d.relu, d.nterms, d.strips_cap = _FAKE, int(relu != "off"), len(terms), spec.get("cap", 0)
+    d.out = _FAKE if relu in ("out", "shift") else None
+    d.relu_mask = _FAKE if relu == "mask" else None
+    for i, (bn, l, acc, same) in enumerate(terms):
+        if bn:
+            d.x[i] = d.scale[i] = d.save_mean[i] = d.save_invstd[i] = d.dgamma[i] = d.dbeta[i] = _FAKE
+            d.shift[i] = _FAKE if relu == "shift" else None
+        d.dx[i] = _FAKE + 4096 * (i if same is None else same)
+        d.log2up[i], d.accumulate[i] = l, acc
+    if pre:
+        d.pre_partial, d.pre_rows = _FAKE, pre
+        if sum(bn for bn, *_ in terms) == 2:
+            d.pre_partial2 = _FAKE
+    return d
+
+
+def test_bn_route_table_is_what_the_planners_return(monkeypatch):
+    """lh_fuse_bwd_plan / lh_fuse_fwd_plan on every case of exact_data.BN_BWD_CASES, BN_RAGGED_CASES and BN_FWD_CASES: exactly the kinds,
+    grids (= strips for the reduce records) and fold rows the tables name -- so every GPU case reaches the route it was written for --
+    and between them all eight backward and all three forward kinds."""
+    import ctypes as C
+    from lighthand_amd import _lib
+    lib = _lib.load()
+    kb = dict(RG=_lib.LH_FB_REDUCE_GEN, RF=_lib.LH_FB_REDUCE_FLAT, RFX=_lib.LH_FB_REDUCE_FLAT_X, CO=_lib.LH_FB_COEF, AG=_lib.LH_FB_APPLY_GEN,
+              AF=_lib.LH_FB_APPLY_FLAT, AFX=_lib.LH_FB_APPLY_FLAT_X, A2=_lib.LH_FB_APPLY2)
+    kf = dict(GEN=_lib.LH_FF_GEN, FLAT1=_lib.LH_FF_FLAT1, FLAT2=_lib.LH_FF_FLAT2)
+    assert sorted(kb.values()) == list(range(8)) and sorted(kf.values()) == list(range(3))
+    code = dict(bf16=_lib.LH_BF16, fp16=_lib.LH_F16, fp32=_lib.LH_F32)
+    seen = set()
+    for name, precision in E.BN_BWD_RUNS:
+        spec = E.BN_BWD_CASES[name]
+        monkeypatch.delenv("LH_FOLD_IN_APPLY", raising=False)
+        if spec.get("env"):
+            monkeypatch.setenv("LH_FOLD_IN_APPLY", "0")
+        got = E.bn_planned_route(lib, _fake_bwd_desc(spec), *spec["shape"], E.bn_case_c(spec, precision), _FAKE, code[precision])
+        assert got == [(kb[k], g, f) for k, g, f in E.bn_case_route(spec, precision)], (name, precision, got)
+        seen |= {k for k, _, _ in got}
+    monkeypatch.delenv("LH_FOLD_IN_APPLY", raising=False)
+    assert seen == set(range(8))
+    for name, spec in E.BN_RAGGED_CASES.items():
+        got = E.bn_planned_route(lib, _fake_bwd_desc(spec), *spec["shape"], spec["c"], _FAKE, _lib.LH_BF16)
+        assert [k for k, _, _ in got] == [kb[k] for k in spec["kinds"]], (name, got)
+    # a record buffer shorter than the plan: the count is still returned, nothing is written past `cap`
+    spec = E.BN_BWD_CASES["mixed3"]
+    kinds = (C.c_int * 3)(-1, -1, -1)
+    assert lib.lh_fuse_bwd_plan(C.byref(_fake_bwd_desc(spec)), *spec["shape"], spec["c"], _FAKE, _lib.LH_BF16, kinds, None, None, 2) == 6
+    assert list(kinds) == [kb["RF"], kb["AF"], -1]
+    assert lib.lh_fuse_bwd_plan(C.byref(_fake_bwd_desc(spec)), *spec["shape"], 12, _FAKE, _lib.LH_BF16, kinds, None, None, 2) == -1
+    seen_f = set()
+    for name, (n, h, w), c, terms, want in E.BN_FWD_CASES:
+        for precision in ("bf16", "fp16", "fp32"):
+            d = _lib.FuseDesc()
+            d.nterms, d.relu = len(terms), 1
+            for i, (bn, l) in enumerate(terms):
+                d.x[i], d.log2up[i] = _FAKE, l
+                d.scale[i] = d.shift[i] = _FAKE if bn else None
+            kind, grid = C.c_int(-1), C.c_int(-1)
+            assert lib.lh_fuse_fwd_plan(C.byref(d), _FAKE, n, h, w, c, code[precision], C.byref(kind), C.byref(grid)) == 0, lib.lh_last_error()
+            chunks = n * h * w * c // (4 if precision == "fp32" else 8)
+            assert kind.value == kf[want] and grid.value == (-(-chunks // 256) if want == "GEN" else max(1, -(-chunks // 1024))), (name, precision)
+            seen_f.add(kind.value)
+    assert seen_f == set(range(3))
