@@ -99,6 +99,21 @@ int lh_box_affine(const float* boxes_dev, const int* frame_index_dev, int b, int
 int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
                             int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
                             int dtype, void* stream);
+/* The antialiased sibling (opt-in; the same kernel, and max_taps = 1 is lh_frames_crop_to_nhwc4 bit for bit): a minified ROI averages
+ * kx x ky of the samples above, spread evenly over each crop pixel's footprint.  fp32, in this order.  Per slot:
+ * sx = sqrtf(m0*m0 + m3*m3), sy = sqrtf(m1*m1 + m4*m4) (frame pixels per crop pixel along the crop's axes),
+ * kx = sx > 1.015625f && isfinite(sx) ? min(max_taps, (int)ceilf(fminf(sx, 64.f))) : 1, ky likewise from sy (a NaN or infinite
+ * scale gives 1: every sample of such a slot is outside the frame; a slot that is not minified takes the single sample).  Per
+ * output pixel, j = 0..ky-1 outside, i = 0..kx-1 inside: dy = (float)(2*j + 1 - ky) / (float)(2*ky) (= (j + 0.5) / ky - 0.5, rounded
+ * once), uy = (float)oy + dy, dx and ux likewise, fx = (m0*ux + m1*uy) + m2, fy = (m3*ux + m4*uy) + m5, acc[ch] += the sample at
+ * (fx, fy) on the raw 0..255 values (same inside test, clamp and blend; outside or NaN adds 0); then
+ * c = (acc * (1.f / (float)(kx*ky))) * (1/255) and Normalize as above.  An aligned integer minification s = 2, 3, 4, 6 or 8
+ * <= max_taps (m = (s, 0, (s-1)/2, 0, s, (s-1)/2)) is the exact mean of each s x s block, bit for bit, for crops up to 512 pixels
+ * a side; above max_taps the taps are more than one frame pixel apart (aliasing reduced, not removed).
+ * max_taps outside 1..8 is LH_ERR_ARG. */
+int lh_frames_crop_area_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
+                                 int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                 int max_taps, int dtype, void* stream);
 /* preds_dev fp32 [b][j][2] (frame coordinates), maxvals_dev fp32 [b][j] -> next_boxes_dev fp32 [b][4], lost_dev int32 [b]: the bounds
  * of the keypoints with maxval >= min_score, each side widened about its centre to at least min_side.  With fewer than min_joints
  * such keypoints, or for an empty slot (src_frame < 0), next_boxes[i] = boxes[i] and lost[i] = 1; otherwise lost[i] = 0.  No

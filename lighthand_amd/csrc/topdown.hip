@@ -42,6 +42,31 @@ extern "C" int lh_box_affine(const float* boxes_dev, const int* frame_index_dev,
 // matrix and frame number are the same for the whole workgroup (scalar loads); one thread per pixel of the padded output, as
 // image_u8_kernel.  A gather over bytes: neighbouring lanes read neighbouring source pixels (a box maps rows to rows), the four taps
 // of a pixel share cache lines with its neighbours', and the frame's reuse across the boxes that read it is the L2's.
+//
+// Area sampling of minified ROIs (lh_frames_crop_area_to_nhwc4; max_taps = 1 is the plain crop).  One bilinear sample per crop pixel
+// skips frame pixels as soon as a crop pixel covers more than one of them, so a minified crop averages kx x ky samples spread evenly
+// over each crop pixel's footprint instead.  The rule, fp32 in this order; topdown.py's frames_crop_host / crop_taps_host restate it.
+// Per slot, from its matrix:
+//     sx = sqrtf(m0*m0 + m3*m3), sy = sqrtf(m1*m1 + m4*m4)          frame pixels per crop pixel along the crop's x and y axes
+//     kx = sx > 1.015625f && isfinite(sx) ? min(max_taps, (int)ceilf(fminf(sx, 64.f))) : 1, ky likewise from sy
+// A NaN scale fails the comparison and gives 1, an infinite one is given 1 (such a matrix puts every sample outside the frame); the
+// 1/64 slack keeps a ROI at scale 1 + rounding error on the single-sample path.
+// Per output pixel (ox, oy), j = 0..ky-1 outside and i = 0..kx-1 inside:
+//     dy = (float)(2*j + 1 - ky) / (float)(2*ky), uy = (float)oy + dy;  dx, ux likewise from i, kx and ox
+//     (the offset (j + 0.5) / ky - 0.5 rounded ONCE: formed as (j + 0.5f) / ky - 0.5f it is -0.33333331 for ky = 3, and the first
+//     sample of an aligned s = 3 crop then lands 6e-8 beside its pixel instead of on it)
+//     fx = (m0*ux + m1*uy) + m2, fy = (m3*ux + m4*uy) + m5
+//     acc[ch] += the plain crop's sample at (fx, fy) on the raw 0..255 values: the same inside test, edge clamp and blend
+//                top + (bot - top) * wy; a sample outside the frame (or a NaN) adds 0
+// then c[ch] = (acc[ch] * (1.f / (float)(kx*ky))) * (1.f / 255.f), Normalize and the store as in the plain crop.
+// With kx = ky = 1 the offsets are 0 and acc * 1.f = acc: the plain crop bit for bit (the kernel takes the plain body then).  A pixel
+// whose samples all fall outside is exactly black.  An aligned integer minification s <= max_taps (m = (s, 0, (s-1)/2, 0, s, (s-1)/2))
+// puts the samples on the integer pixels s*ox + i for s = 2, 3, 4, 5, 6, 8 and crops up to 512 pixels a side (s = 7 does not:
+// 3/7 has no short binary form): the exact mean of the s x s block.  Above max_taps the taps are more than one frame
+// pixel apart, so aliasing is reduced, not removed.  kx and ky are the same for the whole workgroup (the slot is blockIdx.y): the
+// tap loops are uniform, no divergence.  Texels are byte loads as in the plain crop: the taps of a pixel and of its neighbours share
+// cache lines, and the frame's reuse is the L2's.  Which pixel a thread takes does not enter the rule: a slot whose crop rows run
+// across the frame's rows is walked in 8 x 8 tiles (crop_pixels).
 struct CropArgs {
     const unsigned char* src;
     void* dst;
@@ -49,39 +74,80 @@ struct CropArgs {
     const int* src_frame;
     int n_frames, hs, ws, h, w, pad, hp, wp;
     float mean[3], istd[3];
+    int max_taps;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
-    const int slot = blockIdx.y;
-    const float* m = p.mat + slot * 6;
-    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
-    const int sf = p.src_frame[slot];
-    const bool live = sf >= 0 && sf < p.n_frames;                 // anything else is an empty slot: never an address
-    const unsigned char* base = p.src + (long)(live ? sf : 0) * p.hs * p.ws * 3;
-    const int per_slot = p.hp * p.wp;
-    T* dst = (T*)p.dst + (long)slot * per_slot * 4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per_slot; i += gridDim.x * blockDim.x) {
-        const int y = i / p.wp, x = i - y * p.wp;
+// One bilinear sample of the frame at (fx, fy) on the raw 0..255 values; false (s untouched) outside the frame or for a NaN.
+__device__ __forceinline__ bool crop_sample(const unsigned char* base, int hs, int ws, float fx, float fy, float s[3]) {
+    if (!(fx >= -0.5f && fx <= ws - 0.5f && fy >= -0.5f && fy <= hs - 0.5f)) return false;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    // f up to size-0.5: the upper clamp only keeps the gather in bounds (x1 == x0 there, the weight does not matter)
+    const int y0 = min((int)fy, hs - 1), x0 = min((int)fx, ws - 1);
+    const int y1 = y0 + 1 < hs ? y0 + 1 : hs - 1, x1 = x0 + 1 < ws ? x0 + 1 : ws - 1;
+    const float wy = fy - y0, wx = fx - x0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a00 = base[((long)y0 * ws + x0) * 3 + ch], a01 = base[((long)y0 * ws + x1) * 3 + ch];
+        const float a10 = base[((long)y1 * ws + x0) * 3 + ch], a11 = base[((long)y1 * ws + x1) * 3 + ch];
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        s[ch] = top + (bot - top) * wy;
+    }
+    return true;
+}
+
+__device__ __forceinline__ int crop_taps(float a, float b, int max_taps) {
+    const float s = sqrtf(a * a + b * b);
+    return s > 1.015625f && isfinite(s) ? min(max_taps, (int)ceilf(fminf(s, 64.f))) : 1;
+}
+
+// The pixels of one slot.  AREA = false is the plain crop, one sample at the pixel's centre: the loop the kernel always had, kept apart
+// from the tap loops so that it compiles to what it was.  AREA = true: a live slot, kx x ky samples over the pixel's footprint.
+template <typename T, bool AREA>
+__device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned char* base, bool live, T* dst, int first, int stride,
+                                            int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky,
+                                            bool tiled) {
+    const float fkx2 = (float)(2 * kx), fky2 = (float)(2 * ky), inv = 1.f / (float)(kx * ky);
+    // AREA, tiled (the slot's choice, below): a wave takes an 8 x 8 tile of the output instead of 64 pixels of a row, so that its samples
+    // stay within a square of the frame (a row of a turned ROI is a slanted line across many frame rows: a cache line per lane and load)
+    const int tiles_x = (p.wp + 7) >> 3, n = AREA && tiled ? tiles_x * ((p.hp + 7) >> 3) * 64 : per_slot;
+    for (int q = first; q < n; q += stride) {
+        int y, x;
+        if (AREA && tiled) {
+            const int tile = q >> 6, ty = tile / tiles_x;
+            y = ty * 8 + ((q >> 3) & 7);
+            x = (tile - ty * tiles_x) * 8 + (q & 7);
+            if (y >= p.hp || x >= p.wp) continue;
+        } else {
+            y = q / p.wp;
+            x = q - y * p.wp;
+        }
+        const int i = y * p.wp + x;
         const int oy = y - p.pad, ox = x - p.pad;
         float v[3] = {0.f, 0.f, 0.f};
         if ((unsigned)oy < (unsigned)p.h && (unsigned)ox < (unsigned)p.w) {
             float c[3] = {0.f, 0.f, 0.f};
-            float fx = (m0 * ox + m1 * oy) + m2, fy = (m3 * ox + m4 * oy) + m5;
-            if (live && fx >= -0.5f && fx <= p.ws - 0.5f && fy >= -0.5f && fy <= p.hs - 0.5f) {        // NaN fails the test: black
-                fy = fy < 0.f ? 0.f : fy;
-                fx = fx < 0.f ? 0.f : fx;
-                // f up to size-0.5: the upper clamp only keeps the gather in bounds (x1 == x0 there, the weight does not matter)
-                const int y0 = min((int)fy, p.hs - 1), x0 = min((int)fx, p.ws - 1);
-                const int y1 = y0 + 1 < p.hs ? y0 + 1 : p.hs - 1, x1 = x0 + 1 < p.ws ? x0 + 1 : p.ws - 1;
-                const float wy = fy - y0, wx = fx - x0;
+            if constexpr (!AREA) {
+                float s[3];
+                if (live && crop_sample(base, p.hs, p.ws, (m0 * ox + m1 * oy) + m2, (m3 * ox + m4 * oy) + m5, s)) {   // NaN: black
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float a00 = base[((long)y0 * p.ws + x0) * 3 + ch], a01 = base[((long)y0 * p.ws + x1) * 3 + ch];
-                    const float a10 = base[((long)y1 * p.ws + x0) * 3 + ch], a11 = base[((long)y1 * p.ws + x1) * 3 + ch];
-                    const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
-                    c[ch] = (top + (bot - top) * wy) * (1.f / 255.f);
+                    for (int ch = 0; ch < 3; ++ch) c[ch] = s[ch] * (1.f / 255.f);
                 }
+            } else {
+                float acc[3] = {0.f, 0.f, 0.f};
+                for (int j = 0; j < ky; ++j) {
+                    const float uy = (float)oy + (float)(2 * j + 1 - ky) / fky2;
+                    for (int t = 0; t < kx; ++t) {
+                        const float ux = (float)ox + (float)(2 * t + 1 - kx) / fkx2;
+                        float s[3];
+                        if (crop_sample(base, p.hs, p.ws, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, s)) {
+#pragma unroll
+                            for (int ch = 0; ch < 3; ++ch) acc[ch] += s[ch];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) c[ch] = (acc[ch] * inv) * (1.f / 255.f);
             }
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
@@ -97,23 +163,58 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     }
 }
 
-extern "C" int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
-                                       int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
-                                       int dtype, void* stream) {
+template <typename T>
+__global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
+    const int slot = blockIdx.y;
+    const float* m = p.mat + slot * 6;
+    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    const int sf = p.src_frame[slot];
+    const bool live = sf >= 0 && sf < p.n_frames;                 // anything else is an empty slot: never an address
+    const unsigned char* base = p.src + (long)(live ? sf : 0) * p.hs * p.ws * 3;
+    const int per_slot = p.hp * p.wp;
+    T* dst = (T*)p.dst + (long)slot * per_slot * 4;
+    int kx = 1, ky = 1;                                           // workgroup-uniform; the plain entry never pays for the square roots
+    if (p.max_taps > 1 && live) { kx = crop_taps(m0, m3, p.max_taps); ky = crop_taps(m1, m4, p.max_taps); }
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    // 64 pixels of a crop row cross 64 * |m3| frame rows: from 16 on the tiled walk reads fewer cache lines per load (measured: EXPERIMENTS.md)
+    if (kx * ky == 1) crop_pixels<T, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false);
+    else crop_pixels<T, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, fabsf(m3) >= 0.25f);
+}
+
+// Both entries: ``who`` names the entry in the error text, max_taps = 1 is the plain crop.
+static int frames_crop_launch(const char* who, const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w,
+                              int pad, int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                              int max_taps, int dtype, void* stream) {
     LH_REQUIRE(frames_u8 && out && mean3 && std3 && mat_dev && src_frame_dev && b > 0 && b <= 65535 && n_frames > 0 && hs > 0 && ws > 0
-               && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "lh_frames_crop_to_nhwc4: bad arguments");
-    LH_REQUIRE(lh_dtype_size(dtype) > 0, "lh_frames_crop_to_nhwc4: unsupported dtype %d", dtype);
-    LH_REQUIRE(((uintptr_t)out & 7) == 0, "lh_frames_crop_to_nhwc4: out must be 8-byte aligned");
+               && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "%s: bad arguments", who);
+    LH_REQUIRE(max_taps >= 1 && max_taps <= 8, "%s: max_taps must be 1..8, not %d", who, max_taps);
+    LH_REQUIRE(lh_dtype_size(dtype) > 0, "%s: unsupported dtype %d", who, dtype);
+    LH_REQUIRE(((uintptr_t)out & 7) == 0, "%s: out must be 8-byte aligned", who);
     CropArgs a;
     a.src = frames_u8; a.dst = out; a.mat = mat_dev; a.src_frame = src_frame_dev;
     a.n_frames = n_frames; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
+    a.max_taps = max_taps;
     // one slot's pixels and one frame's bytes are 32-bit quantities; the frame BUFFER is indexed with long (64 frames of 1080p pass 2^31)
-    LH_REQUIRE((long)a.hp * wp < (1L << 29) && (long)hs * ws * 3 < (1L << 31), "lh_frames_crop_to_nhwc4: crop or frame too large for 32-bit pixel indices");
+    LH_REQUIRE((long)a.hp * wp < (1L << 29) && (long)hs * ws * 3 < (1L << 31), "%s: crop or frame too large for 32-bit pixel indices", who);
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
     const int chunks = lh_grid((long)a.hp * wp, 1024);
     LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((frames_crop_kernel<T>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a));
-    LH_LAUNCH_CHECK("frames_crop_to_nhwc4 launch");
+    LH_LAUNCH_CHECK(max_taps > 1 ? "frames_crop_area_to_nhwc4 launch" : "frames_crop_to_nhwc4 launch");
     return LH_OK;
+}
+
+extern "C" int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
+                                       int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                       int dtype, void* stream) {
+    return frames_crop_launch("lh_frames_crop_to_nhwc4", frames_u8, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
+                              src_frame_dev, 1, dtype, stream);
+}
+
+extern "C" int lh_frames_crop_area_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w,
+                                            int pad, int wp, const float* mean3, const float* std3, const float* mat_dev,
+                                            const int* src_frame_dev, int max_taps, int dtype, void* stream) {
+    return frames_crop_launch("lh_frames_crop_area_to_nhwc4", frames_u8, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
+                              src_frame_dev, max_taps, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ keypoints -> next box

@@ -947,7 +947,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             m3, s3) + extra + (self.dt,), what + (" + ColorJitter" if jitter else ""))
         return self.img_u8
 
-    def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False):
+    def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False,
+                        max_taps=1):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
@@ -956,7 +957,11 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         -1 = empty slot), lh_frames_crop_to_nhwc4 samples the frames through them, normalises and writes the stem's padded NHWC4
         input.  run_forward(mirrored=True) still replaces only the launch that writes img_nhwc4.  ``oriented=True``: the plan also
         owns ``rot`` (fp32 [n][2], the frame direction of each crop's +x axis, (1, 0) = upright until the caller writes it) and
-        ``mirror`` (int32 [n], 0), and lh_roi_affine writes ``crop_mat`` in lh_box_affine's place.  Returns the frame buffer."""
+        ``mirror`` (int32 [n], 0), and lh_roi_affine writes ``crop_mat`` in lh_box_affine's place.  ``max_taps`` 2..8: the image
+        launch is lh_frames_crop_area_to_nhwc4, which averages up to max_taps x max_taps samples over each crop pixel's footprint
+        where a ROI is minified (topdown.crop_taps_host); 1: the launches above, unchanged.  Returns the frame buffer."""
+        if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
+            raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
         self.frames_u8 = self._alloc(n_frames, hs, ws, 3, dtype=torch.uint8, zero=True)
         self.boxes = self._alloc(self.n, 4, dtype=torch.float32)
         self.boxes.copy_(torch.tensor([-0.5, -0.5, ws - 0.5, hs - 0.5], dtype=torch.float32, device=self.device).expand(self.n, 4))
@@ -969,9 +974,14 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         self.keep += [m3, s3]
         i = self._image_call_index
         slane = self.fwd[i].slane
-        self.fwd[i] = _Call(self.lib.lh_frames_crop_to_nhwc4, (
-            self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3, s3,
-            self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt), "frame crop input pipeline")
+        if max_taps > 1:
+            self.fwd[i] = _Call(self.lib.lh_frames_crop_area_to_nhwc4, (
+                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
+                s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt), "antialiased frame crop input pipeline")
+        else:
+            self.fwd[i] = _Call(self.lib.lh_frames_crop_to_nhwc4, (
+                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
+                s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt), "frame crop input pipeline")
         self.rot = self.mirror = None
         if oriented:
             self.rot = self._alloc(self.n, 2, dtype=torch.float32)

@@ -94,10 +94,23 @@ def _check_beta(soft_argmax_beta):
         raise ValueError(f"soft_argmax_beta must be a finite number > 0, not {soft_argmax_beta!r}")
 
 
-def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side):
-    """InferStep / InferPipeline(frames=, box_padding=, track*=): refuse what cannot run, before any device work.  Returns the
-    (n_frames, hs, ws) tuple of ints, or None."""
+def _antialias_taps(antialias):
+    """InferStep / InferPipeline(antialias=): False -> 1 (the plain crop), True -> 8, an integer 1..8 -> itself: the most samples per
+    crop pixel and axis (lh_frames_crop_area_to_nhwc4's max_taps)."""
+    if isinstance(antialias, bool):
+        return 8 if antialias else 1
+    if not isinstance(antialias, numbers.Integral) or not 1 <= antialias <= 8:
+        raise ValueError(f"antialias must be False, True (= 8) or an integer 1..8, not {antialias!r}")
+    return int(antialias)
+
+
+def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side, antialias=False):
+    """InferStep / InferPipeline(frames=, box_padding=, track*=, antialias=): refuse what cannot run, before any device work.  Returns
+    the (n_frames, hs, ws) tuple of ints, or None."""
+    taps = _antialias_taps(antialias)
     if frames is None:
+        if antialias is not False:
+            raise ValueError(f"antialias={antialias!r} samples hand ROIs on full frames ({taps} taps): pass frames=(n_frames, hs, ws)")
         if track:
             raise ValueError("track=True follows hand boxes on full frames: pass frames=(n_frames, hs, ws)")
         return None
@@ -519,17 +532,24 @@ class InferStep:
     from the raw keypoints (a filtered ROI lags).  ``dt`` (fp32 [batch], seconds since the slot's previous frame, 1/30 until
     written; ``dt=`` takes a tensor or one number) is an input.  One call is one frame.  A slot that is empty, or lost under
     ``track=True``, passes its keypoints through and starts fresh when it is found again; ``reset_filter(slots=None)`` does the same
-    by hand (a scene cut, a new hand in the slot)."""
+    by hand (a scene cut, a new hand in the slot).
+    ``antialias=True`` (= 8) or an integer 1..8, on top of ``frames=``: the crop launch becomes lh_frames_crop_area_to_nhwc4, which
+    averages up to that many samples per axis over each crop pixel's footprint wherever a ROI is minified (more than 1 + 1/64 frame
+    pixels per crop pixel; topdown.crop_taps_host gives the counts, topdown.frames_crop_host the rule), so the network does not see
+    texture that aliases with every sub-pixel move of the box.  A ROI that is not minified is cropped bit for bit as before, and
+    ``False`` / 1 is the step as it was.  The matrix, the map-back and the flip test's mirror are untouched, so it composes with
+    every option above; ``step.antialias`` keeps the number."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
                  frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0,
-                 oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None):
+                 oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None, antialias=False):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
-        frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side)
+        frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias)
+        self.antialias = _antialias_taps(antialias)                 # samples per crop pixel and axis at most; 1 = the plain crop
         smooth = _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
@@ -553,7 +573,7 @@ class InferStep:
             self.track_axis, self.track_min_axis = (int(track_axis[0]), int(track_axis[1])), float(track_min_axis)
         if frames:
             self.images = None                                      # the inputs of such a step are frames / boxes / frame_index
-            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented)
+            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias)
             self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
             self.rot, self.mirror = self.plan.rot, self.plan.mirror
             self.crop_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
@@ -701,6 +721,7 @@ class InferPipeline:
     ``submit(frames=, boxes=, frame_index=)`` fills them (``steps[i]`` gives a slot's ``valid`` / ``next_boxes`` / ``lost``).
     ``oriented`` / ``track_axis`` / ``track_min_axis`` / ``smooth``: as InferStep's; every slot owns its ROIs and its filter state
     (one slot is one video stream: ``submit(rot=, mirror=, dt=)``, ``steps[i].smooth_preds`` / ``next_rot`` / ``reset_filter()``).
+    ``antialias``: as InferStep's, for every slot.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -709,16 +730,18 @@ class InferPipeline:
 
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
                  blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
-                 track_min_joints=8, track_min_side=16.0, oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None):
+                 track_min_joints=8, track_min_side=16.0, oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None,
+                 antialias=False):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side), oriented,
-                   track_axis, track_min_axis, smooth)
+        _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias),
+                   oriented, track_axis, track_min_axis, smooth)
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
                                 shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
                                 soft_argmax_beta=soft_argmax_beta, frames=frames, box_padding=box_padding, track=track,
                                 track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side,
-                                oriented=oriented, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth)
+                                oriented=oriented, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth,
+                                antialias=antialias)
                       for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth

@@ -4,7 +4,7 @@ decoded and taken back to frame coordinates, and the next frame's boxes are the 
 captured graph plus one device-to-device copy per frame, no host arithmetic in between (runtime.InferStep(frames=..., track=True)).
 
     track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
-                    [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME]
+                    [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME] [--antialias [N]]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -17,8 +17,9 @@ the boxes move from frame to frame and some slots are lost -- the loop runs as i
 ``--oriented`` follows oriented ROIs (InferStep(oriented=True): the crop is turned so that wrist -> middle-finger MCP points up),
 ``--mirror`` marks every second hand as a left one (its crop is mirrored; needs ``--oriented``), ``--one_euro MIN_CUTOFF BETA``
 filters the keypoints (InferStep(smooth=...)); the line then also gives the mean distance between ``preds`` and ``smooth_preds``.
-``--spin DEG_PER_FRAME`` turns every synthetic constellation about its centre.  With none of the four the sequence and the line are
-what they were; the new keys appear only with the new options."""
+``--spin DEG_PER_FRAME`` turns every synthetic constellation about its centre.  ``--antialias [N]`` averages up to N (8 when N is left
+out) samples per axis over each crop pixel's footprint where a ROI is minified (InferStep(antialias=N)).  With none of the five the
+sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
 import time
@@ -48,6 +49,8 @@ def build_parser():
     ap.add_argument("--mirror", action="store_true", help="every second hand is a left one: its crop is mirrored (needs --oriented)")
     ap.add_argument("--one_euro", nargs=2, type=float, default=None, metavar=("MIN_CUTOFF", "BETA"), help="One-Euro filter of the keypoints")
     ap.add_argument("--spin", default=0.0, type=float, metavar="DEG_PER_FRAME", help="turn each synthetic constellation about its centre")
+    ap.add_argument("--antialias", nargs="?", type=int, const=8, default=None, metavar="N",
+                    help="area sampling of minified ROIs: at most N (1..8, default 8) samples per crop pixel and axis")
     return ap
 
 
@@ -96,6 +99,8 @@ def main(argv=None):
         ap.error("--hands must be >= 1")
     if args.mirror and not args.oriented:
         ap.error("--mirror needs --oriented")
+    if args.antialias is not None and not 1 <= args.antialias <= 8:
+        ap.error("--antialias takes 1..8")
     hs, ws = args.frame_size
     frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed, spin=args.spin)
     torch.manual_seed(args.seed)
@@ -104,6 +109,8 @@ def main(argv=None):
     options = dict(frames=(1, hs, ws), flip_test=args.flip_test, post_process="dark" if args.dark_decode else False)
     if args.oriented:
         options["oriented"] = True
+    if args.antialias is not None:
+        options["antialias"] = args.antialias
     mirror = torch.arange(args.hands, dtype=torch.int32) % 2 if args.mirror else None
     seq = torch.from_numpy(frames).pin_memory()
     probe = InferStep(model, args.hands, args.size, args.size, **options)
@@ -144,6 +151,8 @@ def main(argv=None):
         result["smooth_mean_dist"] = float(moved) / args.synthetic
     if args.spin:
         result["spin"] = args.spin
+    if args.antialias is not None:
+        result["antialias"] = args.antialias
     print(json.dumps(result))
     return result
 

@@ -10,7 +10,10 @@ tests check the geometry on them, the GPU tests check the kernels against them.
 Oriented, mirrored ROIs and the One-Euro filter (lh_roi_affine / lh_keypoints_to_rois / lh_one_euro, InferStep(oriented=True, smooth=...))
 follow the same pattern: ``roi_affine`` / ``rois_from_keypoints`` / ``one_euro`` on device tensors, ``*_host`` in numpy, ``one_euro_host64``
 the filter's recurrence in fp64.  An orientation is a direction vector -- the frame direction of the crop's +x axis, (1, 0) = upright --
-never an angle: the kernels use + - * /, sqrt, abs and comparisons only, which numpy rounds as the device does."""
+never an angle: the kernels use + - * /, sqrt, abs and comparisons only, which numpy rounds as the device does.
+
+The antialiased crop of minified ROIs (lh_frames_crop_area_to_nhwc4, InferStep(antialias=...)): ``frames_crop`` on device tensors,
+``crop_taps_host`` / ``frames_crop_host`` in numpy -- with ``max_taps=1`` the plain crop's sampling rule."""
 import numpy as np
 
 F = np.float32
@@ -34,6 +37,74 @@ def box_affine_host(boxes, frame_index, n_frames, size, padding):
         mat = np.stack([a, zero, (cx - sw * F(0.5)) + a * F(0.5), zero, a, (cy - sh * F(0.5)) + a * F(0.5)], 1).astype(np.float32)
     mat[~ok] = 0
     return mat, np.where(ok, fi, -1).astype(np.int32)
+
+
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def crop_taps_host(mat, max_taps=8):
+    """mat [b][6] -> int32 [b][2] = (kx, ky), the samples lh_frames_crop_area_to_nhwc4 averages per crop pixel along the crop's x and y
+    axes: sx = sqrt(m0*m0 + m3*m3) frame pixels per crop pixel, kx = min(max_taps, ceil(min(sx, 64))) where sx > 1 + 1/64 and is
+    finite, otherwise 1 (not minified, NaN, or a matrix that samples nothing); ky likewise from (m1, m4)."""
+    if not 1 <= int(max_taps) <= 8:
+        raise ValueError(f"max_taps must be 1..8, not {max_taps!r}")
+    m = np.asarray(mat, np.float32).reshape(-1, 6)
+    out = np.ones((m.shape[0], 2), np.int32)
+    with np.errstate(all="ignore"):
+        for axis, (a, b) in enumerate(((m[:, 0], m[:, 3]), (m[:, 1], m[:, 4]))):
+            s = np.sqrt(a * a + b * b)
+            many = (s > F(1.015625)) & np.isfinite(s)
+            k = np.minimum(int(max_taps), np.ceil(np.minimum(np.where(many, s, F(1)), F(64))).astype(np.int32))
+            out[:, axis] = np.where(many, k, 1)
+    return out
+
+
+def _sample_host(img, hs, ws, fx, fy):
+    """One bilinear sample per element of fx / fy on the raw 0..255 values of img fp32 [3][hs][ws], the crop kernel's: -> (fp32
+    [3][...], inside mask); outside the frame (NaN included) the sample is 0."""
+    with np.errstate(all="ignore"):
+        inside = (fx >= F(-0.5)) & (fx <= F(ws) - F(0.5)) & (fy >= F(-0.5)) & (fy <= F(hs) - F(0.5))
+    cy = np.where(inside, np.maximum(fy, F(0)), F(0)).astype(np.float32)
+    cx = np.where(inside, np.maximum(fx, F(0)), F(0)).astype(np.float32)
+    y0, x0 = np.minimum(cy.astype(np.int32), hs - 1), np.minimum(cx.astype(np.int32), ws - 1)
+    y1, x1 = np.minimum(y0 + 1, hs - 1), np.minimum(x0 + 1, ws - 1)
+    wy, wx = cy - y0.astype(np.float32), cx - x0.astype(np.float32)
+    a00, a01, a10, a11 = img[:, y0, x0], img[:, y0, x1], img[:, y1, x0], img[:, y1, x1]
+    top, bot = a00 + (a01 - a00) * wx, a10 + (a11 - a10) * wx
+    return np.where(inside, top + (bot - top) * wy, F(0)).astype(np.float32), inside
+
+
+def frames_crop_host(frames, mat, src_frame, size, max_taps=1, mean=MEAN, std=STD):
+    """uint8 frames [n][hs][ws][3], mat [b][6], src_frame [b], size = (h, w) of the crop -> normalised fp32 [b][3][h][w];
+    lh_frames_crop_area_to_nhwc4 in numpy (``max_taps=1``: lh_frames_crop_to_nhwc4), fp32 in the kernel's order: per slot
+    (kx, ky) = crop_taps_host, per pixel the kx * ky samples at ux = ox + (2*i + 1 - kx) / (2*kx), uy likewise (j outside, i inside)
+    are summed on the raw 0..255 values, a sample outside the frame adding 0, then (acc * (1 / (kx*ky))) * (1/255) and Normalize."""
+    frames = np.asarray(frames)
+    n, hs, ws = frames.shape[:3]
+    h, w = int(size[0]), int(size[1])
+    mat = np.asarray(mat, np.float32).reshape(-1, 6)
+    src = np.asarray(src_frame, np.int32).reshape(-1)
+    taps = crop_taps_host(mat, max_taps)
+    mean, istd = np.asarray(mean, np.float32)[:, None, None], F(1) / np.asarray(std, np.float32)[:, None, None]
+    oy, ox = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
+    out = np.empty((len(src), 3, h, w), np.float32)
+    for s in range(len(src)):
+        acc = np.zeros((3, h, w), np.float32)
+        kx, ky = int(taps[s, 0]), int(taps[s, 1])
+        if 0 <= src[s] < n:
+            m0, m1, m2, m3, m4, m5 = mat[s]
+            img = np.transpose(frames[src[s]].astype(np.float32), (2, 0, 1))
+            with np.errstate(all="ignore"):
+                for j in range(ky):
+                    uy = oy + F(2 * j + 1 - ky) / F(2 * ky)
+                    for i in range(kx):
+                        ux = ox + F(2 * i + 1 - kx) / F(2 * kx)
+                        acc += _sample_host(img, hs, ws, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5)[0]
+        else:
+            kx = ky = 1
+        c = (acc * (F(1) / F(kx * ky))) * (F(1) / F(255))
+        out[s] = (c - mean) * istd
+    return out
 
 
 def boxes_from_keypoints_host(preds, maxvals, boxes, src_frame, min_score=0.1, min_joints=8, min_side=16.0):
@@ -211,6 +282,36 @@ def box_affine(boxes, frame_index, n_frames, size, padding=1.25):
         _lib.check(_lib.load().lh_box_affine(boxes.data_ptr(), frame_index.data_ptr(), b, int(n_frames), int(size[0]), int(size[1]),
                                              float(padding), mat.data_ptr(), src.data_ptr(), _stream()), "lh_box_affine")
     return mat, src
+
+
+def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD):
+    """Device tensors frames uint8 [n][hs][ws][3], mat fp32 [b][6], src_frame int32 [b] -> the normalised crops as NHWC4
+    [b][h][w][4] of ``dtype`` (torch.float32 by default; no padding, channel 3 is 0) for an h x w = ``size`` crop: one
+    lh_frames_crop_area_to_nhwc4 launch on the current stream.  ``max_taps`` 1..8: the most samples per crop pixel and axis that a
+    minified ROI averages (crop_taps_host); 1 is the plain crop."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
+        raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
+    dtype = dtype or torch.float32
+    frames = frames.contiguous()
+    mat = mat.to(torch.float32).contiguous()
+    src_frame = src_frame.to(torch.int32).contiguous()
+    b = mat.shape[0]
+    if (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,)
+            or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
+        raise _lib.LightHandError(f"frames_crop: frames uint8 [n, hs, ws, 3], mat [b, 6] and src_frame [b] on one device, got "
+                                  f"{tuple(frames.shape)} {frames.dtype} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
+    n, hs, ws = frames.shape[:3]
+    h, w = int(size[0]), int(size[1])
+    out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.load().lh_frames_crop_area_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, n, hs, ws, h, w, 0, w, m3, s3, mat.data_ptr(),
+                                                            src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
+                   "lh_frames_crop_area_to_nhwc4")
+    return out
 
 
 def boxes_from_keypoints(preds, maxvals, boxes, src_frame, min_score=0.1, min_joints=8, min_side=16.0):

@@ -6,7 +6,9 @@ lh_keypoints_to_boxes] and swap the uint8 input kernel for lh_frames_crop_to_nhw
 199 MB of frames.  Two more legs price the oriented ROIs and the One-Euro filter against the track=True leg of the same run:
 oriented + track swaps lh_box_affine / lh_keypoints_to_boxes for lh_roi_affine / lh_keypoints_to_rois (seeded directions, every second
 box mirrored), oriented + track + smooth adds the lh_one_euro launch; the upright leg runs the oriented kernels with rot = (1, 0) and
-no mirror, which separates the cost of the two sibling launches from that of gathering along turned rows.  Device events around `steps` replays, after a warm-up; median
+no mirror, which separates the cost of the two sibling launches from that of gathering along turned rows.  Two legs price the
+antialiased crop (antialias=True: lh_frames_crop_area_to_nhwc4 in the crop's place) against the frames leg: with the boxes above
+(187..625 frame px into 256: 1..3 samples per axis) and with large boxes of half extent 300..500 px (3..5 per axis).  Device events around `steps` replays, after a warm-up; median
 over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
@@ -46,6 +48,9 @@ def main():
     index = (torch.arange(batch, dtype=torch.int32) // 2).cuda()
     rot = torch.from_numpy(rng.normal(size=(batch, 2)).astype(np.float32)).cuda()
     mirror = (torch.arange(batch, dtype=torch.int32) % 2).cuda()
+    # a hand close to the camera: half extents of 300..500 px (drawn after everything above, which keeps its numbers)
+    half_l = rng.uniform(300, 500, size=(batch, 1))
+    large = torch.from_numpy(np.concatenate([centre - half_l, centre + half_l], 1).astype(np.float32)).cuda()
 
     forms = {"uint8 crops": InferStep(model, batch, size, size, input_u8=(size, size)),
              "frames": InferStep(model, batch, size, size, frames=(n_frames, hs, ws)),
@@ -53,13 +58,21 @@ def main():
              "oriented+track": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True),
              "oriented upright": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True),
              "oriented+track+smooth": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True,
-                                                smooth=(1.0, 0.007))}
+                                                smooth=(1.0, 0.007)),
+             "frames+antialias": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), antialias=True),
+             "frames+antialias large": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), antialias=True)}
     forms["uint8 crops"](crops)
     for tag in ("frames", "frames+track"):
         forms[tag](frames=frames, boxes=boxes, frame_index=index)
     for tag in ("oriented+track", "oriented+track+smooth"):
         forms[tag](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
     forms["oriented upright"](frames=frames, boxes=boxes, frame_index=index)
+    forms["frames+antialias"](frames=frames, boxes=boxes, frame_index=index)
+    forms["frames+antialias large"](frames=frames, boxes=large, frame_index=index)
+    from lighthand_amd.topdown import crop_taps_host
+    for tag in ("frames+antialias", "frames+antialias large"):
+        taps = crop_taps_host(forms[tag].plan.crop_mat.cpu().numpy())
+        print(f"  {tag}: {int(taps.min())}..{int(taps.max())} samples per axis, {float(taps.prod(1).mean()):.1f} per crop pixel on average", flush=True)
     for step in forms.values():
         timed(step, 10)                                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
@@ -69,8 +82,8 @@ def main():
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
     for tag, v in ms.items():
-        print(f"  {tag:21s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops, "
-              f"{med[tag] - med['frames+track']:+.3f} vs frames+track; rounds: {', '.join(f'{x:.3f}' for x in v)})", flush=True)
+        print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops, {med[tag] - med['frames']:+.3f} "
+              f"vs frames, {med[tag] - med['frames+track']:+.3f} vs frames+track; rounds: {', '.join(f'{x:.3f}' for x in v)})", flush=True)
 
 
 if __name__ == "__main__":
