@@ -114,6 +114,28 @@ int lh_frames_crop_to_nhwc4(const unsigned char* frames_u8, void* out, int b, in
 int lh_frames_crop_area_to_nhwc4(const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w, int pad,
                                  int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
                                  int max_taps, int dtype, void* stream);
+/* The NV12 sibling (opt-in; the same kernel, the two entries above keep their output bits): the frames are what a video decoder
+ * writes, 8-bit 4:2:0 with interleaved chroma, and the colour conversion runs per sample on the ROI only.  Frame f starts at byte
+ * f * frame_stride of frames_nv12; luma byte (x, y) is at y*pitch + x; Cb and Cr of chroma sample (cx, cy) are at
+ * uv_offset + cy*pitch + 2*cx and that address + 1; wc = ws/2, hc = hs/2.  The tight layout is pitch = ws, uv_offset = hs*ws,
+ * frame_stride = hs*ws*3/2; a decoder surface has pitch >= ws and uv_offset = pitch * aligned_height.  csc12 is a HOST float[12]
+ * copied by value: k[3][3] row-major, then o[3].  max_taps 1..8 as lh_frames_crop_area_to_nhwc4's (1: the plain crop).  Every sample
+ * at (fx, fy) -- the pixel's centre or one tap of the area rule -- fp32, in this order: the inside test and the lower clamp to 0 of
+ * the RGB entries give (cx_, cy_); Y is their bilinear sample of one channel on the luma plane (same indices, upper index clamp,
+ * weights wx, wy and blend top + (bot - top) * wy); gx = chroma_siting == 0 ? cx_ * 0.5f : (cx_ - 0.5f) * 0.5f,
+ * gy = (cy_ - 0.5f) * 0.5f (siting 0, "left": chroma co-sited with the even luma columns, the H.264 / HEVC default; 1, "center":
+ * between them, JPEG / MPEG-1; vertically centred in both), gx = fminf(fmaxf(gx, 0), wc-1), gy = fminf(fmaxf(gy, 0), hc-1); U and V
+ * are the same blend on the chroma plane at (gx, gy) with x0 = min((int)gx, wc-1), x1 = min(x0+1, wc-1) and y likewise;
+ * e0 = Y - o[0], e1 = U - o[1], e2 = V - o[2], s[c] = fminf(fmaxf((k[c][0]*e0 + k[c][1]*e1) + k[c][2]*e2, 0.f), 255.f).  s is then
+ * the RGB entries' sample: * (1/255) or the tap sum and (acc * inv) * (1/255), Normalize, the store; a sample outside the frame or
+ * NaN, an empty slot (which never forms an address), padding and channel 3 behave as there.  Frames with CbCr = 128 and k[c][0] = 1,
+ * o[0] = 0 give the RGB entries' bits on the grey frames.  LH_ERR_ARG, before any device work: hs, ws odd or < 2; pitch < ws;
+ * uv_offset < pitch*hs; uv_offset + (hc-1)*pitch + ws > frame_stride; frame_stride >= 2^31; chroma_siting outside {0, 1}; a
+ * coefficient that is not finite; max_taps, dtype and alignment as above. */
+int lh_frames_crop_yuv_to_nhwc4(const unsigned char* frames_nv12, void* out, int b, int n_frames, int hs, int ws, int pitch,
+                                int uv_offset, long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad, int wp,
+                                const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev, int max_taps,
+                                int dtype, void* stream);
 /* preds_dev fp32 [b][j][2] (frame coordinates), maxvals_dev fp32 [b][j] -> next_boxes_dev fp32 [b][4], lost_dev int32 [b]: the bounds
  * of the keypoints with maxval >= min_score, each side widened about its centre to at least min_side.  With fewer than min_joints
  * such keypoints, or for an empty slot (src_frame < 0), next_boxes[i] = boxes[i] and lost[i] = 1; otherwise lost[i] = 0.  No

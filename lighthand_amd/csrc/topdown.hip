@@ -67,6 +67,21 @@ extern "C" int lh_box_affine(const float* boxes_dev, const int* frame_index_dev,
 // tap loops are uniform, no divergence.  Texels are byte loads as in the plain crop: the taps of a pixel and of its neighbours share
 // cache lines, and the frame's reuse is the L2's.  Which pixel a thread takes does not enter the rule: a slot whose crop rows run
 // across the frame's rows is walked in 8 x 8 tiles (crop_pixels).
+//
+// NV12 frames (lh_frames_crop_yuv_to_nhwc4): the same kernel, format is a workgroup-uniform switch in front of the pixel loops, so the
+// RGB entries run the bodies they always ran.  Frame f starts at byte f * frame_stride; luma byte (x, y) is at y*pitch + x, Cb and Cr of
+// chroma sample (cx, cy) at uv_offset + cy*pitch + 2*cx and + 1; wc = ws/2, hc = hs/2.  Every sample at (fx, fy) -- the pixel's centre
+// or one tap of the area rule -- passes the RGB inside test and lower clamp (cx_, cy_), then, fp32 in this order:
+//     Y    = the RGB sample of one channel on the luma plane: same indices, upper index clamp, weights and blend
+//     gx   = siting == 0 ? cx_ * 0.5f : (cx_ - 0.5f) * 0.5f, gy = (cy_ - 0.5f) * 0.5f       (0: chroma co-sited with even luma
+//            columns, 1: centred between them; vertically always centred)
+//     gx   = fminf(fmaxf(gx, 0), wc-1), gy = fminf(fmaxf(gy, 0), hc-1)
+//     U, V = the same blend on the chroma plane at (gx, gy): x0 = min((int)gx, wc-1), x1 = min(x0+1, wc-1), y likewise
+//     e    = (Y - o[0], U - o[1], V - o[2]),  s[c] = fminf(fmaxf((k[c][0]*e0 + k[c][1]*e1) + k[c][2]*e2, 0.f), 255.f)
+// and s is the RGB path's sample from there on (* 1/255 or the tap sum, Normalize, store).  topdown.py: frames_crop_nv12_host.
+// A sample reads 4 luma and 8 chroma bytes; the highest one is uv_offset + (hc-1)*pitch + ws - 1 < frame_stride (checked on the host).
+enum { LH_FRAMES_RGB = 0, LH_FRAMES_NV12 = 1 };
+
 struct CropArgs {
     const unsigned char* src;
     void* dst;
@@ -75,6 +90,9 @@ struct CropArgs {
     int n_frames, hs, ws, h, w, pad, hp, wp;
     float mean[3], istd[3];
     int max_taps;
+    int format, pitch, uv_offset, siting;                         // NV12 only from here (format = LH_FRAMES_RGB: not read)
+    long frame_stride;
+    float k[9], o[3];
 };
 
 // One bilinear sample of the frame at (fx, fy) on the raw 0..255 values; false (s untouched) outside the frame or for a NaN.
@@ -96,6 +114,45 @@ __device__ __forceinline__ bool crop_sample(const unsigned char* base, int hs, i
     return true;
 }
 
+// The NV12 sibling (the rule: above): base is the frame's first luma byte.  One frame's bytes are a 32-bit quantity (frame_stride < 2^31).
+// csc = k[9], o[3] in VECTOR registers (frames_crop_kernel).
+__device__ __forceinline__ bool crop_sample_nv12(const CropArgs& p, const float* csc, const unsigned char* base, float fx, float fy,
+                                                 float s[3]) {
+    const int hs = p.hs, ws = p.ws, pitch = p.pitch;
+    if (!(fx >= -0.5f && fx <= ws - 0.5f && fy >= -0.5f && fy <= hs - 0.5f)) return false;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    float yuv[3];
+    {
+        const int y0 = min((int)fy, hs - 1), x0 = min((int)fx, ws - 1);
+        const int y1 = y0 + 1 < hs ? y0 + 1 : hs - 1, x1 = x0 + 1 < ws ? x0 + 1 : ws - 1;
+        const float wy = fy - y0, wx = fx - x0;
+        const float a00 = base[y0 * pitch + x0], a01 = base[y0 * pitch + x1];
+        const float a10 = base[y1 * pitch + x0], a11 = base[y1 * pitch + x1];
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        yuv[0] = top + (bot - top) * wy;
+    }
+    const int hc = hs >> 1, wc = ws >> 1;
+    float gx = p.siting == 0 ? fx * 0.5f : (fx - 0.5f) * 0.5f, gy = (fy - 0.5f) * 0.5f;
+    gx = fminf(fmaxf(gx, 0.f), (float)(wc - 1));
+    gy = fminf(fmaxf(gy, 0.f), (float)(hc - 1));
+    const int y0 = min((int)gy, hc - 1), x0 = min((int)gx, wc - 1);
+    const int y1 = min(y0 + 1, hc - 1), x1 = min(x0 + 1, wc - 1);
+    const float wy = gy - y0, wx = gx - x0;
+    const unsigned char* uv = base + p.uv_offset;
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+        const float a00 = uv[y0 * pitch + 2 * x0 + ch], a01 = uv[y0 * pitch + 2 * x1 + ch];
+        const float a10 = uv[y1 * pitch + 2 * x0 + ch], a11 = uv[y1 * pitch + 2 * x1 + ch];
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        yuv[1 + ch] = top + (bot - top) * wy;
+    }
+    const float e0 = yuv[0] - csc[9], e1 = yuv[1] - csc[10], e2 = yuv[2] - csc[11];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c] = fminf(fmaxf((csc[c * 3] * e0 + csc[c * 3 + 1] * e1) + csc[c * 3 + 2] * e2, 0.f), 255.f);
+    return true;
+}
+
 __device__ __forceinline__ int crop_taps(float a, float b, int max_taps) {
     const float s = sqrtf(a * a + b * b);
     return s > 1.015625f && isfinite(s) ? min(max_taps, (int)ceilf(fminf(s, 64.f))) : 1;
@@ -103,10 +160,17 @@ __device__ __forceinline__ int crop_taps(float a, float b, int max_taps) {
 
 // The pixels of one slot.  AREA = false is the plain crop, one sample at the pixel's centre: the loop the kernel always had, kept apart
 // from the tap loops so that it compiles to what it was.  AREA = true: a live slot, kx x ky samples over the pixel's footprint.
-template <typename T, bool AREA>
+// NV12 picks the sample function, nothing else: the walk, the tap offsets, the accumulation and the store are shared.
+template <bool NV12>
+__device__ __forceinline__ bool crop_sample_of(const CropArgs& p, const float* csc, const unsigned char* base, float fx, float fy, float s[3]) {
+    if constexpr (NV12) return crop_sample_nv12(p, csc, base, fx, fy, s);
+    else return crop_sample(base, p.hs, p.ws, fx, fy, s);
+}
+
+template <typename T, bool AREA, bool NV12>
 __device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned char* base, bool live, T* dst, int first, int stride,
                                             int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky,
-                                            bool tiled) {
+                                            bool tiled, const float* csc = nullptr) {
     const float fkx2 = (float)(2 * kx), fky2 = (float)(2 * ky), inv = 1.f / (float)(kx * ky);
     // AREA, tiled (the slot's choice, below): a wave takes an 8 x 8 tile of the output instead of 64 pixels of a row, so that its samples
     // stay within a square of the frame (a row of a turned ROI is a slanted line across many frame rows: a cache line per lane and load)
@@ -129,7 +193,7 @@ __device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned ch
             float c[3] = {0.f, 0.f, 0.f};
             if constexpr (!AREA) {
                 float s[3];
-                if (live && crop_sample(base, p.hs, p.ws, (m0 * ox + m1 * oy) + m2, (m3 * ox + m4 * oy) + m5, s)) {   // NaN: black
+                if (live && crop_sample_of<NV12>(p, csc, base, (m0 * ox + m1 * oy) + m2, (m3 * ox + m4 * oy) + m5, s)) {   // NaN: black
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) c[ch] = s[ch] * (1.f / 255.f);
                 }
@@ -140,7 +204,7 @@ __device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned ch
                     for (int t = 0; t < kx; ++t) {
                         const float ux = (float)ox + (float)(2 * t + 1 - kx) / fkx2;
                         float s[3];
-                        if (crop_sample(base, p.hs, p.ws, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, s)) {
+                        if (crop_sample_of<NV12>(p, csc, base, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, s)) {
 #pragma unroll
                             for (int ch = 0; ch < 3; ++ch) acc[ch] += s[ch];
                         }
@@ -170,21 +234,42 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
     const int sf = p.src_frame[slot];
     const bool live = sf >= 0 && sf < p.n_frames;                 // anything else is an empty slot: never an address
-    const unsigned char* base = p.src + (long)(live ? sf : 0) * p.hs * p.ws * 3;
+    const bool nv12 = p.format == LH_FRAMES_NV12;                 // workgroup-uniform: one branch in front of the pixel loops
+    const unsigned char* base = p.src + (nv12 ? (long)(live ? sf : 0) * p.frame_stride : (long)(live ? sf : 0) * p.hs * p.ws * 3);
     const int per_slot = p.hp * p.wp;
     T* dst = (T*)p.dst + (long)slot * per_slot * 4;
     int kx = 1, ky = 1;                                           // workgroup-uniform; the plain entry never pays for the square roots
     if (p.max_taps > 1 && live) { kx = crop_taps(m0, m3, p.max_taps); ky = crop_taps(m1, m4, p.max_taps); }
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     // 64 pixels of a crop row cross 64 * |m3| frame rows: from 16 on the tiled walk reads fewer cache lines per load (measured: EXPERIMENTS.md)
-    if (kx * ky == 1) crop_pixels<T, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false);
-    else crop_pixels<T, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, fabsf(m3) >= 0.25f);
+    const bool tiled = fabsf(m3) >= 0.25f;
+    if (nv12) {
+        // the 12 coefficients live in vector registers: as scalars they take the kernel past 100 SGPRs, and the RGB entries, which never
+        // read them, from 8 waves a SIMD to 7 (measured on the turned legs of tools/topdown_cost.py: EXPERIMENTS.md)
+        float csc[12];
+#pragma unroll
+        for (int c = 0; c < 12; ++c) {
+            csc[c] = c < 9 ? p.k[c] : p.o[c - 9];
+            asm volatile("" : "+v"(csc[c]));
+        }
+        if (kx * ky == 1) crop_pixels<T, false, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc);
+        else crop_pixels<T, true, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc);
+    } else if (kx * ky == 1) crop_pixels<T, false, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false);
+    else crop_pixels<T, true, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled);
 }
 
-// Both entries: ``who`` names the entry in the error text, max_taps = 1 is the plain crop.
+// What the NV12 entry adds to the RGB ones' arguments.
+struct Nv12Layout {
+    int pitch, uv_offset;
+    long frame_stride;
+    int siting;
+    const float* csc12;
+};
+
+// All entries: ``who`` names the entry in the error text, max_taps = 1 is the plain crop, yuv = nullptr packed RGB frames.
 static int frames_crop_launch(const char* who, const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w,
                               int pad, int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
-                              int max_taps, int dtype, void* stream) {
+                              int max_taps, int dtype, void* stream, const Nv12Layout* yuv = nullptr) {
     LH_REQUIRE(frames_u8 && out && mean3 && std3 && mat_dev && src_frame_dev && b > 0 && b <= 65535 && n_frames > 0 && hs > 0 && ws > 0
                && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "%s: bad arguments", who);
     LH_REQUIRE(max_taps >= 1 && max_taps <= 8, "%s: max_taps must be 1..8, not %d", who, max_taps);
@@ -194,12 +279,33 @@ static int frames_crop_launch(const char* who, const unsigned char* frames_u8, v
     a.src = frames_u8; a.dst = out; a.mat = mat_dev; a.src_frame = src_frame_dev;
     a.n_frames = n_frames; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
     a.max_taps = max_taps;
+    a.format = yuv ? LH_FRAMES_NV12 : LH_FRAMES_RGB;
+    a.pitch = a.uv_offset = a.siting = 0; a.frame_stride = 0;
+    for (int c = 0; c < 9; ++c) a.k[c] = 0.f;
+    a.o[0] = a.o[1] = a.o[2] = 0.f;
     // one slot's pixels and one frame's bytes are 32-bit quantities; the frame BUFFER is indexed with long (64 frames of 1080p pass 2^31)
-    LH_REQUIRE((long)a.hp * wp < (1L << 29) && (long)hs * ws * 3 < (1L << 31), "%s: crop or frame too large for 32-bit pixel indices", who);
+    LH_REQUIRE((long)a.hp * wp < (1L << 29) && (yuv || (long)hs * ws * 3 < (1L << 31)), "%s: crop or frame too large for 32-bit pixel indices",
+               who);
+    if (yuv) {
+        LH_REQUIRE(yuv->csc12, "%s: bad arguments", who);
+        LH_REQUIRE(hs >= 2 && ws >= 2 && hs % 2 == 0 && ws % 2 == 0, "%s: NV12 frames have even sides >= 2, not %d x %d", who, hs, ws);
+        LH_REQUIRE(yuv->pitch >= ws, "%s: pitch %d is below the frame's width %d", who, yuv->pitch, ws);
+        LH_REQUIRE(yuv->uv_offset >= (long)yuv->pitch * hs, "%s: uv_offset %d lies inside the luma plane (pitch * hs = %ld)", who,
+                   yuv->uv_offset, (long)yuv->pitch * hs);
+        LH_REQUIRE(yuv->frame_stride < (1L << 31), "%s: frame_stride %ld does not fit 32-bit byte indices", who, yuv->frame_stride);
+        LH_REQUIRE(yuv->uv_offset + (long)(hs / 2 - 1) * yuv->pitch + ws <= yuv->frame_stride,
+                   "%s: the chroma plane (uv_offset %d, %d rows of pitch %d) does not end inside frame_stride %ld", who, yuv->uv_offset, hs / 2,
+                   yuv->pitch, yuv->frame_stride);
+        LH_REQUIRE(yuv->siting == 0 || yuv->siting == 1, "%s: chroma_siting must be 0 (left) or 1 (center), not %d", who, yuv->siting);
+        for (int c = 0; c < 12; ++c) LH_REQUIRE(yuv->csc12[c] - yuv->csc12[c] == 0.f, "%s: csc12[%d] is not finite", who, c);
+        a.pitch = yuv->pitch; a.uv_offset = yuv->uv_offset; a.frame_stride = yuv->frame_stride; a.siting = yuv->siting;
+        for (int c = 0; c < 9; ++c) a.k[c] = yuv->csc12[c];
+        for (int c = 0; c < 3; ++c) a.o[c] = yuv->csc12[9 + c];
+    }
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
     const int chunks = lh_grid((long)a.hp * wp, 1024);
     LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((frames_crop_kernel<T>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a));
-    LH_LAUNCH_CHECK(max_taps > 1 ? "frames_crop_area_to_nhwc4 launch" : "frames_crop_to_nhwc4 launch");
+    LH_LAUNCH_CHECK(yuv ? "frames_crop_yuv_to_nhwc4 launch" : max_taps > 1 ? "frames_crop_area_to_nhwc4 launch" : "frames_crop_to_nhwc4 launch");
     return LH_OK;
 }
 
@@ -215,6 +321,15 @@ extern "C" int lh_frames_crop_area_to_nhwc4(const unsigned char* frames_u8, void
                                             const int* src_frame_dev, int max_taps, int dtype, void* stream) {
     return frames_crop_launch("lh_frames_crop_area_to_nhwc4", frames_u8, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
                               src_frame_dev, max_taps, dtype, stream);
+}
+
+extern "C" int lh_frames_crop_yuv_to_nhwc4(const unsigned char* frames_nv12, void* out, int b, int n_frames, int hs, int ws, int pitch,
+                                           int uv_offset, long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad,
+                                           int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                           int max_taps, int dtype, void* stream) {
+    const Nv12Layout yuv = {pitch, uv_offset, frame_stride, chroma_siting, csc12};
+    return frames_crop_launch("lh_frames_crop_yuv_to_nhwc4", frames_nv12, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
+                              src_frame_dev, max_taps, dtype, stream, &yuv);
 }
 
 // ------------------------------------------------------------------------------------------------ keypoints -> next box

@@ -948,7 +948,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         return self.img_u8
 
     def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False,
-                        max_taps=1):
+                        max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
@@ -959,10 +959,23 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         owns ``rot`` (fp32 [n][2], the frame direction of each crop's +x axis, (1, 0) = upright until the caller writes it) and
         ``mirror`` (int32 [n], 0), and lh_roi_affine writes ``crop_mat`` in lh_box_affine's place.  ``max_taps`` 2..8: the image
         launch is lh_frames_crop_area_to_nhwc4, which averages up to max_taps x max_taps samples over each crop pixel's footprint
-        where a ROI is minified (topdown.crop_taps_host); 1: the launches above, unchanged.  Returns the frame buffer."""
+        where a ROI is minified (topdown.crop_taps_host); 1: the launches above, unchanged.  ``frame_format="nv12"``: ``frames_u8``
+        is a decoder's output, uint8 [n_frames][rows][pitch] in ``frame_layout`` (topdown.nv12_layout's tuple; None: the tight
+        layout), and the image launch is lh_frames_crop_yuv_to_nhwc4 for every max_taps: ``yuv`` ((standard, range) or 12
+        coefficients: topdown.yuv_matrix) and ``chroma_siting`` ("left" / "center") convert each sample; the zero-filled buffer
+        decodes to a defined colour.  "rgb": the plan and its launches as above.  Returns the frame buffer."""
+        from . import topdown
         if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
             raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
-        self.frames_u8 = self._alloc(n_frames, hs, ws, 3, dtype=torch.uint8, zero=True)
+        if frame_format not in ("rgb", "nv12"):
+            raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
+        if frame_format == "nv12":
+            pitch, uv_offset, frame_stride, rows = topdown._check_layout(hs, ws, frame_layout)
+            csc, siting = (C.c_float * 12)(*topdown._csc12(yuv).tolist()), topdown.chroma_siting_code(chroma_siting)
+            self.keep.append(csc)
+            self.frames_u8 = self._alloc(n_frames, rows, pitch, dtype=torch.uint8, zero=True)
+        else:
+            self.frames_u8 = self._alloc(n_frames, hs, ws, 3, dtype=torch.uint8, zero=True)
         self.boxes = self._alloc(self.n, 4, dtype=torch.float32)
         self.boxes.copy_(torch.tensor([-0.5, -0.5, ws - 0.5, hs - 0.5], dtype=torch.float32, device=self.device).expand(self.n, 4))
         self.frame_index = self._alloc(self.n, dtype=torch.int32)
@@ -974,7 +987,12 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         self.keep += [m3, s3]
         i = self._image_call_index
         slane = self.fwd[i].slane
-        if max_taps > 1:
+        if frame_format == "nv12":
+            self.fwd[i] = _Call(self.lib.lh_frames_crop_yuv_to_nhwc4, (
+                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, pitch, uv_offset, frame_stride, siting, csc,
+                self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt),
+                "NV12 frame crop input pipeline" + (", antialiased" if max_taps > 1 else ""))
+        elif max_taps > 1:
             self.fwd[i] = _Call(self.lib.lh_frames_crop_area_to_nhwc4, (
                 self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
                 s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt), "antialiased frame crop input pipeline")

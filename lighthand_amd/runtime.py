@@ -13,7 +13,7 @@ import numbers
 
 import torch
 
-from . import _lib, heatmap
+from . import _lib, heatmap, topdown
 from ._lib import LightHandError, check
 from .amp import DynamicLossScale
 from .optim import Adam
@@ -104,11 +104,30 @@ def _antialias_taps(antialias):
     return int(antialias)
 
 
-def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side, antialias=False):
-    """InferStep / InferPipeline(frames=, box_padding=, track*=, antialias=): refuse what cannot run, before any device work.  Returns
-    the (n_frames, hs, ws) tuple of ints, or None."""
+_FRAME_DEFAULTS = dict(frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None)
+
+
+def _is_frame_default(key, value):
+    default = _FRAME_DEFAULTS[key]
+    if default is None or isinstance(default, str):
+        return value is None if default is None else value == default
+    return isinstance(value, (tuple, list)) and tuple(value) == default
+
+
+def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side, antialias=False, frame_format="rgb",
+                  yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
+    """InferStep / InferPipeline(frames=, box_padding=, track*=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=): refuse
+    what cannot run, before any device work.  Returns the (n_frames, hs, ws) tuple of ints, or None."""
     taps = _antialias_taps(antialias)
+    given = dict(frame_format=frame_format, yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout)
+    if not isinstance(frame_format, str) or frame_format not in ("rgb", "nv12"):
+        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
+    topdown._csc12(yuv)
+    topdown.chroma_siting_code(chroma_siting)
     if frames is None:
+        for key, value in given.items():
+            if not _is_frame_default(key, value):
+                raise ValueError(f"{key}={value!r} describes full frames: pass frames=(n_frames, hs, ws)")
         if antialias is not False:
             raise ValueError(f"antialias={antialias!r} samples hand ROIs on full frames ({taps} taps): pass frames=(n_frames, hs, ws)")
         if track:
@@ -122,6 +141,12 @@ def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, m
         raise ValueError(f"frames must be (n_frames, hs, ws), three positive integers, not {frames!r}")
     if not _is_number(box_padding) or box_padding <= 0:
         raise ValueError(f"box_padding must be a finite number > 0, not {box_padding!r}")
+    if frame_format == "nv12":
+        topdown._check_layout(int(frames[1]), int(frames[2]), frame_layout)
+    else:
+        for key in ("yuv", "chroma_siting", "frame_layout"):
+            if not _is_frame_default(key, given[key]):
+                raise ValueError(f"{key}={given[key]!r} describes NV12 frames: pass frame_format='nv12'")
     if track:
         if not _is_number(min_score):
             raise ValueError(f"track_min_score must be a finite number, not {min_score!r}")
@@ -538,18 +563,30 @@ class InferStep:
     pixels per crop pixel; topdown.crop_taps_host gives the counts, topdown.frames_crop_host the rule), so the network does not see
     texture that aliases with every sub-pixel move of the box.  A ROI that is not minified is cropped bit for bit as before, and
     ``False`` / 1 is the step as it was.  The matrix, the map-back and the flip test's mirror are untouched, so it composes with
-    every option above; ``step.antialias`` keeps the number."""
+    every option above; ``step.antialias`` keeps the number.
+    ``frame_format="nv12"``, on top of ``frames=``: ``frames`` is what a video decoder or a camera stack hands over, uint8
+    [n_frames][rows][pitch] -- hs rows of luma, then hs/2 rows of interleaved CbCr, on a row pitch that may be wider than ws
+    (``frame_layout`` = topdown.nv12_layout(hs, ws, pitch, luma_rows); None: the tight layout, rows = hs*3/2, pitch = ws) -- and the
+    crop launch becomes lh_frames_crop_yuv_to_nhwc4: every sample, the single one or each tap under ``antialias``, reads luma and
+    bilinear chroma and is converted to RGB on the spot, so no pass over whole frames runs.  ``yuv=(standard, range)`` ("bt601" /
+    "bt709", "limited" / "full"; or 12 coefficients: topdown.yuv_matrix) picks the conversion, ``chroma_siting`` "left" (H.264 / HEVC)
+    or "center" (JPEG / MPEG-1) where the chroma samples sit.  hs and ws must be even.  topdown.frames_crop_nv12_host states the
+    rule; the matrix and everything after the crop are untouched, so it composes with every option above.  ``step.frame_format``
+    keeps the choice; "rgb" is the step as it was."""
 
     _serial = 0
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
                  frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0,
-                 oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None, antialias=False):
+                 oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None, antialias=False, frame_format="rgb",
+                 yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
-        frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias)
+        frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias,
+                               frame_format, yuv, chroma_siting, frame_layout)
         self.antialias = _antialias_taps(antialias)                 # samples per crop pixel and axis at most; 1 = the plain crop
+        self.frame_format = frame_format if frames else None        # "rgb" / "nv12": what ``frames`` holds
         smooth = _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
@@ -573,7 +610,11 @@ class InferStep:
             self.track_axis, self.track_min_axis = (int(track_axis[0]), int(track_axis[1])), float(track_min_axis)
         if frames:
             self.images = None                                      # the inputs of such a step are frames / boxes / frame_index
-            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias)
+            if frame_format == "nv12":                              # the RGB step calls use_frame_input as it always did
+                self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
+                                                        frame_format="nv12", yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout)
+            else:
+                self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias)
             self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
             self.rot, self.mirror = self.plan.rot, self.plan.mirror
             self.crop_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
@@ -722,6 +763,7 @@ class InferPipeline:
     ``oriented`` / ``track_axis`` / ``track_min_axis`` / ``smooth``: as InferStep's; every slot owns its ROIs and its filter state
     (one slot is one video stream: ``submit(rot=, mirror=, dt=)``, ``steps[i].smooth_preds`` / ``next_rot`` / ``reset_filter()``).
     ``antialias``: as InferStep's, for every slot.
+    ``frame_format`` / ``yuv`` / ``chroma_siting`` / ``frame_layout``: as InferStep's; every slot owns its NV12 buffer.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -731,17 +773,19 @@ class InferPipeline:
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
                  blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
                  track_min_joints=8, track_min_side=16.0, oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None,
-                 antialias=False):
+                 antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias),
+        _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias,
+                                        frame_format, yuv, chroma_siting, frame_layout),
                    oriented, track_axis, track_min_axis, smooth)
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
                                 shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
                                 soft_argmax_beta=soft_argmax_beta, frames=frames, box_padding=box_padding, track=track,
                                 track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side,
                                 oriented=oriented, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth,
-                                antialias=antialias)
+                                antialias=antialias, frame_format=frame_format, yuv=yuv, chroma_siting=chroma_siting,
+                                frame_layout=frame_layout)
                       for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth

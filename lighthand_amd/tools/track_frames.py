@@ -5,6 +5,7 @@ captured graph plus one device-to-device copy per frame, no host arithmetic in b
 
     track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
                     [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME] [--antialias [N]]
+                    [--frame_format nv12 [--yuv_matrix bt601|bt709] [--yuv_range limited|full] [--chroma_siting left|center]]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -18,8 +19,10 @@ the boxes move from frame to frame and some slots are lost -- the loop runs as i
 ``--mirror`` marks every second hand as a left one (its crop is mirrored; needs ``--oriented``), ``--one_euro MIN_CUTOFF BETA``
 filters the keypoints (InferStep(smooth=...)); the line then also gives the mean distance between ``preds`` and ``smooth_preds``.
 ``--spin DEG_PER_FRAME`` turns every synthetic constellation about its centre.  ``--antialias [N]`` averages up to N (8 when N is left
-out) samples per axis over each crop pixel's footprint where a ROI is minified (InferStep(antialias=N)).  With none of the five the
-sequence and the line are what they were; the new keys appear only with the new options."""
+out) samples per axis over each crop pixel's footprint where a ROI is minified (InferStep(antialias=N)).  ``--frame_format nv12`` hands
+the step what a video decoder does: the synthetic frames are encoded to NV12 on the host (topdown.rgb_to_nv12_host, with
+``--yuv_matrix`` / ``--yuv_range``) and the crop converts each sample back (InferStep(frame_format="nv12", yuv=..., chroma_siting=...)).
+With none of the six the sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
 import time
@@ -51,6 +54,10 @@ def build_parser():
     ap.add_argument("--spin", default=0.0, type=float, metavar="DEG_PER_FRAME", help="turn each synthetic constellation about its centre")
     ap.add_argument("--antialias", nargs="?", type=int, const=8, default=None, metavar="N",
                     help="area sampling of minified ROIs: at most N (1..8, default 8) samples per crop pixel and axis")
+    ap.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12"], help="what the frame buffer holds: packed RGB or NV12")
+    ap.add_argument("--yuv_matrix", default="bt709", choices=["bt601", "bt709"], help="luma coefficients of NV12 frames")
+    ap.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
+    ap.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
     return ap
 
 
@@ -111,6 +118,14 @@ def main(argv=None):
         options["oriented"] = True
     if args.antialias is not None:
         options["antialias"] = args.antialias
+    if args.frame_format == "nv12":
+        from lighthand_amd.topdown import rgb_to_nv12_host
+        if hs % 2 or ws % 2:
+            ap.error("--frame_format nv12 needs even frame sides")
+        frames = rgb_to_nv12_host(frames, args.yuv_matrix, args.yuv_range)
+        options.update(frame_format="nv12", yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
+    elif (args.yuv_matrix, args.yuv_range, args.chroma_siting) != ("bt709", "limited", "left"):
+        ap.error("--yuv_matrix / --yuv_range / --chroma_siting need --frame_format nv12")
     mirror = torch.arange(args.hands, dtype=torch.int32) % 2 if args.mirror else None
     seq = torch.from_numpy(frames).pin_memory()
     probe = InferStep(model, args.hands, args.size, args.size, **options)
@@ -153,6 +168,8 @@ def main(argv=None):
         result["spin"] = args.spin
     if args.antialias is not None:
         result["antialias"] = args.antialias
+    if args.frame_format == "nv12":
+        result.update(frame_format="nv12", yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range, chroma_siting=args.chroma_siting)
     print(json.dumps(result))
     return result
 

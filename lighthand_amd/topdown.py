@@ -13,7 +13,12 @@ the filter's recurrence in fp64.  An orientation is a direction vector -- the fr
 never an angle: the kernels use + - * /, sqrt, abs and comparisons only, which numpy rounds as the device does.
 
 The antialiased crop of minified ROIs (lh_frames_crop_area_to_nhwc4, InferStep(antialias=...)): ``frames_crop`` on device tensors,
-``crop_taps_host`` / ``frames_crop_host`` in numpy -- with ``max_taps=1`` the plain crop's sampling rule."""
+``crop_taps_host`` / ``frames_crop_host`` in numpy -- with ``max_taps=1`` the plain crop's sampling rule.
+
+NV12 frames (lh_frames_crop_yuv_to_nhwc4, InferStep(frames=..., frame_format="nv12")): ``yuv_matrix`` gives the conversion's 12
+coefficients, ``nv12_layout`` the buffer of a pitched surface, ``frames_crop(..., frame_format="nv12")`` is the launch,
+``frames_crop_nv12_host`` its rule in numpy (fp32, or fp64 with ``dtype=np.float64``) and ``rgb_to_nv12_host`` an encoder for the tools
+and tests."""
 import numpy as np
 
 F = np.float32
@@ -103,6 +108,176 @@ def frames_crop_host(frames, mat, src_frame, size, max_taps=1, mean=MEAN, std=ST
         else:
             kx = ky = 1
         c = (acc * (F(1) / F(kx * ky))) * (F(1) / F(255))
+        out[s] = (c - mean) * istd
+    return out
+
+
+_YUV_K = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb)
+_YUV_RANGE = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16.0), "full": (1.0, 1.0, 0.0)}          # (luma scale, chroma scale, luma offset)
+_SITING = {"left": 0, "center": 1}
+
+
+def _yuv_matrix64(standard, range):
+    if not (isinstance(standard, str) and isinstance(range, str)) or standard not in _YUV_K or range not in _YUV_RANGE:
+        raise ValueError(f"yuv_matrix: standard is one of {sorted(_YUV_K)} and range one of {sorted(_YUV_RANGE)}, not {standard!r} / {range!r}")
+    kr, kb = _YUV_K[standard]
+    kg = 1.0 - kr - kb
+    ys, cs, o0 = _YUV_RANGE[range]
+    k = np.array([[ys, 0.0, 2 * (1 - kr) * cs], [ys, -2 * (1 - kb) * kb / kg * cs, -2 * (1 - kr) * kr / kg * cs], [ys, 2 * (1 - kb) * cs, 0.0]])
+    return k, np.array([o0, 128.0, 128.0])
+
+
+def yuv_matrix(standard="bt709", range="limited"):
+    """float32 [12] = k[3][3] row-major then o[3], lh_frames_crop_yuv_to_nhwc4's csc12: rgb = k (yuv - o) on 8-bit values, for the
+    luma coefficients of ``standard`` ("bt601": Kr, Kb = 0.299, 0.114; "bt709": 0.2126, 0.0722; Kg = 1 - Kr - Kb) and ``range``
+    ("limited": Y in 16..235, CbCr in 16..240; "full": 0..255).  Computed in fp64 and rounded once."""
+    k, o = _yuv_matrix64(standard, range)
+    return np.concatenate([k.ravel(), o]).astype(np.float32)
+
+
+def chroma_siting_code(chroma_siting):
+    """"left" (chroma co-sited with the even luma columns: H.264 / HEVC) -> 0, "center" (between them: JPEG / MPEG-1) -> 1."""
+    if not isinstance(chroma_siting, str) or chroma_siting not in _SITING:
+        raise ValueError(f"chroma_siting is 'left' or 'center', not {chroma_siting!r}")
+    return _SITING[chroma_siting]
+
+
+def _csc12(yuv):
+    """yuv = (standard, range) or 12 numbers -> float32 [12]."""
+    if isinstance(yuv, (tuple, list)) and len(yuv) == 2 and all(isinstance(v, str) for v in yuv):
+        return yuv_matrix(*yuv)
+    if isinstance(yuv, str):
+        raise ValueError(f"yuv is (standard, range) or 12 coefficients, not {yuv!r}")
+    try:
+        csc = np.asarray(yuv, np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        csc = np.zeros(0, np.float32)
+    if csc.shape != (12,) or not np.isfinite(csc).all():
+        raise ValueError(f"yuv is (standard, range) or 12 finite coefficients (k[3][3] row-major, then o[3]), not {yuv!r}")
+    return csc
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def nv12_layout(hs, ws, pitch=None, luma_rows=None):
+    """The NV12 buffer of hs x ws frames -> (pitch, uv_offset, frame_stride, rows): uint8 [n][rows][pitch] per frame, ``luma_rows``
+    (>= hs, default hs) rows of luma on a row pitch of ``pitch`` (>= ws, default ws) bytes, then hs/2 rows of interleaved CbCr on the
+    same pitch: uv_offset = pitch * luma_rows, rows = luma_rows + hs/2, frame_stride = pitch * rows.  The defaults are the tight layout
+    (ws, hs*ws, hs*ws*3/2, hs*3/2); a decoder's surface passes its pitch and its aligned height."""
+    pitch = ws if pitch is None else pitch
+    luma_rows = hs if luma_rows is None else luma_rows
+    if not all(_is_int(v) for v in (hs, ws, pitch, luma_rows)) or hs < 2 or ws < 2 or hs % 2 or ws % 2:
+        raise ValueError(f"nv12_layout: NV12 frames have even integer sides >= 2, not {hs!r} x {ws!r} (pitch {pitch!r}, luma_rows {luma_rows!r})")
+    if pitch < ws or luma_rows < hs:
+        raise ValueError(f"nv12_layout: pitch {pitch} / luma_rows {luma_rows} are below the frame's {ws} / {hs}")
+    rows = int(luma_rows) + int(hs) // 2
+    if int(pitch) * rows >= 1 << 31:
+        raise ValueError(f"nv12_layout: a frame of {rows} rows of {pitch} bytes does not fit 32-bit byte indices")
+    return int(pitch), int(pitch) * int(luma_rows), int(pitch) * rows, rows
+
+
+def _check_layout(hs, ws, layout):
+    """layout = None (tight) or nv12_layout's tuple for hs x ws frames -> the tuple."""
+    if layout is None:
+        return nv12_layout(hs, ws)
+    ok = isinstance(layout, (tuple, list)) and len(layout) == 4 and all(_is_int(v) for v in layout)
+    if not ok or tuple(layout) != nv12_layout(hs, ws, layout[0], layout[3] - hs // 2):
+        raise ValueError(f"frame layout must be topdown.nv12_layout({hs}, {ws}, pitch, luma_rows)'s (pitch, uv_offset, frame_stride, rows), "
+                         f"not {layout!r}")
+    return tuple(int(v) for v in layout)
+
+
+def rgb_to_nv12_host(frames_rgb, standard="bt709", range="limited", layout=None):
+    """uint8 RGB frames [n][hs][ws][3] (even hs, ws) -> uint8 NV12 [n][rows][pitch] in ``layout`` (nv12_layout's tuple; None: tight),
+    what an encoder of ``standard`` / ``range`` followed by a decoder would hand over: yuv = k^-1 rgb + o of yuv_matrix's fp64 matrix,
+    Y = rint per pixel, Cb and Cr = rint of the mean over each 2 x 2 block, clipped to 0..255.  The bytes between the planes and beside
+    the rows are 0.  For the tools and the tests."""
+    frames = np.asarray(frames_rgb)
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
+        raise ValueError(f"rgb_to_nv12_host: frames uint8 [n][hs][ws][3], not {frames.shape} {frames.dtype}")
+    n, hs, ws = frames.shape[:3]
+    pitch, uv_offset, _, rows = _check_layout(hs, ws, layout)
+    k, o = _yuv_matrix64(standard, range)
+    yuv = frames.astype(np.float64) @ np.linalg.inv(k).T + o
+    out = np.zeros((n, rows, pitch), np.uint8)
+    out[:, :hs, :ws] = np.clip(np.rint(yuv[..., 0]), 0, 255).astype(np.uint8)
+    chroma = yuv[..., 1:].reshape(n, hs // 2, 2, ws // 2, 2, 2).mean((2, 4))
+    out[:, uv_offset // pitch:, :ws] = np.clip(np.rint(chroma), 0, 255).astype(np.uint8).reshape(n, hs // 2, ws)
+    return out
+
+
+def _sample_nv12_host(flat, hs, ws, pitch, uv_offset, siting, k, o, fx, fy, T):
+    """One sample per element of fx / fy of one NV12 frame (``flat``: its bytes as type T), lh_frames_crop_yuv_to_nhwc4's: -> (RGB on
+    0..255, type T [3][...], inside mask); outside the frame (NaN included) the sample is 0."""
+    with np.errstate(all="ignore"):
+        inside = (fx >= T(-0.5)) & (fx <= T(ws) - T(0.5)) & (fy >= T(-0.5)) & (fy <= T(hs) - T(0.5))
+    cy = np.where(inside, np.maximum(fy, T(0)), T(0)).astype(T)
+    cx = np.where(inside, np.maximum(fx, T(0)), T(0)).astype(T)
+
+    def blend(at, x0, x1, y0, y1, wx, wy):
+        a00, a01, a10, a11 = flat[at(x0, y0)], flat[at(x1, y0)], flat[at(x0, y1)], flat[at(x1, y1)]
+        top, bot = a00 + (a01 - a00) * wx, a10 + (a11 - a10) * wx
+        return top + (bot - top) * wy
+
+    y0, x0 = np.minimum(cy.astype(np.int32), hs - 1), np.minimum(cx.astype(np.int32), ws - 1)
+    y1, x1 = np.minimum(y0 + 1, hs - 1), np.minimum(x0 + 1, ws - 1)
+    lum = blend(lambda x, y: y * pitch + x, x0, x1, y0, y1, cx - x0.astype(T), cy - y0.astype(T))
+    hc, wc = hs // 2, ws // 2
+    gx = cx * T(0.5) if siting == 0 else (cx - T(0.5)) * T(0.5)
+    gy = (cy - T(0.5)) * T(0.5)
+    gx, gy = np.minimum(np.maximum(gx, T(0)), T(wc - 1)), np.minimum(np.maximum(gy, T(0)), T(hc - 1))
+    v0, u0 = np.minimum(gy.astype(np.int32), hc - 1), np.minimum(gx.astype(np.int32), wc - 1)
+    v1, u1 = np.minimum(v0 + 1, hc - 1), np.minimum(u0 + 1, wc - 1)
+    wx, wy = gx - u0.astype(T), gy - v0.astype(T)
+    cb = blend(lambda x, y: uv_offset + y * pitch + 2 * x, u0, u1, v0, v1, wx, wy)
+    cr = blend(lambda x, y: uv_offset + y * pitch + 2 * x + 1, u0, u1, v0, v1, wx, wy)
+    e0, e1, e2 = lum - o[0], cb - o[1], cr - o[2]
+    rgb = np.stack([np.minimum(np.maximum((k[c, 0] * e0 + k[c, 1] * e1) + k[c, 2] * e2, T(0)), T(255)) for c in (0, 1, 2)])
+    return np.where(inside, rgb, T(0)).astype(T), inside
+
+
+def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("bt709", "limited"), chroma_siting="left", max_taps=1,
+                          layout=None, mean=MEAN, std=STD, dtype=np.float32):
+    """uint8 NV12 frames [n][rows][pitch] of ``frame_size`` = (hs, ws) in ``layout`` (nv12_layout's tuple; None: tight), mat [b][6],
+    src_frame [b], size = (h, w) of the crop -> normalised [b][3][h][w]; lh_frames_crop_yuv_to_nhwc4 in numpy, fp32 in the kernel's order:
+    frames_crop_host's tap loop with the NV12 sample (csrc/topdown.hip's header comment) in the RGB one's place.  ``yuv`` is
+    (standard, range) or the 12 coefficients, ``chroma_siting`` "left" or "center".  ``dtype=np.float64``: the same operations in fp64
+    on the same fp32 matrices and coefficients (the tap counts stay crop_taps_host's) -- what the fp32 order is measured against."""
+    T = np.dtype(dtype).type
+    hs, ws = int(frame_size[0]), int(frame_size[1])
+    pitch, uv_offset, frame_stride, rows = _check_layout(hs, ws, layout)
+    frames = np.asarray(frames_nv12)
+    if frames.dtype != np.uint8 or frames.ndim != 3 or frames.shape[1:] != (rows, pitch):
+        raise ValueError(f"frames_crop_nv12_host: frames uint8 [n][{rows}][{pitch}], not {frames.shape} {frames.dtype}")
+    n = frames.shape[0]
+    h, w = int(size[0]), int(size[1])
+    csc = _csc12(yuv).astype(dtype)
+    k, o = csc[:9].reshape(3, 3), csc[9:]
+    siting = chroma_siting_code(chroma_siting)
+    mat = np.asarray(mat, np.float32).reshape(-1, 6)
+    src = np.asarray(src_frame, np.int32).reshape(-1)
+    taps = crop_taps_host(mat, max_taps)
+    mean, istd = np.asarray(mean, np.float32).astype(dtype)[:, None, None], (F(1) / np.asarray(std, np.float32)).astype(dtype)[:, None, None]
+    oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
+    out = np.empty((len(src), 3, h, w), dtype)
+    for s in range(len(src)):
+        acc = np.zeros((3, h, w), dtype)
+        kx, ky = int(taps[s, 0]), int(taps[s, 1])
+        if 0 <= src[s] < n:
+            m0, m1, m2, m3, m4, m5 = mat[s].astype(dtype)
+            flat = frames[src[s]].reshape(-1).astype(dtype)
+            with np.errstate(all="ignore"):
+                for j in range(ky):
+                    uy = oy + T(2 * j + 1 - ky) / T(2 * ky)
+                    for i in range(kx):
+                        ux = ox + T(2 * i + 1 - kx) / T(2 * kx)
+                        acc += _sample_nv12_host(flat, hs, ws, pitch, uv_offset, siting, k, o, (m0 * ux + m1 * uy) + m2,
+                                                 (m3 * ux + m4 * uy) + m5, T)[0]
+        else:
+            kx = ky = 1
+        c = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
         out[s] = (c - mean) * istd
     return out
 
@@ -284,21 +459,45 @@ def box_affine(boxes, frame_index, n_frames, size, padding=1.25):
     return mat, src
 
 
-def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD):
+def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD, frame_format="rgb", frame_size=None,
+                yuv=("bt709", "limited"), chroma_siting="left", layout=None):
     """Device tensors frames uint8 [n][hs][ws][3], mat fp32 [b][6], src_frame int32 [b] -> the normalised crops as NHWC4
     [b][h][w][4] of ``dtype`` (torch.float32 by default; no padding, channel 3 is 0) for an h x w = ``size`` crop: one
     lh_frames_crop_area_to_nhwc4 launch on the current stream.  ``max_taps`` 1..8: the most samples per crop pixel and axis that a
-    minified ROI averages (crop_taps_host); 1 is the plain crop."""
+    minified ROI averages (crop_taps_host); 1 is the plain crop.  ``frame_format="nv12"``: frames uint8 [n][rows][pitch] of
+    ``frame_size`` = (hs, ws) in ``layout`` (nv12_layout's tuple; None: tight), converted per sample with ``yuv`` ((standard, range)
+    or 12 coefficients) and ``chroma_siting`` ("left" / "center"): one lh_frames_crop_yuv_to_nhwc4 launch."""
     import ctypes as C
     import torch
     from . import _lib
     if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
         raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
+    if frame_format not in ("rgb", "nv12"):
+        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
     dtype = dtype or torch.float32
     frames = frames.contiguous()
     mat = mat.to(torch.float32).contiguous()
     src_frame = src_frame.to(torch.int32).contiguous()
     b = mat.shape[0]
+    if frame_format == "nv12":
+        if not (isinstance(frame_size, (tuple, list)) and len(frame_size) == 2):
+            raise ValueError(f"frame_format='nv12' needs frame_size=(hs, ws), not {frame_size!r}")
+        hs, ws = int(frame_size[0]), int(frame_size[1])
+        pitch, uv_offset, frame_stride, rows = _check_layout(hs, ws, layout)
+        csc, siting = (C.c_float * 12)(*_csc12(yuv).tolist()), chroma_siting_code(chroma_siting)
+        if (frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (rows, pitch) or frames.dim() != 3 or tuple(mat.shape) != (b, 6)
+                or tuple(src_frame.shape) != (b,) or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
+            raise _lib.LightHandError(f"frames_crop: NV12 frames uint8 [n, {rows}, {pitch}], mat [b, 6] and src_frame [b] on one device, got "
+                                      f"{tuple(frames.shape)} {frames.dtype} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
+        h, w = int(size[0]), int(size[1])
+        out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
+        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        with torch.cuda.device(frames.device):
+            _lib.check(_lib.load().lh_frames_crop_yuv_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, frames.shape[0], hs, ws, pitch, uv_offset,
+                                                               frame_stride, siting, csc, h, w, 0, w, m3, s3, mat.data_ptr(),
+                                                               src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
+                       "lh_frames_crop_yuv_to_nhwc4")
+        return out
     if (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,)
             or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
         raise _lib.LightHandError(f"frames_crop: frames uint8 [n, hs, ws, 3], mat [b, 6] and src_frame [b] on one device, got "

@@ -8,7 +8,9 @@ oriented + track swaps lh_box_affine / lh_keypoints_to_boxes for lh_roi_affine /
 box mirrored), oriented + track + smooth adds the lh_one_euro launch; the upright leg runs the oriented kernels with rot = (1, 0) and
 no mirror, which separates the cost of the two sibling launches from that of gathering along turned rows.  Two legs price the
 antialiased crop (antialias=True: lh_frames_crop_area_to_nhwc4 in the crop's place) against the frames leg: with the boxes above
-(187..625 frame px into 256: 1..3 samples per axis) and with large boxes of half extent 300..500 px (3..5 per axis).  Device events around `steps` replays, after a warm-up; median
+(187..625 frame px into 256: 1..3 samples per axis) and with large boxes of half extent 300..500 px (3..5 per axis).  Two legs price
+NV12 frames (frame_format="nv12": lh_frames_crop_yuv_to_nhwc4 in the crop's place, 100 MB of frames, tight layout, BT.709 limited)
+against the frames and the frames+antialias legs, same boxes.  Device events around `steps` replays, after a warm-up; median
 over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
@@ -61,6 +63,11 @@ def main():
                                                 smooth=(1.0, 0.007)),
              "frames+antialias": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), antialias=True),
              "frames+antialias large": InferStep(model, batch, size, size, frames=(n_frames, hs, ws), antialias=True)}
+    forms["nv12"] = InferStep(model, batch, size, size, frames=(n_frames, hs, ws), frame_format="nv12")
+    forms["nv12+antialias"] = InferStep(model, batch, size, size, frames=(n_frames, hs, ws), frame_format="nv12", antialias=True)
+    nv12 = torch.from_numpy(rng.randint(0, 256, size=(n_frames, hs * 3 // 2, ws)).astype(np.uint8)).cuda()   # drawn last: see above
+    for tag in ("nv12", "nv12+antialias"):
+        forms[tag](frames=nv12, boxes=boxes, frame_index=index)
     forms["uint8 crops"](crops)
     for tag in ("frames", "frames+track"):
         forms[tag](frames=frames, boxes=boxes, frame_index=index)
