@@ -171,6 +171,32 @@ int lh_keypoints_to_rois(const float* preds_dev, const float* maxvals_dev, const
  * multiplies |dxhat|, units of x per second). */
 int lh_one_euro(const float* x_dev, const int* src_frame_dev, const int* lost_dev, const float* dt_dev, int b, int j, float min_cutoff,
                 float beta, float d_cutoff, float* xhat_dev, float* dxhat_dev, int* init_dev, float* out_dev, void* stream);
+/* Training on hand ROIs cropped from full frames (opt-in; runtime.TrainStep(frames=..., roi_aug=...)).
+ * lh_roi_perturb: the caller's ROI (boxes_dev fp32 [b][4], rot_dev fp32 [b][2] or NULL = (1, 0), mirror_dev int32 [b] or NULL = 0) and
+ * this step's draw aug_dev fp32 [b][6] = (c, s, k, tx, ty, flip) -> the ROI that lh_roi_affine reads (boxes_out, rot_out, mirror_out).
+ * (c, s) = (cos, sin) of the drawn rotation, k the scale of the extents, (tx, ty) a shift of the centre along the ROI's own axes as a
+ * fraction of its extents, flip != 0 toggles the mirror.  One thread per slot, no atomics, no sinf / cosf; fp32 in this order:
+ *   bw = x1-x0, bh = y1-y0, cx = (x0+x1)*0.5, cy = (y0+y1)*0.5
+ *   n = sqrtf(rx*rx + ry*ry), ux = rx/n, uy = ry/n
+ *   dx = tx*bw, dy = ty*bh, cx' = cx + (dx*ux - dy*uy), cy' = cy + (dx*uy + dy*ux)
+ *   hw = (bw*k)*0.5, hh = (bh*k)*0.5, box' = (cx'-hw, cy'-hh, cx'+hw, cy'+hh)
+ *   rot' = (ux*c - uy*s, ux*s + uy*c)
+ *   mirror' = (mirror != 0) != (flip != 0) ? 1 : 0
+ * A slot whose aug row is exactly (1, 0, 1, 0, 0, 0) copies box, rot and mirror bit for bit (rot is not normalised): no augmentation
+ * is the un-augmented crop.  A box, rot or aug row that is not finite, or n not > 0, copies box, rot and mirror as well (lh_roi_affine
+ * turns such a ROI into an empty slot).  No output may be one of the inputs: LH_ERR_ARG. */
+int lh_roi_perturb(const float* boxes_dev, const float* rot_dev, const int* mirror_dev, const float* aug_dev, int b, float* boxes_out,
+                   float* rot_out, int* mirror_out, void* stream);
+/* The position lh_affine_points_inv gives the points of a slot it cannot map: every target renderer treats it as off the map (a zero
+ * plane, target weight 0). */
+#define LH_POINT_OFF (-65536.f)
+/* The twin of lh_affine_points: pts (frame coordinates, pstride floats per point) through the INVERSE of mat_dev fp32 [b][6]
+ * (crop pixel index -> frame pixel index, lh_box_affine's / lh_roi_affine's) into out (crop coordinates, ostride floats per point).
+ * One thread per point, fp32 in this order: det = m0*m4 - m1*m3, qx = x - m2, qy = y - m5, ox = (m4*qx - m1*qy) / det,
+ * oy = (m0*qy - m3*qx) / det.  An empty slot (src_frame_dev[slot] < 0), or det not finite or == 0, writes (LH_POINT_OFF,
+ * LH_POINT_OFF).  The matrix (1, 0, 0, 0, 1, 0) returns the points' own bits.  Columns past the first two are not read or written. */
+int lh_affine_points_inv(const float* pts, int pstride, const float* mat_dev, const int* src_frame_dev, float* out, int ostride, int b,
+                         int j, void* stream);
 /* NHWC (run dtype) -> NCHW fp32 heatmaps (what model(images) returns, pose_resnet.py:246)
  * and the inverse for the incoming gradient. c_stride = channel stride of the NHWC side. */
 int lh_nhwc_to_nchw_f32(const void* nhwc, float* nchw, int n, int h, int w, int c, int c_stride,

@@ -93,7 +93,16 @@ struct CropArgs {
     int format, pitch, uv_offset, siting;                         // NV12 only from here (format = LH_FRAMES_RGB: not read)
     long frame_stride;
     float k[9], o[3];
+    // The two small entries of training on frames run as modes of this kernel's fp32 instantiation (op != LH_CROP; the resource tables
+    // the tests hold the library to admit no new kernel symbol).  op is workgroup-uniform and tested once, in front of everything the
+    // crop does; the crop entries pass LH_CROP and read none of the fields below.
+    int op, n, j, pstride, ostride;
+    const float *in0, *in1, *in2;                                 // perturb: boxes, rot, aug          inverse: points, matrices, -
+    const int* iin;                                               //          mirror                            src_frame
+    float *out0, *out1;                                           //          boxes', rot'                      points', -
+    int* iout;                                                    //          mirror'                           -
 };
+enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2 };
 
 // One bilinear sample of the frame at (fx, fy) on the raw 0..255 values; false (s untouched) outside the frame or for a NaN.
 __device__ __forceinline__ bool crop_sample(const unsigned char* base, int hs, int ws, float fx, float fy, float s[3]) {
@@ -227,8 +236,85 @@ __device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned ch
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ROI augmentation (training on frames)
+// The caller's ROI and this step's draw aug = (c, s, k, tx, ty, flip) -> the ROI that lh_roi_affine turns into the crop matrix: the
+// centre moves by (tx, ty) extents along the ROI's own axes, the extents grow by k, the direction turns by (c, s) = (cos, sin) of the
+// drawn angle and flip toggles the mirror.  One thread per slot, fp32 in this order; topdown.py's roi_perturb_host restates it.
+// (A mode of frames_crop_kernel<float>, launched by lh_roi_perturb: CropArgs.)
+//     bw = x1-x0, bh = y1-y0, cx = (x0+x1)*0.5, cy = (y0+y1)*0.5,  n = sqrtf(rx*rx + ry*ry), ux = rx/n, uy = ry/n
+//     dx = tx*bw, dy = ty*bh,  cx' = cx + (dx*ux - dy*uy), cy' = cy + (dx*uy + dy*ux)
+//     hw = (bw*k)*0.5, hh = (bh*k)*0.5,  box' = (cx'-hw, cy'-hh, cx'+hw, cy'+hh)
+//     rot' = (ux*c - uy*s, ux*s + uy*c),  mirror' = (mirror != 0) != (flip != 0)
+// A row that is exactly (1, 0, 1, 0, 0, 0) copies box, rot and mirror bit for bit (rot is NOT normalised): no augmentation is the
+// un-augmented crop.  A box, rot or aug row that is not finite, or n not > 0, copies them as well: lh_roi_affine empties such a slot.
+__device__ __forceinline__ void roi_perturb_slot(int i, const float* boxes, const float* rot, const int* mirror, const float* aug,
+                                                 float* boxes_out, float* rot_out, int* mirror_out) {
+    const float x0 = boxes[i * 4], y0 = boxes[i * 4 + 1], x1 = boxes[i * 4 + 2], y1 = boxes[i * 4 + 3];
+    const float rx = rot ? rot[i * 2] : 1.f, ry = rot ? rot[i * 2 + 1] : 0.f;
+    const int mi = mirror ? mirror[i] : 0;
+    const float* a = aug + i * 6;
+    const float c = a[0], s = a[1], k = a[2], tx = a[3], ty = a[4], flip = a[5];
+    const float n = sqrtf(rx * rx + ry * ry);
+    const bool same = c == 1.f && s == 0.f && k == 1.f && tx == 0.f && ty == 0.f && flip == 0.f;
+    const bool ok = isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && isfinite(rx) && isfinite(ry) && n > 0.f && isfinite(c)
+                    && isfinite(s) && isfinite(k) && isfinite(tx) && isfinite(ty) && isfinite(flip);
+    if (same || !ok) {
+        boxes_out[i * 4] = x0; boxes_out[i * 4 + 1] = y0; boxes_out[i * 4 + 2] = x1; boxes_out[i * 4 + 3] = y1;
+        rot_out[i * 2] = rx; rot_out[i * 2 + 1] = ry;
+        mirror_out[i] = mi;
+        return;
+    }
+    const float bw = x1 - x0, bh = y1 - y0;
+    const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f;
+    const float ux = rx / n, uy = ry / n;
+    const float dx = tx * bw, dy = ty * bh;
+    const float ncx = cx + (dx * ux - dy * uy), ncy = cy + (dx * uy + dy * ux);
+    const float hw = (bw * k) * 0.5f, hh = (bh * k) * 0.5f;
+    boxes_out[i * 4] = ncx - hw; boxes_out[i * 4 + 1] = ncy - hh; boxes_out[i * 4 + 2] = ncx + hw; boxes_out[i * 4 + 3] = ncy + hh;
+    rot_out[i * 2] = ux * c - uy * s; rot_out[i * 2 + 1] = ux * s + uy * c;
+    mirror_out[i] = ((mi != 0) != (flip != 0.f)) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------ frame -> crop for the joints
+// The twin of lh_affine_points: frame coordinates through the INVERSE of the slot's crop matrix (crop -> frame), so that the target of
+// a training step on frames is rendered where the crop kernel put the hand.  One thread per point, fp32 in this order
+// (topdown.py: affine_points_inv_host):
+//     det = m0*m4 - m1*m3, qx = x - m2, qy = y - m5,  ox = (m4*qx - m1*qy) / det, oy = (m0*qy - m3*qx) / det
+// An empty slot (src_frame < 0), or det not finite or == 0, writes (LH_POINT_OFF, LH_POINT_OFF): off every target renderer's map.
+// The matrix (1, 0, 0, 0, 1, 0) returns the points' own bits.  Columns past the first two are neither read nor written.
+// (The other mode of frames_crop_kernel<float>, launched by lh_affine_points_inv.)
+__device__ __forceinline__ void affine_points_inv_point(int i, const float* pts, int pstride, const float* mat, const int* src_frame,
+                                                        float* out, int ostride, int j) {
+    const int slot = i / j;
+    const float* m = mat + slot * 6;
+    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    const float det = m0 * m4 - m1 * m3;
+    float ox = LH_POINT_OFF, oy = LH_POINT_OFF;
+    if (src_frame[slot] >= 0 && isfinite(det) && det != 0.f) {
+        const float qx = pts[(long)i * pstride] - m2, qy = pts[(long)i * pstride + 1] - m5;
+        ox = (m4 * qx - m1 * qy) / det;
+        oy = (m0 * qy - m3 * qx) / det;
+    }
+    out[(long)i * ostride] = ox;
+    out[(long)i * ostride + 1] = oy;
+}
+
+// The modes' thread: one slot or one point.
+__device__ __forceinline__ void crop_aux_modes(const CropArgs& p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n) return;
+    if (p.op == LH_CROP_ROI_PERTURB) roi_perturb_slot(i, p.in0, p.in1, p.iin, p.in2, p.out0, p.out1, p.iout);
+    else affine_points_inv_point(i, p.in0, p.pstride, p.in1, p.iin, p.out0, p.ostride, p.j);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
+    if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the two modes (CropArgs)
+        if (p.op != LH_CROP) {
+            crop_aux_modes(p);
+            return;
+        }
+    }
     const int slot = blockIdx.y;
     const float* m = p.mat + slot * 6;
     const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
@@ -279,6 +365,8 @@ static int frames_crop_launch(const char* who, const unsigned char* frames_u8, v
     a.src = frames_u8; a.dst = out; a.mat = mat_dev; a.src_frame = src_frame_dev;
     a.n_frames = n_frames; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
     a.max_taps = max_taps;
+    a.op = LH_CROP; a.n = a.j = a.pstride = a.ostride = 0;
+    a.in0 = a.in1 = a.in2 = nullptr; a.iin = nullptr; a.out0 = a.out1 = nullptr; a.iout = nullptr;
     a.format = yuv ? LH_FRAMES_NV12 : LH_FRAMES_RGB;
     a.pitch = a.uv_offset = a.siting = 0; a.frame_stride = 0;
     for (int c = 0; c < 9; ++c) a.k[c] = 0.f;
@@ -330,6 +418,34 @@ extern "C" int lh_frames_crop_yuv_to_nhwc4(const unsigned char* frames_nv12, voi
     const Nv12Layout yuv = {pitch, uv_offset, frame_stride, chroma_siting, csc12};
     return frames_crop_launch("lh_frames_crop_yuv_to_nhwc4", frames_nv12, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
                               src_frame_dev, max_taps, dtype, stream, &yuv);
+}
+
+// ------------------------------------------------------------------------------------------------ training on frames: the two modes
+extern "C" int lh_roi_perturb(const float* boxes_dev, const float* rot_dev, const int* mirror_dev, const float* aug_dev, int b,
+                              float* boxes_out, float* rot_out, int* mirror_out, void* stream) {
+    LH_REQUIRE(boxes_dev && aug_dev && boxes_out && rot_out && mirror_out && b > 0, "lh_roi_perturb: bad arguments");
+    LH_REQUIRE(boxes_out != boxes_dev && rot_out != rot_dev && mirror_out != mirror_dev && (const void*)boxes_out != (const void*)aug_dev
+               && (const void*)rot_out != (const void*)aug_dev && (const void*)rot_out != (const void*)boxes_dev
+               && (const void*)boxes_out != (const void*)rot_dev, "lh_roi_perturb: the outputs must not alias the inputs");
+    CropArgs a = {};
+    a.op = LH_CROP_ROI_PERTURB; a.n = b;
+    a.in0 = boxes_dev; a.in1 = rot_dev; a.in2 = aug_dev; a.iin = mirror_dev; a.out0 = boxes_out; a.out1 = rot_out; a.iout = mirror_out;
+    hipLaunchKernelGGL((frames_crop_kernel<float>), dim3((b + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    LH_LAUNCH_CHECK("roi_perturb launch");
+    return LH_OK;
+}
+
+
+extern "C" int lh_affine_points_inv(const float* pts, int pstride, const float* mat_dev, const int* src_frame_dev, float* out, int ostride,
+                                    int b, int j, void* stream) {
+    LH_REQUIRE(pts && mat_dev && src_frame_dev && out && pstride >= 2 && ostride >= 2 && b > 0 && j > 0 && (long)b * j < (1L << 30),
+               "lh_affine_points_inv: bad arguments");
+    CropArgs a = {};
+    a.op = LH_CROP_POINTS_INV; a.n = b * j; a.j = j; a.pstride = pstride; a.ostride = ostride;
+    a.in0 = pts; a.in1 = mat_dev; a.iin = src_frame_dev; a.out0 = out;
+    hipLaunchKernelGGL((frames_crop_kernel<float>), dim3((b * j + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    LH_LAUNCH_CHECK("affine_points_inv launch");
+    return LH_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ keypoints -> next box

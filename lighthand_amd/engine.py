@@ -948,7 +948,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         return self.img_u8
 
     def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False,
-                        max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
+                        max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, perturb=False):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
@@ -963,7 +963,11 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         is a decoder's output, uint8 [n_frames][rows][pitch] in ``frame_layout`` (topdown.nv12_layout's tuple; None: the tight
         layout), and the image launch is lh_frames_crop_yuv_to_nhwc4 for every max_taps: ``yuv`` ((standard, range) or 12
         coefficients: topdown.yuv_matrix) and ``chroma_siting`` ("left" / "center") convert each sample; the zero-filled buffer
-        decodes to a defined colour.  "rgb": the plan and its launches as above.  Returns the frame buffer."""
+        decodes to a defined colour.  "rgb": the plan and its launches as above.  ``perturb=True`` (training on frames with ROI
+        augmentation; implies the oriented launch, a turned ROI needs it): the plan also owns ``roi_aug`` (fp32 [n][6] = c, s, k, tx,
+        ty, flip per slot, identity rows until the caller writes: ``runtime.sample_roi_aug``) and ``roi_boxes`` / ``roi_rot`` /
+        ``roi_mirror``, the perturbed ROI; lh_roi_perturb runs in front of lh_roi_affine, which reads the perturbed ROI, and the
+        caller's ``boxes`` / ``rot`` / ``mirror`` are never written.  False: the launch list as above.  Returns the frame buffer."""
         from . import topdown
         if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
             raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
@@ -1000,14 +1004,28 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             self.fwd[i] = _Call(self.lib.lh_frames_crop_to_nhwc4, (
                 self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
                 s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt), "frame crop input pipeline")
-        self.rot = self.mirror = None
-        if oriented:
+        self.rot = self.mirror = self.roi_aug = self.roi_boxes = self.roi_rot = self.roi_mirror = None
+        if oriented or perturb:
             self.rot = self._alloc(self.n, 2, dtype=torch.float32)
             self.rot.copy_(torch.tensor([1.0, 0.0], dtype=torch.float32, device=self.device).expand(self.n, 2))
             self.mirror = self._alloc(self.n, dtype=torch.int32, zero=True)
+            roi = (self.boxes, self.rot, self.mirror)
+            if perturb:
+                self.roi_aug = self._alloc(self.n, 6, dtype=torch.float32)
+                self.roi_aug.copy_(torch.tensor(topdown.ROI_AUG_IDENTITY, dtype=torch.float32, device=self.device).expand(self.n, 6))
+                self.roi_boxes = self._alloc(self.n, 4, dtype=torch.float32, zero=True)
+                self.roi_rot = self._alloc(self.n, 2, dtype=torch.float32, zero=True)
+                self.roi_mirror = self._alloc(self.n, dtype=torch.int32, zero=True)
+                roi = (self.roi_boxes, self.roi_rot, self.roi_mirror)
             self.fwd.insert(i, _Call(self.lib.lh_roi_affine, (
-                self.boxes.data_ptr(), self.rot.data_ptr(), self.mirror.data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h,
+                roi[0].data_ptr(), roi[1].data_ptr(), roi[2].data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h,
                 self.w, float(padding), self.crop_mat.data_ptr(), self.src_frame.data_ptr()), "oriented hand ROI -> crop matrix"))
+            if perturb:
+                self.fwd.insert(i, _Call(self.lib.lh_roi_perturb, (
+                    self.boxes.data_ptr(), self.rot.data_ptr(), self.mirror.data_ptr(), self.roi_aug.data_ptr(), self.n,
+                    self.roi_boxes.data_ptr(), self.roi_rot.data_ptr(), self.roi_mirror.data_ptr()), "hand ROI augmentation"))
+                self.fwd[i].slane = slane
+                i += 1
         else:
             self.fwd.insert(i, _Call(self.lib.lh_box_affine, (
                 self.boxes.data_ptr(), self.frame_index.data_ptr(), self.n, n_frames, self.h, self.w, float(padding),

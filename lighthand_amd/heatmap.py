@@ -90,6 +90,44 @@ def generate_target(joints, device="cuda", return_weight=False, unbiased=False):
     return render_targets(j[None], unbiased=unbiased)[0].cpu()
 
 
+def render_targets_host(joints, size=HEATMAP_SIZE, weighted=False, unbiased=False):
+    """The three renderers in numpy (lh_gaussian_target, lh_gaussian_target_w, lh_gaussian_target_sub): joints [B, J, >=2] (column 2,
+    when present and ``weighted``, is the visibility) -> (target fp32 [B, J, size, size], weight fp32 [B, J, 1]; ones when not
+    ``weighted``).  The window and the skip test are the kernel's, in fp32: centre int(v * 0.25 + 0.5) truncated toward zero, a patch
+    wholly outside the map is skipped, weight = (vis > 0.5 ? vis : 0) x (not skipped), a joint of weight 0 gets a zero map.  The
+    quantised value is the patch's, the unbiased one exp(-(d^2) / (2 sigma^2)) around v * 0.25 (numpy's expf: the last bit may differ
+    from the device's)."""
+    F = np.float32
+    jt = np.asarray(joints, np.float32)
+    b, nj = jt.shape[:2]
+    out, weight = np.zeros((b, nj, size, size), np.float32), np.ones((b, nj, 1), np.float32)
+    patch = gaussian_patch_host()
+    ys, xs = np.mgrid[0:size, 0:size]
+    for i in range(b):
+        for k in range(nj):
+            jx, jy = jt[i, k, 0], jt[i, k, 1]
+            mx, my = int(jx * F(0.25) + F(0.5)), int(jy * F(0.25) + F(0.5))
+            x0, y0, x1, y1 = mx - RADIUS, my - RADIUS, mx + RADIUS + 1, my + RADIUS + 1
+            skip = x0 >= size or y0 >= size or x1 < 0 or y1 < 0
+            draw = not skip
+            if weighted:
+                v = jt[i, k, 2] if jt.shape[2] >= 3 else F(1)
+                weight[i, k, 0] = (v if v > 0.5 else F(0)) * F(0 if skip else 1)
+                draw = weight[i, k, 0] > 0
+            if not draw:
+                continue
+            inside = (xs >= x0) & (xs < x1) & (ys >= y0) & (ys < y1)
+            if unbiased:
+                dx, dy = xs.astype(np.float32) - jx * F(0.25), ys.astype(np.float32) - jy * F(0.25)
+                val = np.exp(-(dx * dx + dy * dy) / F(2 * SIGMA * SIGMA)).astype(np.float32)
+            else:
+                val = np.zeros((size, size), np.float32)
+                iy0, iy1, ix0, ix1 = max(0, y0), min(y1, size), max(0, x0), min(x1, size)
+                val[iy0:iy1, ix0:ix1] = patch[iy0 - y0:iy1 - y0, ix0 - x0:ix1 - x0]
+            out[i, k] = np.where(inside, val, F(0))
+    return out, weight
+
+
 class GenerateHeatmap:
     """The reference's alternate renderer (src/utils/dataset_loader.py:22-53), same constructor and call: points
     ``[num_parts, >=2]`` already in heat-map coordinates -> float32 ``[num_parts, res, res]`` (CPU, like the reference);

@@ -186,20 +186,111 @@ def _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth):
     return float(min_cutoff), float(beta), float(d_cutoff)
 
 
+def sample_roi_aug(n, rotation=0.0, scale=0.0, shift=0.0, mirror_prob=0.0, prob=1.0, mask=None, generator=None):
+    """Per-slot random perturbation of a hand ROI (host side, seeded like ``sample_affine``), the rows of Plan.roi_aug that lh_roi_perturb
+    reads: angle ~ U[-rotation, rotation] degrees (positive turns the crop's +x axis towards the frame's +y, topdown.rot_from_angle's
+    sign), k ~ U[1-scale, 1+scale] on the ROI's extents, tx, ty ~ U[-shift, shift] as fractions of the ROI's extents along its own
+    axes, flip ~ Bernoulli(mirror_prob).  A slot is drawn with probability ``prob`` and only where ``mask`` (bool [n], optional) is
+    set; the others -- and every slot when all four factors are 0 -- get the exact identity row (1, 0, 1, 0, 0, 0), which the kernel
+    copies bit for bit.  (c, s) = (cos, sin) are formed in float64 and rounded to fp32.
+    Returns a CPU fp32 tensor [n][6] = (c, s, k, tx, ty, flip)."""
+    u = torch.rand(n, 6, generator=generator, dtype=torch.float64)
+    theta = torch.deg2rad((2 * u[:, 0] - 1) * rotation)
+    k = 1 + (2 * u[:, 1] - 1) * scale
+    tx, ty = (2 * u[:, 2] - 1) * shift, (2 * u[:, 3] - 1) * shift
+    flip = (u[:, 4] < mirror_prob).to(torch.float64)
+    drawn = u[:, 5] < prob
+    if mask is not None:
+        drawn &= torch.as_tensor(mask, dtype=torch.bool).cpu()
+    if not (rotation or scale or shift or mirror_prob):
+        drawn[:] = False
+    rows = torch.stack([torch.cos(theta), torch.sin(theta), k, tx, ty, flip], 1)
+    rows[~drawn] = torch.tensor(topdown.ROI_AUG_IDENTITY, dtype=torch.float64)
+    return (rows + 0.0).to(torch.float32)          # + 0.0: no signed zeros
+
+
+def _roi_aug_spec(roi_aug):
+    """TrainStep(roi_aug=): (rotation_deg, scale, shift), (rotation_deg, scale, shift, mirror_prob), or a dict of rotation / scale /
+    shift / mirror_prob / prob / generator."""
+    keys = ("rotation", "scale", "shift", "mirror_prob", "prob", "generator")
+    if isinstance(roi_aug, dict):
+        spec = dict(roi_aug)
+    elif isinstance(roi_aug, (tuple, list)) and len(roi_aug) in (3, 4):
+        spec = dict(zip(keys[:4], roi_aug))
+    else:
+        raise ValueError(f"roi_aug must be (rotation_deg, scale, shift[, mirror_prob]) or a dict of {', '.join(keys)}, not {roi_aug!r}")
+    unknown = set(spec) - set(keys)
+    if unknown:
+        raise ValueError(f"roi_aug: unknown keys {sorted(unknown)} (known: {', '.join(keys)})")
+    out = {"rotation": 0.0, "scale": 0.0, "shift": 0.0, "mirror_prob": 0.0, "prob": 1.0, "generator": None}
+    out.update(spec)
+    for key in keys[:5]:
+        if not _is_number(out[key]) or out[key] < 0:
+            raise ValueError(f"roi_aug: {key} must be a finite number >= 0, not {out[key]!r}")
+    if out["scale"] >= 1:
+        raise ValueError(f"roi_aug: scale must stay below 1 (the extents are multiplied by 1 - scale .. 1 + scale), not {out['scale']!r}")
+    if out["mirror_prob"] > 1 or out["prob"] > 1:
+        raise ValueError(f"roi_aug: mirror_prob and prob are probabilities in 0..1, not {out['mirror_prob']!r} / {out['prob']!r}")
+    return out
+
+
+def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_jitter=None, targets_from_joints=True, box_padding=1.25,
+                        oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left",
+                        frame_layout=None, roi_aug=None, coord_loss_weight=0.0, use_target_weight=False):
+    """TrainStep(frames=, box_padding=, oriented=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=, roi_aug=): refuse what
+    cannot run, before any device work (no device is touched here).  The options shared with InferStep follow _check_frames' /
+    _check_roi's rules.  Returns (frames as a tuple of ints or None, the roi_aug spec or None)."""
+    checked = _check_frames(frames, input_u8, box_padding, False, 0.0, 1, 0.0, antialias, frame_format, yuv, chroma_siting, frame_layout)
+    _check_roi(model, checked, oriented, (0, 1), 1.0, None)
+    if checked is None:
+        if roi_aug is not None:
+            raise ValueError("roi_aug perturbs hand ROIs on full frames: pass frames=(n_frames, hs, ws)")
+        return None, None
+    if geometric_aug is not None:
+        raise ValueError("frames= and geometric_aug= are two augmentations of two input paths: with frames pass roi_aug=, which samples "
+                         "the frame itself")
+    if color_jitter is not None:
+        raise ValueError("frames= and color_jitter=: ColorJitter runs in the uint8 input kernel, the frame crop has none")
+    if not targets_from_joints:
+        raise ValueError("frames= needs targets_from_joints=True: the target is rendered from the joints taken into the crop")
+    if coord_loss_weight > 0 and not use_target_weight:
+        raise ValueError("coord_loss_weight > 0 with frames= needs use_target_weight=True: the joints of an empty slot lie off the map "
+                         "and must carry weight 0 in the coordinate term")
+    return checked, (None if roi_aug is None else _roi_aug_spec(roi_aug))
+
+
 class TrainStep:
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
                  input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
-                 use_target_weight=False, ohkm_topk=0, target_encoding="quantised", coord_loss_weight=0.0, soft_argmax_beta=100.0):
+                 use_target_weight=False, ohkm_topk=0, target_encoding="quantised", coord_loss_weight=0.0, soft_argmax_beta=100.0,
+                 frames=None, box_padding=1.25, oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"),
+                 chroma_siting="left", frame_layout=None, roi_aug=None):
         """``coord_loss_weight`` = L > 0 (opt-in, integral regression; 0 = the step as it was: the same launches and buffers) adds
         L * mean |soft-arg-max(beta * heat-map) * 4 - joint| to the loss and its gradient to ``plan.dout_nchw`` (lh_integral_l1 right
         behind the MSE kernel, on the joints the target was rendered from, weighted by ``target_weight`` under ``use_target_weight``,
         with the step's loss scale).  The coordinate term covers EVERY joint whatever ``ohkm_topk`` says: mining selects planes of
         the MSE term only.  ``coord_loss`` holds the coordinate term alone, ``soft_preds`` the soft-arg-max keypoints and
-        ``coord_joint_loss`` [B, J] the weighted L1 distance of every joint (lh_integral_l1's joint_loss); ``preds`` stays the arg-max.  Data parallel needs nothing new: the normaliser 2*b*j is a constant every rank shares."""
-        self.lib = _lib.load()
+        ``coord_joint_loss`` [B, J] the weighted L1 distance of every joint (lh_integral_l1's joint_loss); ``preds`` stays the arg-max.  Data parallel needs nothing new: the normaliser 2*b*j is a constant every rank shares.
+
+        Training on hand ROIs cropped from full frames, opt-in (``frames=None``: the step as it was, the same launches and buffers):
+        ``frames=(n_frames, hs, ws)`` makes the static inputs ``frames`` / ``boxes`` / ``frame_index`` (and ``rot`` / ``mirror`` under
+        ``oriented`` or ``roi_aug``) with InferStep's meaning and launches -- ``box_padding``, ``oriented``, ``antialias``,
+        ``frame_format`` / ``yuv`` / ``chroma_siting`` / ``frame_layout`` as there, so the crop a model is trained on is the crop it is
+        deployed behind, bit for bit.  ``joints`` are FRAME coordinates (``step.joints`` keeps them): lh_affine_points_inv takes them
+        through the inverse of ``plan.crop_mat`` into ``joints_crop``, which the target is rendered from (and lh_integral_l1 reads).
+        ``preds`` stays in crop coordinates, ``frame_preds`` (with ``decode``) is ``preds`` through ``crop_mat``; ``valid`` is
+        ``src_frame >= 0``.  An empty slot's joints lie at topdown.POINT_OFF: a zero target and, under ``use_target_weight``, weight 0.
+        ``roi_aug=(rotation_deg, scale, shift[, mirror_prob])`` or a dict that may also carry prob / generator: every call draws one
+        perturbation per slot (sample_roi_aug) into ``plan.roi_aug``; lh_roi_perturb moves, scales, turns and mirrors the caller's
+        ROI in front of lh_roi_affine, so the crop samples the frame once and its margin is real context.  The caller's ``boxes`` /
+        ``rot`` / ``mirror`` are never written.  A mirrored ROI needs no joint permutation (a hand has no left / right joint pairs)."""
         if not _is_number(coord_loss_weight) or coord_loss_weight < 0:
             raise ValueError(f"coord_loss_weight must be a finite number >= 0, not {coord_loss_weight!r}")
+        frames, roi_aug = _check_train_frames(model, frames, input_u8, geometric_aug, color_jitter, targets_from_joints, box_padding, oriented,
+                                              antialias, frame_format, yuv, chroma_siting, frame_layout, roi_aug, coord_loss_weight,
+                                              use_target_weight)
+        self.lib = _lib.load()
         _check_beta(soft_argmax_beta)
         if coord_loss_weight > 0 and not targets_from_joints:
             raise LightHandError("coord_loss_weight needs targets_from_joints=True: the coordinate loss reads the joints the target is rendered from")
@@ -223,7 +314,7 @@ class TrainStep:
         self._model_generation = getattr(model, "_lh_generation", 0)
         model.train()
         # uint8 input rewires the plan's image launch: such a step owns its plan (model(x) in train mode keeps the float one)
-        owner = ("train", "u8") if input_u8 else None
+        owner = ("train", "frames") if frames else ("train", "u8") if input_u8 else None
         if grad_sync is not None:               # data parallel: one set of measured kernel choices for all ranks
             from . import parallel
             self.plan = parallel.plan_with_shared_tuning(
@@ -245,6 +336,22 @@ class TrainStep:
         self.joints = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
         # the joints through this step's forward matrices: what the model is asked to predict (self.joints keeps the caller's)
         self.joints_aug = torch.zeros_like(self.joints) if geometric_aug is not None else None
+        # frames=(n_frames, hs, ws): the input is hand ROIs on full frames (the docstring); joints_crop takes joints_aug's place
+        self.frames = self.boxes = self.frame_index = self.rot = self.mirror = self.joints_crop = self.frame_preds = None
+        self.roi_aug, self.oriented = roi_aug, False
+        self.antialias = _antialias_taps(antialias)
+        self.frame_format = frame_format if frames else None
+        if frames:
+            self.images = None                                         # the inputs of such a step are frames / boxes / frame_index
+            self.oriented = bool(oriented) or roi_aug is not None      # a turned ROI needs the oriented launch
+            extra = dict(frame_format="nv12", yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout) if frame_format == "nv12" else {}
+            self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
+                                                    perturb=roi_aug is not None, **extra)
+            self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
+            self.rot, self.mirror = self.plan.rot, self.plan.mirror
+            self.joints_crop = torch.zeros_like(self.joints)
+            if decode:
+                self.frame_preds = torch.zeros_like(self.joints)
         self.target = torch.zeros_like(out)
         self.targets_from_joints = targets_from_joints
         # use_target_weight / ohkm_topk (opt-in extensions, off = the step as it was: the same launches and buffers): the loss is
@@ -319,6 +426,10 @@ class TrainStep:
             check(self.lib.lh_affine_points(self.joints.data_ptr(), 2, self.plan.warp_fwd.data_ptr(), self.joints_aug.data_ptr(), 2, b, j,
                                             stream), "lh_affine_points")
             joints = self.joints_aug
+        if self.joints_crop is not None:                               # frame -> crop through this step's matrix (behind the matrix launch)
+            check(self.lib.lh_affine_points_inv(self.joints.data_ptr(), 2, self.plan.crop_mat.data_ptr(), self.plan.src_frame.data_ptr(),
+                                                self.joints_crop.data_ptr(), 2, b, j, stream), "lh_affine_points_inv")
+            joints = self.joints_crop
         if self.target_encoding == "unbiased":
             check(self.lib.lh_gaussian_target_sub(joints.data_ptr(), 2, _ptr(self.vis) if self.use_target_weight else None, 1, heatmap.RADIUS,
                                                   float(heatmap.SIGMA), self.target.data_ptr(),
@@ -335,7 +446,9 @@ class TrainStep:
 
     def _fwd_loss(self, stream):
         # the target only depends on the joints: it is rendered on the weight-pack side stream, under the stem
-        rendered = self.plan.refresh_packs(stream, overlap=True, side_work=self._render_target if self.targets_from_joints else None)
+        # (on frames the joints go through the crop matrix, which the forward list writes: the render follows it on the main stream)
+        side = self._render_target if self.targets_from_joints and self.frames is None else None
+        rendered = self.plan.refresh_packs(stream, overlap=True, side_work=side)
         self.plan.run_forward(stream)
         self._fwd_loss_tail(stream, target_done=rendered)
 
@@ -357,7 +470,7 @@ class TrainStep:
             check(self.lib.lh_mse_heatmap(out.data_ptr(), self.target.data_ptr(), out.numel(), self.loss.data_ptr(),
                                           p.dout_nchw.data_ptr(), _ptr(self._loss_scale_dev), self._mse_ws.data_ptr(), stream), "lh_mse_heatmap")
         if self._integral_ws is not None:
-            joints = self.joints_aug if self.joints_aug is not None else self.joints
+            joints = self.joints_crop if self.joints_crop is not None else self.joints_aug if self.joints_aug is not None else self.joints
             check(self.lib.lh_integral_l1(out.data_ptr(), joints.data_ptr(), 2, self.target_weight.data_ptr() if self.use_target_weight else None,
                                           out.shape[0], out.shape[1], out.shape[2], out.shape[3], self.soft_argmax_beta, self.heat_scale,
                                           self.coord_loss_weight, self.soft_preds.data_ptr(), self.coord_joint_loss.data_ptr(),
@@ -367,6 +480,9 @@ class TrainStep:
             check(self.lib.lh_heatmap_argmax(out.data_ptr(), out.shape[0] * out.shape[1], out.shape[2], out.shape[3],
                                              self.heat_scale, self.preds.data_ptr(), self.maxvals.data_ptr(), None,
                                              aux.cuda_stream if aux is not None else stream), "lh_heatmap_argmax")
+            if self.frame_preds is not None:
+                check(self.lib.lh_affine_points(self.preds.data_ptr(), 2, p.crop_mat.data_ptr(), self.frame_preds.data_ptr(), 2, out.shape[0],
+                                                out.shape[1], aux.cuda_stream if aux is not None else stream), "lh_affine_points")
             if aux is not None:
                 torch.cuda.current_stream().wait_event(aux.record_event())
 
@@ -465,15 +581,36 @@ class TrainStep:
             if st is not None:
                 self.optimizer._sync_hyper(st, group)
 
-    def __call__(self, images=None, joints=None, target=None, aug=None):
+    @property
+    def valid(self):
+        """bool [batch]: the slots whose ROI and frame index were usable in the last run (None without ``frames``)."""
+        return None if self.frames is None else self.plan.src_frame >= 0
+
+    def __call__(self, images=None, joints=None, target=None, aug=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None):
         """``joints``: [batch, J, >=2]; under ``use_target_weight`` a third column is the visibility (two columns = all visible).
+        A step built with ``frames=`` takes ``frames`` / ``boxes`` / ``frame_index`` (and ``rot`` / ``mirror`` under ``oriented`` or
+        ``roi_aug``) in place of ``images``, copied into the static buffers as InferStep does; its ``joints`` are frame coordinates.
         ``aug`` (bool [batch], optional; uint8 input with color_jitter only): which samples are jittered this step
         (the reference's fixed --ratio_of_aug subset, src/tools/dataset.py:133); None = all of them."""
         if getattr(self.model, "_lh_generation", 0) != self._model_generation:
             raise LightHandError("the model's parameter storages were re-created (.to() / .cuda() / .float()) after this TrainStep "
                                  "was built: its graph still trains the old buffers -- build a new TrainStep")
+        if self.frames is None:
+            if frames is not None or boxes is not None or frame_index is not None or rot is not None or mirror is not None:
+                raise ValueError("frames / boxes / frame_index / rot / mirror are the inputs of TrainStep(frames=(n_frames, hs, ws))")
+        elif images is not None or target is not None:
+            raise ValueError("a step built with frames= takes frames / boxes / frame_index and joints, not images or target")
+        elif (rot is not None or mirror is not None) and not self.oriented:
+            raise ValueError("rot / mirror are the inputs of TrainStep(frames=..., oriented=True) or roi_aug=")
         if self.graphs is not None:
             self.sync_hyper()
+        for dst, src in ((self.frames, frames), (self.boxes, boxes), (self.frame_index, frame_index), (self.rot, rot), (self.mirror, mirror)):
+            if src is not None:
+                dst.copy_(src, non_blocking=True)
+        if self.roi_aug is not None:
+            g = self.roi_aug                       # read by the replay from the plan's buffer, never baked into the graph
+            self.plan.roi_aug.copy_(sample_roi_aug(self.joints.shape[0], g["rotation"], g["scale"], g["shift"], g["mirror_prob"],
+                                                   prob=g["prob"], generator=g["generator"]), non_blocking=True)
         if images is not None:
             (self.images_u8 if images.dtype == torch.uint8 and self.images_u8 is not None else self.images).copy_(images, non_blocking=True)
         if self.color_jitter is not None and self.images_u8 is not None:

@@ -27,14 +27,7 @@ import argparse
 import json
 import time
 
-import numpy as np
-
-
-def _frame_size(text):
-    parts = text.lower().split("x")
-    if len(parts) != 2 or not all(p.isdigit() and int(p) > 0 for p in parts):
-        raise argparse.ArgumentTypeError(f"--frame_size wants HSxWS (e.g. 1080x1920), not {text!r}")
-    return int(parts[0]), int(parts[1])
+from lighthand_amd.tools.synthetic_frames import frame_size_arg as _frame_size, synthetic_sequence  # noqa: F401  (the renderer is shared with tools.train)
 
 
 def build_parser():
@@ -59,37 +52,6 @@ def build_parser():
     ap.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
     ap.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
     return ap
-
-
-def synthetic_sequence(n, hs, ws, hands, seed=0, spin=0.0):
-    """n frames uint8 [n][hs][ws][3] and the first frame's hand boxes fp32 [hands][4] (pixel-index coordinates, the bounds of each
-    hand's 21 joints).  Every hand is a fixed constellation of 21 discs, about a fifth of the frame's short side across, whose
-    centre drifts on a seeded smooth path that stays inside the frame; ``spin`` degrees per frame turn it about that centre."""
-    rng = np.random.RandomState(seed)
-    span = max(8.0, min(hs, ws) / 5.0)
-    frames = rng.randint(0, 32, size=(n, hs, ws, 3)).astype(np.uint8)
-    shape = rng.uniform(-0.5, 0.5, size=(hands, 21, 2)) * span
-    start = np.stack([rng.uniform(span, ws - span, size=hands), rng.uniform(span, hs - span, size=hands)], 1)
-    phase, speed = rng.uniform(0, 2 * np.pi, size=(hands, 2)), rng.uniform(0.02, 0.08, size=(hands, 2))
-    r = max(2, int(span / 16))
-    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
-    disc = (255 * np.clip(1.25 - np.hypot(xx, yy) / r, 0, 1)).astype(np.uint8)
-    boxes = np.zeros((hands, 4), np.float32)
-    for t in range(n):
-        drift = 0.5 * span * np.sin(phase + speed * t) - 0.5 * span * np.sin(phase)
-        turned = shape
-        if spin:
-            c, s = np.cos(np.deg2rad(spin * t)), np.sin(np.deg2rad(spin * t))
-            turned = shape @ np.array([[c, s], [-s, c]])
-        joints = turned + np.clip(start + drift, [span, span], [ws - span, hs - span])[:, None, :]
-        if t == 0:
-            boxes[:, :2], boxes[:, 2:] = joints.min(1), joints.max(1)
-        for x, y in np.rint(joints.reshape(-1, 2)).astype(int):
-            y0, y1, x0, x1 = max(y - r, 0), min(y + r + 1, hs), max(x - r, 0), min(x + r + 1, ws)
-            if y0 < y1 and x0 < x1:
-                patch = disc[y0 - (y - r):y1 - (y - r), x0 - (x - r):x1 - (x - r), None]
-                frames[t, y0:y1, x0:x1] = np.maximum(frames[t, y0:y1, x0:x1], patch)
-    return frames, boxes
 
 
 def main(argv=None):

@@ -35,6 +35,13 @@ are decoded with the Taylor step on the log of the blurred map instead of the ha
 step adds L x the L1 distance between the soft-arg-max under softmax(B * heat-map) and the joint, in input pixels, to the heat-map
 loss (every joint, whatever ``--ohkm_topk`` selects; weighted like the heat-map loss under ``--use_target_weight``); the validation
 loss stays the heat-map loss, and ``--soft_decode`` decodes the validation keypoints with that soft-arg-max (not with ``--dark_decode``).
+``--frame_size HSxWS`` (with ``--synthetic N``; off by default = the tool as it was): train on hand ROIs cropped from full frames on
+the device (TrainStep(frames=...)): the samples are seeded HS x WS frames of one hand each, a constellation of 21 discs whose centres
+are the joints in FRAME coordinates and whose bounds are the hand box (tools.synthetic_frames, the renderer of tools.track_frames).
+``--roi_rot DEG`` / ``--roi_scale S`` / ``--roi_shift F`` / ``--roi_mirror P`` perturb the ROI per sample and step (TrainStep(roi_aug=):
+the frame is sampled once, so the margin of a turned or shrunk crop is real context), ``--oriented``, ``--antialias [N]`` and
+``--frame_format nv12 [--yuv_matrix --yuv_range --chroma_siting]`` are InferStep's crop options, so the model trains on the crop it is
+deployed behind; validation crops the un-augmented ROI with the same options and scores loss / PCK / EPE in crop coordinates.
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -106,7 +113,40 @@ def parse_args(argv=None, phase="train"):
                    help="integral regression: weight of the L1 loss on the soft-arg-max coordinates, input pixels (0 = off)")
     p.add_argument("--soft_argmax_beta", default=100.0, type=float, help="softmax temperature of the soft-arg-max (heat-map x beta)")
     p.add_argument("--soft_decode", action="store_true", help="decode the validation keypoints with the soft-arg-max (default: hard arg-max)")
+    from lighthand_amd.tools.synthetic_frames import frame_size_arg
+    p.add_argument("--frame_size", default=None, type=frame_size_arg, metavar="HSxWS",
+                   help="train on hand ROIs cropped from synthetic HS x WS frames on the device (needs --synthetic; default: off)")
+    p.add_argument("--roi_rot", default=0.0, type=float, help="ROI augmentation: rotation U[-DEG, DEG] degrees (needs --frame_size)")
+    p.add_argument("--roi_scale", default=0.0, type=float, help="ROI augmentation: extents x U[1-S, 1+S] (needs --frame_size)")
+    p.add_argument("--roi_shift", default=0.0, type=float, help="ROI augmentation: centre shift U[-F, F] x the extents (needs --frame_size)")
+    p.add_argument("--roi_mirror", default=0.0, type=float, help="ROI augmentation: probability of mirroring the crop (needs --frame_size)")
+    p.add_argument("--oriented", action="store_true", help="oriented ROI launch of the frame crop (needs --frame_size)")
+    p.add_argument("--antialias", nargs="?", type=int, const=8, default=None, metavar="N",
+                   help="area sampling of minified ROIs: at most N (1..8, default 8) samples per crop pixel and axis (needs --frame_size)")
+    p.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12"], help="what the frame buffer holds (needs --frame_size)")
+    p.add_argument("--yuv_matrix", default="bt709", choices=["bt601", "bt709"], help="luma coefficients of NV12 frames")
+    p.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
+    p.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
     args = p.parse_args(argv)
+    roi_flags = any((args.roi_rot, args.roi_scale, args.roi_shift, args.roi_mirror))
+    if args.frame_size is None:
+        if roi_flags or args.oriented or args.antialias is not None or args.frame_format != "rgb":
+            p.error("--roi_rot / --roi_scale / --roi_shift / --roi_mirror / --oriented / --antialias / --frame_format need --frame_size HSxWS")
+    else:
+        if not args.synthetic:
+            p.error("--frame_size renders synthetic frames: pass --synthetic N")
+        if any((args.rot_factor, args.scale_factor, args.shift_factor)):
+            p.error("--rot_factor / --scale_factor / --shift_factor warp ready crops: with --frame_size use --roi_rot / --roi_scale / --roi_shift")
+        if args.coord_loss_weight > 0 and not args.use_target_weight:
+            p.error("--coord_loss_weight with --frame_size needs --use_target_weight")
+        if args.antialias is not None and not 1 <= args.antialias <= 8:
+            p.error("--antialias takes 1..8")
+        if args.frame_format == "nv12" and (args.frame_size[0] % 2 or args.frame_size[1] % 2):
+            p.error("--frame_format nv12 needs even frame sides")
+        if min(args.roi_rot, args.roi_scale, args.roi_shift, args.roi_mirror) < 0 or args.roi_scale >= 1 or args.roi_mirror > 1:
+            p.error("--roi_rot, --roi_shift >= 0, 0 <= --roi_scale < 1, 0 <= --roi_mirror <= 1")
+    if args.frame_format != "nv12" and (args.yuv_matrix, args.yuv_range, args.chroma_siting) != ("bt709", "limited", "left"):
+        p.error("--yuv_matrix / --yuv_range / --chroma_siting need --frame_format nv12")
     if args.soft_decode and args.dark_decode:
         p.error("--soft_decode and --dark_decode are two decodes: pass one")
     if not (args.coord_loss_weight >= 0 and np.isfinite(args.coord_loss_weight)):
@@ -150,6 +190,46 @@ class SyntheticHands(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         return self.images[i], self.joints[i]
+
+
+class SyntheticFrames(torch.utils.data.Dataset):
+    """Seeded full frames of one hand each (--frame_size): (frame uint8 [hs, ws, 3] -- or NV12 [rows, ws] with ``nv12=(matrix, range)``
+    --, joint_2d[21, 2] in FRAME coordinates, box[4] = the joints' bounds).  ``invisible``: as SyntheticHands'."""
+
+    def __init__(self, n, frame_size, seed, invisible=None, nv12=None):
+        from lighthand_amd.tools.synthetic_frames import synthetic_sequence
+        from lighthand_amd.topdown import rgb_to_nv12_host
+        frames, _, joints = synthetic_sequence(n, frame_size[0], frame_size[1], 1, seed, return_joints=True)
+        joints = joints[:, 0]
+        self.frames = torch.from_numpy(rgb_to_nv12_host(frames, *nv12) if nv12 else frames)
+        self.boxes = torch.from_numpy(np.concatenate([joints.min(1), joints.max(1)], 1).astype(np.float32))
+        self.joints = torch.from_numpy(joints)
+        if invisible is not None:
+            rng = np.random.RandomState(seed + 77)
+            self.joints = torch.cat([self.joints, torch.from_numpy((rng.uniform(size=(n, 21, 1)) >= invisible).astype(np.float32))], 2)
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __getitem__(self, i):
+        return self.frames[i], self.joints[i], self.boxes[i]
+
+
+def frame_options(args):
+    """The crop options --frame_size's steps share (TrainStep and the validation InferStep), without ``frames=`` itself."""
+    opt = dict(oriented=bool(args.oriented))
+    if args.antialias is not None:
+        opt["antialias"] = args.antialias
+    if args.frame_format == "nv12":
+        opt.update(frame_format="nv12", yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
+    return opt
+
+
+def roi_aug(args):
+    """(rotation, scale, shift, mirror_prob) for TrainStep(roi_aug=) from --roi_rot / --roi_scale / --roi_shift / --roi_mirror, None
+    when all are 0."""
+    factors = (args.roi_rot, args.roi_scale, args.roi_shift, args.roi_mirror)
+    return factors if any(factors) else None
 
 
 class _WithAugFlag(torch.utils.data.Dataset):
@@ -309,10 +389,13 @@ def run_epochs(args, epo, train_loader, train_batch, validate_fn, save_fn, optim
     return stopper.best_loss
 
 
-def validate(model, loader, args, u8_step=None):
+def validate(model, loader, args, u8_step=None, frames_step=None):
     """Runner.run validation branch (src/utils/method.py:218-287): loss, PCK@0.2 (bbox-normalised), EPE.
     ``u8_step``: an InferStep(input_u8=...) of the model for loaders that yield raw uint8 frames, or a callable
-    batch size -> InferStep (the short last batch of the loader needs a step of its own shape)."""
+    batch size -> InferStep (the short last batch of the loader needs a step of its own shape).
+    ``frames_step`` (--frame_size): a callable batch size -> InferStep(frames=(b, hs, ws), ...) for loaders that yield (frame, joint_2d
+    in frame coordinates, box): the un-augmented ROI is cropped, and the joints are taken into the crop (lh_affine_points_inv) before
+    loss, PCK and EPE are scored there."""
     from lighthand_amd.heatmap import JointsMSELoss, WeightedJointsMSELoss, max_preds_device, render_targets
     from lighthand_amd.metrics import device_pck_epe
     model.eval()
@@ -328,7 +411,15 @@ def validate(model, loader, args, u8_step=None):
         for batch in loader:
             images, joints3 = batch[0].cuda(non_blocking=True), batch[1][..., :3].float().cuda(non_blocking=True)
             joints = joints3[..., :2].contiguous()
-            if images.dtype == torch.uint8:
+            if frames_step is not None:
+                from lighthand_amd.topdown import affine_points_inv
+                st = frames_step(images.shape[0])
+                st.refresh_weights()
+                st(frames=images, boxes=batch[2].cuda(non_blocking=True))
+                pred = st.heatmaps
+                joints = affine_points_inv(joints, st.plan.crop_mat, st.plan.src_frame)
+                joints3 = torch.cat([joints, joints3[..., 2:]], 2)
+            elif images.dtype == torch.uint8:
                 st = u8_step(images.shape[0]) if callable(u8_step) and not hasattr(u8_step, "heatmaps") else u8_step
                 st.refresh_weights()
                 st(images)
@@ -392,6 +483,14 @@ def main(args, train_set=None, val_set=None):
     torch.cuda.set_device(local)
     # synthetic samples carry a visibility column only where it is read: their default shape stays [21, 2]
     invisible = args.synthetic_invisible if args.use_target_weight else None
+    frame_size = getattr(args, "frame_size", None)
+    if frame_size is not None:
+        if train_set is not None or val_set is not None:
+            raise SystemExit("--frame_size renders its own synthetic frames: it takes no train_set / val_set")
+        nv12 = (args.yuv_matrix, args.yuv_range) if args.frame_format == "nv12" else None
+        train_set = SyntheticFrames(args.synthetic, frame_size, seed + rank, invisible=invisible, nv12=nv12)
+        val_set = SyntheticFrames(args.val_synthetic or max(args.batch_size, max(args.synthetic, args.batch_size * 8) // 8), frame_size,
+                                  seed + 1000, invisible=invisible, nv12=nv12)
     if train_set is None:
         if not args.synthetic:
             raise SystemExit("the reference's datasets (LightHand99K / FreiHAND / ...) are not shipped: pass --synthetic N, or call "
@@ -400,10 +499,15 @@ def main(args, train_set=None, val_set=None):
     if val_set is None:
         val_set = SyntheticHands(args.val_synthetic or max(args.batch_size, max(args.synthetic, args.batch_size * 8) // 8), args.size, seed + 1000,
                                  invisible=invisible)
-    kind, raw_hw = _sample_kind(train_set)
-    val_kind, val_hw = _sample_kind(val_set)
-    train_set = _WithAugFlag(train_set, args.ratio_of_aug)
-    workers = args.num_workers if not isinstance(train_set.base, SyntheticHands) else 0
+    if frame_size is not None:
+        kind = val_kind = "frames"
+        raw_hw = val_hw = None
+        workers = 0
+    else:
+        kind, raw_hw = _sample_kind(train_set)
+        val_kind, val_hw = _sample_kind(val_set)
+        train_set = _WithAugFlag(train_set, args.ratio_of_aug)
+        workers = args.num_workers if not isinstance(train_set.base, SyntheticHands) else 0
     # persistent workers: a worker is forked from THIS process, which by the first epoch holds a HIP context and hundreds of
     # GB of mappings (~20 s per fork measured on the GPU box) -- fork them once per loader, not once per epoch
     # the reference builds both loaders with drop_last=False (src/tools/train.py:27-38): the short last batch is trained on and
@@ -427,8 +531,13 @@ def main(args, train_set=None, val_set=None):
     loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk,
                    target_encoding="unbiased" if args.unbiased_target else "quantised",
                    coord_loss_weight=args.coord_loss_weight, soft_argmax_beta=args.soft_argmax_beta)
+
+    def frame_kw(b):
+        """--frame_size: one frame per slot (frame_index stays the plan's arange), the crop options and the ROI augmentation."""
+        return dict(frames=(b,) + tuple(frame_size), roi_aug=roi_aug(args), **frame_options(args)) if frame_size is not None else {}
+
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
-                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw)
+                     input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw, **frame_kw(args.batch_size))
     scheduler = make_scheduler(optimizer, args, epo, opt_state)       # src/tools/train.py:50-58, in the reference's order
     steps = {args.batch_size: step}
 
@@ -439,7 +548,7 @@ def main(args, train_set=None, val_set=None):
         st = steps.get(b)
         if st is None:
             st = steps[b] = TrainStep(model, b, args.size, args.size, optimizer=optimizer, use_graph=False, grad_sync=sync,
-                                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw,
+                                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw, **frame_kw(b),
                                       plan_options=PlanOptions.from_env().replace(autotune=False))
         return st
 
@@ -447,18 +556,25 @@ def main(args, train_set=None, val_set=None):
 
     def val_step_for(b):
         if b not in val_steps:
-            val_steps[b] = InferStep(model, b, args.size, args.size, input_u8=val_hw)
+            if frame_size is not None:
+                val_steps[b] = InferStep(model, b, args.size, args.size, frames=(b,) + tuple(frame_size), **frame_options(args))
+            else:
+                val_steps[b] = InferStep(model, b, args.size, args.size, input_u8=val_hw)
         return val_steps[b]
 
     def train_batch(it, batch):
         images, joints, aug = batch
         st = step_for(images.shape[0])
+        if frame_size is not None:                 # (frame, joints in frame coordinates, box)
+            st(frames=images.cuda(non_blocking=True), boxes=aug.cuda(non_blocking=True), joints=joints.cuda(non_blocking=True))
+            return lambda: st.loss
         st(images.cuda(non_blocking=True), joints.cuda(non_blocking=True), aug=aug if jitter else None)
         return lambda: st.loss
 
     stopper = EarlyStop(best_loss, count, args.count)
     return run_epochs(args, epo, train_loader, train_batch,
-                      lambda: validate(model, val_loader, args, val_step_for if val_kind == "u8" else None),
+                      lambda: validate(model, val_loader, args, val_step_for if val_kind == "u8" else None,
+                                       frames_step=val_step_for if frame_size is not None else None),
                       lambda epoch, best, cnt: save_checkpoint(model, args, epoch, optimizer, best, cnt, "good", scaler=scaler),
                       optimizer, scheduler, stopper, rank=rank, world=world, scaler=scaler)
 

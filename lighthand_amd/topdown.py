@@ -18,7 +18,12 @@ The antialiased crop of minified ROIs (lh_frames_crop_area_to_nhwc4, InferStep(a
 NV12 frames (lh_frames_crop_yuv_to_nhwc4, InferStep(frames=..., frame_format="nv12")): ``yuv_matrix`` gives the conversion's 12
 coefficients, ``nv12_layout`` the buffer of a pitched surface, ``frames_crop(..., frame_format="nv12")`` is the launch,
 ``frames_crop_nv12_host`` its rule in numpy (fp32, or fp64 with ``dtype=np.float64``) and ``rgb_to_nv12_host`` an encoder for the tools
-and tests."""
+and tests.
+
+Training on frames (lh_roi_perturb / lh_affine_points_inv, runtime.TrainStep(frames=..., roi_aug=...)): ``roi_perturb`` turns the
+caller's ROI and a drawn row (c, s, k, tx, ty, flip) into the ROI the crop uses, ``affine_points_inv`` takes frame coordinates into
+the crop through the inverse of the crop matrix (``POINT_OFF`` for a slot that has none); ``roi_perturb_host`` /
+``affine_points_inv_host`` restate them in numpy, in fp32 or, as the yardstick, in fp64."""
 import numpy as np
 
 F = np.float32
@@ -347,6 +352,63 @@ def roi_affine_host(boxes, rot, mirror, frame_index, n_frames, size, padding):
     return mat, np.where(ok, fi, -1).astype(np.int32)
 
 
+POINT_OFF = -65536.0          # LH_POINT_OFF: where lh_affine_points_inv puts the points of a slot it cannot map
+ROI_AUG_IDENTITY = (1.0, 0.0, 1.0, 0.0, 0.0, 0.0)          # (c, s, k, tx, ty, flip): lh_roi_perturb copies such a slot bit for bit
+
+
+def roi_perturb_host(boxes, rot, mirror, aug, dtype=np.float32):
+    """boxes [b][4], rot [b][2] (None: (1, 0)), mirror [b] (None: 0), aug [b][6] = (c, s, k, tx, ty, flip) -> (boxes' [b][4], rot'
+    [b][2], mirror' int32 [b]); lh_roi_perturb in numpy, fp32 in the kernel's order.  ``dtype=np.float64``: the same operations in fp64
+    on the same fp32 inputs (the yardstick of the fp32 order); the copied slots are the same in both."""
+    T = np.dtype(dtype).type
+    boxes32 = np.asarray(boxes, np.float32).reshape(-1, 4)
+    b = boxes32.shape[0]
+    rot32 = np.tile(np.array([1, 0], np.float32), (b, 1)) if rot is None else np.asarray(rot, np.float32).reshape(b, 2)
+    mir = np.zeros(b, np.int32) if mirror is None else np.asarray(mirror, np.int32).reshape(b)
+    aug32 = np.asarray(aug, np.float32).reshape(b, 6)
+    bx, rt, ag = boxes32.astype(dtype), rot32.astype(dtype), aug32.astype(dtype)
+    x0, y0, x1, y1 = bx[:, 0], bx[:, 1], bx[:, 2], bx[:, 3]
+    rx, ry = rt[:, 0], rt[:, 1]
+    c, s, k, tx, ty, flip = (ag[:, i] for i in range(6))
+    with np.errstate(all="ignore"):
+        n32 = np.sqrt(rot32[:, 0] * rot32[:, 0] + rot32[:, 1] * rot32[:, 1])          # the decision is the kernel's, in fp32
+        same = (aug32 == np.asarray(ROI_AUG_IDENTITY, np.float32)).all(1)
+        ok = np.isfinite(boxes32).all(1) & np.isfinite(rot32).all(1) & (n32 > 0) & np.isfinite(aug32).all(1)
+        bw, bh = x1 - x0, y1 - y0
+        cx, cy = (x0 + x1) * T(0.5), (y0 + y1) * T(0.5)
+        n = np.sqrt(rx * rx + ry * ry)
+        ux, uy = rx / n, ry / n
+        dx, dy = tx * bw, ty * bh
+        ncx, ncy = cx + (dx * ux - dy * uy), cy + (dx * uy + dy * ux)
+        hw, hh = (bw * k) * T(0.5), (bh * k) * T(0.5)
+        nbox = np.stack([ncx - hw, ncy - hh, ncx + hw, ncy + hh], 1).astype(dtype)
+        nrot = np.stack([ux * c - uy * s, ux * s + uy * c], 1).astype(dtype)
+    nmir = ((mir != 0) != (aug32[:, 5] != 0)).astype(np.int32)
+    keep = same | ~ok
+    nbox[keep], nrot[keep], nmir[keep] = bx[keep], rt[keep], mir[keep]
+    return nbox, nrot, nmir
+
+
+def affine_points_inv_host(pts, mat, src_frame, dtype=np.float32):
+    """pts [b][j][>=2] (frame coordinates), mat [b][6] (crop -> frame), src_frame [b] -> crop coordinates [b][j][2];
+    lh_affine_points_inv in numpy, fp32 in the kernel's order.  A slot with src_frame < 0, or whose determinant (in fp32, the kernel's)
+    is not finite or 0, gives POINT_OFF.  ``dtype=np.float64``: the same operations in fp64 on the same fp32 inputs."""
+    T = np.dtype(dtype).type
+    pts32 = np.asarray(pts, np.float32)
+    b = pts32.shape[0]
+    m32 = np.asarray(mat, np.float32).reshape(b, 6)
+    src = np.asarray(src_frame, np.int32).reshape(b)
+    p, m = pts32.astype(dtype), m32.astype(dtype)[:, None, :]
+    with np.errstate(all="ignore"):
+        det32 = m32[:, 0] * m32[:, 4] - m32[:, 1] * m32[:, 3]
+        ok = (src >= 0) & np.isfinite(det32) & (det32 != 0)
+        det = m[..., 0] * m[..., 4] - m[..., 1] * m[..., 3]
+        qx, qy = p[..., 0] - m[..., 2], p[..., 1] - m[..., 5]
+        out = np.stack([(m[..., 4] * qx - m[..., 1] * qy) / det, (m[..., 0] * qy - m[..., 3] * qx) / det], -1).astype(dtype)
+    out[~ok] = T(POINT_OFF)
+    return out
+
+
 def rois_from_keypoints_host(preds, maxvals, boxes, rot, src_frame, axis=(0, 9), min_score=0.1, min_joints=8, min_side=16.0, min_axis=4.0):
     """preds [b][j][2] (frame coordinates), maxvals [b][j] or [b][j][1], boxes [b][4], rot [b][2], src_frame [b] -> (next_boxes fp32
     [b][4], next_rot fp32 [b][2], lost int32 [b]); lh_keypoints_to_rois in numpy, the joints walked in order."""
@@ -558,6 +620,55 @@ def roi_affine(boxes, rot, mirror, frame_index, n_frames, size, padding=1.25):
                                              int(size[0]), int(size[1]), float(padding), mat.data_ptr(), src.data_ptr(), _stream()),
                    "lh_roi_affine")
     return mat, src
+
+
+def roi_perturb(boxes, rot, mirror, aug):
+    """Device tensors boxes fp32 [b][4], rot fp32 [b][2] or None (= (1, 0)), mirror int32 [b] or None (= 0), aug fp32 [b][6] =
+    (c, s, k, tx, ty, flip) (runtime.sample_roi_aug) -> (boxes' fp32 [b][4], rot' fp32 [b][2], mirror' int32 [b]), the ROI the crop of
+    an augmented training step uses (one lh_roi_perturb launch on the current stream)."""
+    import torch
+    from . import _lib
+    boxes = boxes.to(torch.float32).contiguous()
+    aug = aug.to(torch.float32).contiguous()
+    rot = None if rot is None else rot.to(torch.float32).contiguous()
+    mirror = None if mirror is None else mirror.to(torch.int32).contiguous()
+    b = boxes.shape[0]
+    if (tuple(boxes.shape) != (b, 4) or tuple(aug.shape) != (b, 6) or (rot is not None and tuple(rot.shape) != (b, 2))
+            or (mirror is not None and tuple(mirror.shape) != (b,)) or not boxes.is_cuda
+            or any(t is not None and t.device != boxes.device for t in (rot, mirror, aug))):
+        raise _lib.LightHandError(f"roi_perturb: boxes [b, 4], rot [b, 2] or None, mirror [b] or None and aug [b, 6] on one device, got "
+                                  f"{tuple(boxes.shape)} / {None if rot is None else tuple(rot.shape)} / "
+                                  f"{None if mirror is None else tuple(mirror.shape)} / {tuple(aug.shape)}")
+    nbox = torch.empty(b, 4, dtype=torch.float32, device=boxes.device)
+    nrot = torch.empty(b, 2, dtype=torch.float32, device=boxes.device)
+    nmir = torch.empty(b, dtype=torch.int32, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        _lib.check(_lib.load().lh_roi_perturb(boxes.data_ptr(), None if rot is None else rot.data_ptr(),
+                                              None if mirror is None else mirror.data_ptr(), aug.data_ptr(), b, nbox.data_ptr(),
+                                              nrot.data_ptr(), nmir.data_ptr(), _stream()), "lh_roi_perturb")
+    return nbox, nrot, nmir
+
+
+def affine_points_inv(pts, mat, src_frame):
+    """Device tensors pts fp32 [b][j][>=2] (frame coordinates; further columns are ignored), mat fp32 [b][6] (crop -> frame), src_frame
+    int32 [b] -> crop coordinates fp32 [b][j][2] (one lh_affine_points_inv launch on the current stream); POINT_OFF for the points of a
+    slot that is empty or whose matrix has no inverse."""
+    import torch
+    from . import _lib
+    pts = pts.to(torch.float32).contiguous()
+    mat = mat.to(torch.float32).contiguous()
+    src_frame = src_frame.to(torch.int32).contiguous()
+    if pts.dim() != 3 or pts.shape[2] < 2 or pts.shape[0] < 1 or pts.shape[1] < 1:
+        raise _lib.LightHandError(f"affine_points_inv: pts [b, j, >= 2], got {tuple(pts.shape)}")
+    b, j, stride = pts.shape
+    if tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,) or not pts.is_cuda or mat.device != pts.device or src_frame.device != pts.device:
+        raise _lib.LightHandError(f"affine_points_inv: pts [b, j, >= 2], mat [b, 6] and src_frame [b] on one device, got "
+                                  f"{tuple(pts.shape)} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
+    out = torch.empty(b, j, 2, dtype=torch.float32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        _lib.check(_lib.load().lh_affine_points_inv(pts.data_ptr(), stride, mat.data_ptr(), src_frame.data_ptr(), out.data_ptr(), 2, b, j,
+                                                    _stream()), "lh_affine_points_inv")
+    return out
 
 
 def rois_from_keypoints(preds, maxvals, boxes, rot, src_frame, axis=(0, 9), min_score=0.1, min_joints=8, min_side=16.0, min_axis=4.0):
