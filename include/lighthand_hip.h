@@ -136,6 +136,23 @@ int lh_frames_crop_yuv_to_nhwc4(const unsigned char* frames_nv12, void* out, int
                                 int uv_offset, long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad, int wp,
                                 const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev, int max_taps,
                                 int dtype, void* stream);
+/* The frame crop with torchvision's ColorJitter between the sample and Normalize (training on frames: runtime.TrainStep(frames=...,
+ * crop_jitter=...)): lh_frames_crop_yuv_to_nhwc4's arguments -- csc12 == NULL: packed RGB frames as lh_frames_crop_area_to_nhwc4 reads
+ * them, and pitch, uv_offset, frame_stride and chroma_siting are not looked at -- plus factors_dev fp32 [b][4] (brightness, contrast,
+ * saturation, hue), order_dev int32 [b][4] (op ids 0..3, a negative id skips) and workspace (device, 8-byte aligned,
+ * lh_frames_crop_jitter_workspace_bytes(b)): lh_image_u8_jitter_to_nhwc4's draw, per slot.  The rule is that kernel's, on the crop:
+ * the ops run in the slot's order on the pixel's three channels in 0..1 (after the single sample, the tap average or the YUV
+ * conversion) and Normalize follows.  Contrast blends with the grey mean of the slot's whole h x w crop as it stands when the op runs;
+ * pixels that fell outside the frame are black and count.  Two launches: the first reduces each slot's grey sum into 32 fp64 partials
+ * (fixed order, no atomics: a replay is bit-reproducible; a slot without a contrast op writes zeros and samples nothing), the second
+ * sums them in index order, mean = (float)(sum / (h*w)), and writes the crop.  A slot whose order is (-1, -1, -1, -1) is the
+ * un-jittered entry's crop bit for bit; an empty slot stays black.  LH_ERR_ARG: factors_dev, order_dev or workspace NULL, and
+ * everything the entry it extends refuses. */
+size_t lh_frames_crop_jitter_workspace_bytes(int b);
+int lh_frames_crop_jitter_to_nhwc4(const unsigned char* frames, void* out, int b, int n_frames, int hs, int ws, int pitch, int uv_offset,
+                                   long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad, int wp,
+                                   const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev, int max_taps,
+                                   const float* factors_dev, const int* order_dev, void* workspace, int dtype, void* stream);
 /* preds_dev fp32 [b][j][2] (frame coordinates), maxvals_dev fp32 [b][j] -> next_boxes_dev fp32 [b][4], lost_dev int32 [b]: the bounds
  * of the keypoints with maxval >= min_score, each side widened about its centre to at least min_side.  With fewer than min_joints
  * such keypoints, or for an empty slot (src_frame < 0), next_boxes[i] = boxes[i] and lost[i] = 1; otherwise lost[i] = 0.  No

@@ -130,6 +130,9 @@ SIGNATURES = {
                                           _P]),
     "lh_frames_crop_yuv_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _I, C.POINTER(C.c_float), _I, _I, _I, _I, C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), _P, _P, _I, _I, _P]),
+    "lh_frames_crop_jitter_workspace_bytes": (_SZ, [_I]),
+    "lh_frames_crop_jitter_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _I, C.POINTER(C.c_float), _I, _I, _I, _I, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), _P, _P, _I, _P, _P, _P, _I, _P]),
     "lh_keypoints_to_boxes": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _F, _P, _P, _P]),
     "lh_roi_affine": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
     "lh_keypoints_to_rois": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P]),

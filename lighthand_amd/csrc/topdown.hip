@@ -2,6 +2,7 @@
 // Coordinates are pixel indices (pixel centres on the integers, an image spans [-0.5, size-0.5]); a box is (x0, y0, x1, y1) in them.
 // All arithmetic is fp32 in the order written (-ffp-contract=off): lighthand_amd/topdown.py restates it in numpy.
 #include "common.h"
+#include "color_jitter.h"
 
 // ------------------------------------------------------------------------------------------------ box -> matrix
 // mat[i] takes a CROP pixel index to a FRAME pixel index: the crop kernel samples through it and lh_affine_points moves the decoded
@@ -80,6 +81,19 @@ extern "C" int lh_box_affine(const float* boxes_dev, const int* frame_index_dev,
 //     e    = (Y - o[0], U - o[1], V - o[2]),  s[c] = fminf(fmaxf((k[c][0]*e0 + k[c][1]*e1) + k[c][2]*e2, 0.f), 255.f)
 // and s is the RGB path's sample from there on (* 1/255 or the tap sum, Normalize, store).  topdown.py: frames_crop_nv12_host.
 // A sample reads 4 luma and 8 chroma bytes; the highest one is uv_offset + (hc-1)*pitch + ws - 1 < frame_stride (checked on the host).
+//
+// ColorJitter on the crop (lh_frames_crop_jitter_to_nhwc4, training on frames): the uint8 input kernels' rule (color_jitter.h) on the
+// pixel's c[3] in 0..1 -- after the single sample, the tap average or the YUV conversion -- in the slot's op order, before Normalize.
+// Two launches of this kernel.  The grey-mean mode (op = LH_CROP_GREY_MEAN, the fp32 instantiation whatever the crop's dtype: the
+// samples are fp32 in all three) walks the slot's interior through the crop's own sample path (the same kx, ky, the same walk),
+// applies the ops that precede contrast and reduces cj_gray in fp64: per thread in walk order, then a fixed tree in LDS, one partial
+// per workgroup into workspace[slot][CJ_STRIPS] (grid (CJ_STRIPS, b), no atomics: a replay is bit-reproducible).  Pixels that fell
+// outside the frame are black and count, as the warped uint8 path counts its black fill.  A slot without a contrast op writes zeros
+// and samples nothing.  The apply mode (op = LH_CROP with jfactors != null, a workgroup-uniform switch in front of the pixel loops as
+// format is; also the fp32 instantiation's, which then stores in jdtype: the 16-bit instantiations carry no jitter code at all) sums
+// the slot's partials in index order once per workgroup, mean = (float)(sum / (h*w)), and runs cj_apply(c, factors, order, 0, 4, mean)
+// between the sample and Normalize.  Order (-1, -1, -1, -1) touches nothing: the un-jittered crop bit for bit.  An empty slot stays
+// black: every op maps black with mean 0 to black.  topdown.py: frames_crop_jitter_host.
 enum { LH_FRAMES_RGB = 0, LH_FRAMES_NV12 = 1 };
 
 struct CropArgs {
@@ -101,8 +115,37 @@ struct CropArgs {
     const int* iin;                                               //          mirror                            src_frame
     float *out0, *out1;                                           //          boxes', rot'                      points', -
     int* iout;                                                    //          mirror'                           -
+    // ColorJitter (the header comment): null = none, and the crop entries without it read none of the three
+    const float* jfactors;                                        // [b][4] brightness, contrast, saturation, hue
+    const int* jorder;                                            // [b][4] op ids, negative = skip
+    double* jpartial;                                             // [b][CJ_STRIPS]: written by LH_CROP_GREY_MEAN, read by the apply mode
+    int jdtype;                                                   // the apply mode: the dtype of dst (the launch is the fp32 instantiation's)
 };
-enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2 };
+enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3 };
+enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2 };
+
+// What a jittered launch carries into the pixel loops: the slot's factors and order, then the grey mean (LH_JIT_APPLY) or the number
+// of ops in front of contrast (LH_JIT_MEAN).
+struct CropJit {
+    const float* f;
+    const int* order;
+    float mean;
+    int kc;
+    int dtype;                                                    // LH_JIT_APPLY: what dst holds
+};
+
+// One pixel of padded NHWC4, channel 3 = 0.
+template <typename T>
+__device__ __forceinline__ void crop_store(T* dst, int i, const float v[3]) {
+    if constexpr (sizeof(T) == 2) {                               // one 8-byte store per pixel
+        union { uint2 u; T e[4]; } pk;
+        pk.e[0] = from_f<T>(v[0]); pk.e[1] = from_f<T>(v[1]); pk.e[2] = from_f<T>(v[2]); pk.e[3] = from_f<T>(0.f);
+        *reinterpret_cast<uint2*>(dst + (long)i * 4) = pk.u;
+    } else {
+        T* o = dst + (long)i * 4;
+        o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]); o[3] = from_f<T>(0.f);
+    }
+}
 
 // One bilinear sample of the frame at (fx, fy) on the raw 0..255 values; false (s untouched) outside the frame or for a NaN.
 __device__ __forceinline__ bool crop_sample(const unsigned char* base, int hs, int ws, float fx, float fy, float s[3]) {
@@ -176,14 +219,17 @@ __device__ __forceinline__ bool crop_sample_of(const CropArgs& p, const float* c
     else return crop_sample(base, p.hs, p.ws, fx, fy, s);
 }
 
-template <typename T, bool AREA, bool NV12>
-__device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned char* base, bool live, T* dst, int first, int stride,
+// JIT = LH_JIT_APPLY: ColorJitter between the sample and Normalize.  LH_JIT_MEAN: nothing is stored, the interior pixels' grey levels
+// (after the ops in front of contrast) are summed in the order of the walk: the return value (0 otherwise).
+template <typename T, bool AREA, bool NV12, int JIT = LH_JIT_NONE>
+__device__ __forceinline__ double crop_pixels(const CropArgs& p, const unsigned char* base, bool live, T* dst, int first, int stride,
                                             int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky,
-                                            bool tiled, const float* csc = nullptr) {
+                                            bool tiled, const float* csc = nullptr, const CropJit jit = {}) {
     const float fkx2 = (float)(2 * kx), fky2 = (float)(2 * ky), inv = 1.f / (float)(kx * ky);
     // AREA, tiled (the slot's choice, below): a wave takes an 8 x 8 tile of the output instead of 64 pixels of a row, so that its samples
     // stay within a square of the frame (a row of a turned ROI is a slanted line across many frame rows: a cache line per lane and load)
     const int tiles_x = (p.wp + 7) >> 3, n = AREA && tiled ? tiles_x * ((p.hp + 7) >> 3) * 64 : per_slot;
+    double grey = 0.0;                                            // LH_JIT_MEAN only
     for (int q = first; q < n; q += stride) {
         int y, x;
         if (AREA && tiled) {
@@ -222,18 +268,24 @@ __device__ __forceinline__ void crop_pixels(const CropArgs& p, const unsigned ch
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) c[ch] = (acc[ch] * inv) * (1.f / 255.f);
             }
+            if constexpr (JIT == LH_JIT_MEAN) {
+                cj_apply(c, jit.f, jit.order, 0, jit.kc, 0.f);
+                grey += (double)cj_gray(c);
+            }
+            if constexpr (JIT == LH_JIT_APPLY) cj_apply(c, jit.f, jit.order, 0, 4, jit.mean);          // black pixels are jittered too
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
         }
-        if constexpr (sizeof(T) == 2) {                           // one 8-byte store per pixel
-            union { uint2 u; T e[4]; } pk;
-            pk.e[0] = from_f<T>(v[0]); pk.e[1] = from_f<T>(v[1]); pk.e[2] = from_f<T>(v[2]); pk.e[3] = from_f<T>(0.f);
-            *reinterpret_cast<uint2*>(dst + (long)i * 4) = pk.u;
+        if constexpr (JIT == LH_JIT_MEAN) continue;
+        if constexpr (JIT == LH_JIT_APPLY) {                      // the fp32 instantiation stores for all three dtypes (uniform)
+            if (jit.dtype == LH_BF16) crop_store((bf16*)dst, i, v);
+            else if (jit.dtype == LH_F16) crop_store((f16*)dst, i, v);
+            else crop_store((float*)dst, i, v);
         } else {
-            T* o = dst + (long)i * 4;
-            o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]); o[3] = from_f<T>(0.f);
+            crop_store(dst, i, v);
         }
     }
+    return grey;
 }
 
 // ------------------------------------------------------------------------------------------------ ROI augmentation (training on frames)
@@ -307,10 +359,31 @@ __device__ __forceinline__ void crop_aux_modes(const CropArgs& p) {
     else affine_points_inv_point(i, p.in0, p.pstride, p.in1, p.iin, p.out0, p.ostride, p.j);
 }
 
+// One slot's pixels through the body its format and tap counts select; JIT as in crop_pixels.
+template <typename T, int JIT>
+__device__ __forceinline__ double crop_slot(const CropArgs& p, const unsigned char* base, bool live, bool nv12, T* dst, int first, int stride,
+                                          int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky, bool tiled,
+                                          const CropJit jit) {
+    if (nv12) {
+        // the 12 coefficients live in vector registers: as scalars they take the kernel past 100 SGPRs, and the RGB entries, which never
+        // read them, from 8 waves a SIMD to 7 (measured on the turned legs of tools/topdown_cost.py: EXPERIMENTS.md)
+        float csc[12];
+#pragma unroll
+        for (int c = 0; c < 12; ++c) {
+            csc[c] = c < 9 ? p.k[c] : p.o[c - 9];
+            asm volatile("" : "+v"(csc[c]));
+        }
+        if (kx * ky == 1) return crop_pixels<T, false, true, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc, jit);
+        return crop_pixels<T, true, true, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc, jit);
+    }
+    if (kx * ky == 1) return crop_pixels<T, false, false, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, nullptr, jit);
+    return crop_pixels<T, true, false, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, nullptr, jit);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
-    if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the two modes (CropArgs)
-        if (p.op != LH_CROP) {
+    if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the modes (CropArgs)
+        if (p.op == LH_CROP_ROI_PERTURB || p.op == LH_CROP_POINTS_INV) {
             crop_aux_modes(p);
             return;
         }
@@ -329,19 +402,37 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     // 64 pixels of a crop row cross 64 * |m3| frame rows: from 16 on the tiled walk reads fewer cache lines per load (measured: EXPERIMENTS.md)
     const bool tiled = fabsf(m3) >= 0.25f;
-    if (nv12) {
-        // the 12 coefficients live in vector registers: as scalars they take the kernel past 100 SGPRs, and the RGB entries, which never
-        // read them, from 8 waves a SIMD to 7 (measured on the turned legs of tools/topdown_cost.py: EXPERIMENTS.md)
-        float csc[12];
-#pragma unroll
-        for (int c = 0; c < 12; ++c) {
-            csc[c] = c < 9 ? p.k[c] : p.o[c - 9];
-            asm volatile("" : "+v"(csc[c]));
+    if constexpr (sizeof(T) == 4) {
+        // ColorJitter: both launches are this instantiation's, whatever the crop's dtype -- the samples are fp32 in all three, only the
+        // store differs -- so the 16-bit instantiations keep the code, registers and occupancy they had
+        if (p.op == LH_CROP_GREY_MEAN) {                          // grid (CJ_STRIPS, b): workgroup blockIdx.x of the slot writes partial blockIdx.x
+            __shared__ double red[256];
+            CropJit jit = {p.jfactors + slot * 4, p.jorder + slot * 4, 0.f, 4, LH_F32};
+            for (int k = 3; k >= 0; --k)                          // position of the contrast op (4 = absent)
+                if (jit.order[k] == 1) jit.kc = k;
+            if (jit.kc == 4) {                                    // workgroup-uniform: nothing to reduce, nothing is sampled
+                if (threadIdx.x == 0) p.jpartial[slot * CJ_STRIPS + blockIdx.x] = 0.0;
+                return;
+            }
+            red[threadIdx.x] = crop_slot<T, LH_JIT_MEAN>(p, base, live, nv12, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
+            __syncthreads();
+            for (int o = 128; o > 0; o >>= 1) {
+                if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) p.jpartial[slot * CJ_STRIPS + blockIdx.x] = red[0];
+            return;
         }
-        if (kx * ky == 1) crop_pixels<T, false, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc);
-        else crop_pixels<T, true, true>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc);
-    } else if (kx * ky == 1) crop_pixels<T, false, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false);
-    else crop_pixels<T, true, false>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled);
+        if (p.jfactors) {                                         // workgroup-uniform, as format: the entries without ColorJitter run the bodies below
+            double sum = 0.0;                                     // once per workgroup (uniform addresses), never per pixel
+            for (int k = 0; k < CJ_STRIPS; ++k) sum += p.jpartial[slot * CJ_STRIPS + k];
+            const CropJit jit = {p.jfactors + slot * 4, p.jorder + slot * 4, (float)(sum / ((double)p.h * p.w)), 4, p.jdtype};
+            T* out = (T*)((char*)p.dst + (long)slot * per_slot * (p.jdtype == LH_F32 ? 16 : 8));      // the slot's pixels in dst's dtype
+            crop_slot<T, LH_JIT_APPLY>(p, base, live, nv12, out, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
+            return;
+        }
+    }
+    crop_slot<T, LH_JIT_NONE>(p, base, live, nv12, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, CropJit{});
 }
 
 // What the NV12 entry adds to the RGB ones' arguments.
@@ -352,10 +443,21 @@ struct Nv12Layout {
     const float* csc12;
 };
 
-// All entries: ``who`` names the entry in the error text, max_taps = 1 is the plain crop, yuv = nullptr packed RGB frames.
+// What the ColorJitter entry adds: the per-slot draw and the grey-mean partials (lh_frames_crop_jitter_workspace_bytes).
+struct CropJitter {
+    const float* factors;
+    const int* order;
+    void* workspace;
+};
+
+// All entries: ``who`` names the entry in the error text, max_taps = 1 is the plain crop, yuv = nullptr packed RGB frames, jitter =
+// nullptr no ColorJitter (one launch; with it the grey-mean launch goes first).
 static int frames_crop_launch(const char* who, const unsigned char* frames_u8, void* out, int b, int n_frames, int hs, int ws, int h, int w,
                               int pad, int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
-                              int max_taps, int dtype, void* stream, const Nv12Layout* yuv = nullptr) {
+                              int max_taps, int dtype, void* stream, const Nv12Layout* yuv = nullptr, const CropJitter* jitter = nullptr) {
+    LH_REQUIRE(!jitter || (jitter->factors && jitter->order && jitter->workspace), "%s: bad arguments (factors_dev, order_dev or workspace is null)",
+               who);
+    LH_REQUIRE(!jitter || ((uintptr_t)jitter->workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
     LH_REQUIRE(frames_u8 && out && mean3 && std3 && mat_dev && src_frame_dev && b > 0 && b <= 65535 && n_frames > 0 && hs > 0 && ws > 0
                && h > 0 && w > 0 && pad >= 0 && wp >= w + 2 * pad, "%s: bad arguments", who);
     LH_REQUIRE(max_taps >= 1 && max_taps <= 8, "%s: max_taps must be 1..8, not %d", who, max_taps);
@@ -367,6 +469,7 @@ static int frames_crop_launch(const char* who, const unsigned char* frames_u8, v
     a.max_taps = max_taps;
     a.op = LH_CROP; a.n = a.j = a.pstride = a.ostride = 0;
     a.in0 = a.in1 = a.in2 = nullptr; a.iin = nullptr; a.out0 = a.out1 = nullptr; a.iout = nullptr;
+    a.jfactors = nullptr; a.jorder = nullptr; a.jpartial = nullptr; a.jdtype = dtype;
     a.format = yuv ? LH_FRAMES_NV12 : LH_FRAMES_RGB;
     a.pitch = a.uv_offset = a.siting = 0; a.frame_stride = 0;
     for (int c = 0; c < 9; ++c) a.k[c] = 0.f;
@@ -392,6 +495,16 @@ static int frames_crop_launch(const char* who, const unsigned char* frames_u8, v
     }
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
     const int chunks = lh_grid((long)a.hp * wp, 1024);
+    if (jitter) {
+        a.jfactors = jitter->factors; a.jorder = jitter->order; a.jpartial = (double*)jitter->workspace;
+        a.op = LH_CROP_GREY_MEAN;                                 // the samples are fp32 whatever the crop's dtype is
+        hipLaunchKernelGGL((frames_crop_kernel<float>), dim3(CJ_STRIPS, b), dim3(256), 0, (hipStream_t)stream, a);
+        LH_LAUNCH_CHECK("frames_crop_jitter_to_nhwc4 grey-mean launch");
+        a.op = LH_CROP;                                           // the apply mode: jfactors is set, the store is a.jdtype's
+        hipLaunchKernelGGL((frames_crop_kernel<float>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a);
+        LH_LAUNCH_CHECK("frames_crop_jitter_to_nhwc4 launch");
+        return LH_OK;
+    }
     LH_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((frames_crop_kernel<T>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a));
     LH_LAUNCH_CHECK(yuv ? "frames_crop_yuv_to_nhwc4 launch" : max_taps > 1 ? "frames_crop_area_to_nhwc4 launch" : "frames_crop_to_nhwc4 launch");
     return LH_OK;
@@ -418,6 +531,19 @@ extern "C" int lh_frames_crop_yuv_to_nhwc4(const unsigned char* frames_nv12, voi
     const Nv12Layout yuv = {pitch, uv_offset, frame_stride, chroma_siting, csc12};
     return frames_crop_launch("lh_frames_crop_yuv_to_nhwc4", frames_nv12, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
                               src_frame_dev, max_taps, dtype, stream, &yuv);
+}
+
+extern "C" size_t lh_frames_crop_jitter_workspace_bytes(int b) { return b > 0 ? (size_t)b * CJ_STRIPS * sizeof(double) : 0; }
+
+extern "C" int lh_frames_crop_jitter_to_nhwc4(const unsigned char* frames, void* out, int b, int n_frames, int hs, int ws, int pitch,
+                                              int uv_offset, long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad,
+                                              int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                              int max_taps, const float* factors_dev, const int* order_dev, void* workspace, int dtype,
+                                              void* stream) {
+    const Nv12Layout yuv = {pitch, uv_offset, frame_stride, chroma_siting, csc12};
+    const CropJitter jitter = {factors_dev, order_dev, workspace};
+    return frames_crop_launch("lh_frames_crop_jitter_to_nhwc4", frames, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
+                              src_frame_dev, max_taps, dtype, stream, csc12 ? &yuv : nullptr, &jitter);
 }
 
 // ------------------------------------------------------------------------------------------------ training on frames: the two modes

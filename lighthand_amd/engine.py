@@ -948,7 +948,8 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         return self.img_u8
 
     def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False,
-                        max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, perturb=False):
+                        max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, perturb=False,
+                        jitter=False):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
@@ -967,7 +968,11 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         augmentation; implies the oriented launch, a turned ROI needs it): the plan also owns ``roi_aug`` (fp32 [n][6] = c, s, k, tx,
         ty, flip per slot, identity rows until the caller writes: ``runtime.sample_roi_aug``) and ``roi_boxes`` / ``roi_rot`` /
         ``roi_mirror``, the perturbed ROI; lh_roi_perturb runs in front of lh_roi_affine, which reads the perturbed ROI, and the
-        caller's ``boxes`` / ``rot`` / ``mirror`` are never written.  False: the launch list as above.  Returns the frame buffer."""
+        caller's ``boxes`` / ``rot`` / ``mirror`` are never written.  False: the launch list as above.  ``jitter=True`` (training on
+        frames with ColorJitter): the plan also owns ``jitter_factors`` (fp32 [n][4]) and ``jitter_order`` (int32 [n][4], identity
+        factors and order -1 until the caller draws: ``runtime.sample_color_jitter``), as ``use_uint8_input(jitter=True)`` does, and
+        the image launch is lh_frames_crop_jitter_to_nhwc4 for every ``frame_format`` and ``max_taps``: the grey-mean launch and the
+        crop, one entry.  False: launches, buffers and bits as above.  Returns the frame buffer."""
         from . import topdown
         if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
             raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
@@ -991,7 +996,20 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         self.keep += [m3, s3]
         i = self._image_call_index
         slane = self.fwd[i].slane
-        if frame_format == "nv12":
+        if jitter:
+            self.jitter_factors = self._alloc(self.n, 4, dtype=torch.float32, zero=True)
+            self.jitter_factors[:, :3] = 1.0                                    # identity until the caller draws
+            self.jitter_order = torch.full((self.n, 4), -1, dtype=torch.int32, device=self.device)
+            ws_j = self._alloc(self.lib.lh_frames_crop_jitter_workspace_bytes(self.n), dtype=torch.uint8)
+            self.keep.append(self.jitter_order)
+            nv12 = (pitch, uv_offset, frame_stride, siting, csc) if frame_format == "nv12" else (0, 0, 0, 0, None)
+            self.fwd[i] = _Call(self.lib.lh_frames_crop_jitter_to_nhwc4, (
+                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws) + nv12 + (
+                self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps,
+                self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr(), self.dt),
+                ("NV12 frame crop input pipeline" if frame_format == "nv12" else "frame crop input pipeline")
+                + (", antialiased" if max_taps > 1 else "") + " + ColorJitter")
+        elif frame_format == "nv12":
             self.fwd[i] = _Call(self.lib.lh_frames_crop_yuv_to_nhwc4, (
                 self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, pitch, uv_offset, frame_stride, siting, csc,
                 self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt),

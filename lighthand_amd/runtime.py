@@ -236,27 +236,39 @@ def _roi_aug_spec(roi_aug):
 
 def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_jitter=None, targets_from_joints=True, box_padding=1.25,
                         oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left",
-                        frame_layout=None, roi_aug=None, coord_loss_weight=0.0, use_target_weight=False):
-    """TrainStep(frames=, box_padding=, oriented=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=, roi_aug=): refuse what
-    cannot run, before any device work (no device is touched here).  The options shared with InferStep follow _check_frames' /
-    _check_roi's rules.  Returns (frames as a tuple of ints or None, the roi_aug spec or None)."""
+                        frame_layout=None, roi_aug=None, coord_loss_weight=0.0, use_target_weight=False, crop_jitter=None):
+    """TrainStep(frames=, box_padding=, oriented=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=, roi_aug=,
+    crop_jitter=): refuse what cannot run, before any device work (no device is touched here).  The options shared with InferStep
+    follow _check_frames' / _check_roi's rules.  Returns (frames as a tuple of ints or None, the roi_aug spec or None), and with the
+    ``crop_jitter`` keyword a third value: the validated (brightness, contrast, saturation, hue) tuple of floats, or None."""
     checked = _check_frames(frames, input_u8, box_padding, False, 0.0, 1, 0.0, antialias, frame_format, yuv, chroma_siting, frame_layout)
     _check_roi(model, checked, oriented, (0, 1), 1.0, None)
     if checked is None:
         if roi_aug is not None:
             raise ValueError("roi_aug perturbs hand ROIs on full frames: pass frames=(n_frames, hs, ws)")
+        if crop_jitter is not None:
+            raise ValueError("crop_jitter jitters hand ROIs cropped from full frames: pass frames=(n_frames, hs, ws) (color_jitter= is "
+                             "the uint8 input's)")
         return None, None
     if geometric_aug is not None:
         raise ValueError("frames= and geometric_aug= are two augmentations of two input paths: with frames pass roi_aug=, which samples "
                          "the frame itself")
     if color_jitter is not None:
-        raise ValueError("frames= and color_jitter=: ColorJitter runs in the uint8 input kernel, the frame crop has none")
+        raise ValueError("frames= and color_jitter=: color_jitter runs in the uint8 input kernel; the frame crop's ColorJitter is "
+                         "crop_jitter=(brightness, contrast, saturation, hue)")
     if not targets_from_joints:
         raise ValueError("frames= needs targets_from_joints=True: the target is rendered from the joints taken into the crop")
     if coord_loss_weight > 0 and not use_target_weight:
         raise ValueError("coord_loss_weight > 0 with frames= needs use_target_weight=True: the joints of an empty slot lie off the map "
                          "and must carry weight 0 in the coordinate term")
-    return checked, (None if roi_aug is None else _roi_aug_spec(roi_aug))
+    spec = None if roi_aug is None else _roi_aug_spec(roi_aug)
+    if crop_jitter is None:
+        return checked, spec
+    if (not isinstance(crop_jitter, (tuple, list)) or len(crop_jitter) != 4 or not all(_is_number(v) and v >= 0 for v in crop_jitter)
+            or crop_jitter[3] > 0.5):
+        raise ValueError(f"crop_jitter must be (brightness, contrast, saturation, hue), torchvision ColorJitter ranges: four finite "
+                         f"numbers >= 0, hue <= 0.5, not {crop_jitter!r}")
+    return checked, spec, tuple(float(v) for v in crop_jitter)
 
 
 class TrainStep:
@@ -265,7 +277,7 @@ class TrainStep:
                  input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
                  use_target_weight=False, ohkm_topk=0, target_encoding="quantised", coord_loss_weight=0.0, soft_argmax_beta=100.0,
                  frames=None, box_padding=1.25, oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"),
-                 chroma_siting="left", frame_layout=None, roi_aug=None):
+                 chroma_siting="left", frame_layout=None, roi_aug=None, crop_jitter=None):
         """``coord_loss_weight`` = L > 0 (opt-in, integral regression; 0 = the step as it was: the same launches and buffers) adds
         L * mean |soft-arg-max(beta * heat-map) * 4 - joint| to the loss and its gradient to ``plan.dout_nchw`` (lh_integral_l1 right
         behind the MSE kernel, on the joints the target was rendered from, weighted by ``target_weight`` under ``use_target_weight``,
@@ -284,12 +296,19 @@ class TrainStep:
         ``roi_aug=(rotation_deg, scale, shift[, mirror_prob])`` or a dict that may also carry prob / generator: every call draws one
         perturbation per slot (sample_roi_aug) into ``plan.roi_aug``; lh_roi_perturb moves, scales, turns and mirrors the caller's
         ROI in front of lh_roi_affine, so the crop samples the frame once and its margin is real context.  The caller's ``boxes`` /
-        ``rot`` / ``mirror`` are never written.  A mirrored ROI needs no joint permutation (a hand has no left / right joint pairs)."""
+        ``rot`` / ``mirror`` are never written.  A mirrored ROI needs no joint permutation (a hand has no left / right joint pairs).
+        ``crop_jitter=(brightness, contrast, saturation, hue)``: torchvision ColorJitter ranges (the reference: 0.5 each), the frames'
+        ``color_jitter``: every call draws factors and an op order per slot (sample_color_jitter, ``aug`` as on the uint8 path) into
+        ``plan.jitter_factors`` / ``plan.jitter_order`` and lh_frames_crop_jitter_to_nhwc4 applies them to the crop between the sample
+        and Normalize; contrast blends with the grey mean of the slot's own crop, black outside the frame included.  None: the
+        launches and buffers without it."""
         if not _is_number(coord_loss_weight) or coord_loss_weight < 0:
             raise ValueError(f"coord_loss_weight must be a finite number >= 0, not {coord_loss_weight!r}")
-        frames, roi_aug = _check_train_frames(model, frames, input_u8, geometric_aug, color_jitter, targets_from_joints, box_padding, oriented,
-                                              antialias, frame_format, yuv, chroma_siting, frame_layout, roi_aug, coord_loss_weight,
-                                              use_target_weight)
+        checked = _check_train_frames(model, frames, input_u8, geometric_aug, color_jitter, targets_from_joints, box_padding, oriented,
+                                      antialias, frame_format, yuv, chroma_siting, frame_layout, roi_aug, coord_loss_weight,
+                                      use_target_weight, crop_jitter)
+        frames, roi_aug = checked[:2]
+        crop_jitter = checked[2] if crop_jitter is not None else None
         self.lib = _lib.load()
         _check_beta(soft_argmax_beta)
         if coord_loss_weight > 0 and not targets_from_joints:
@@ -339,6 +358,7 @@ class TrainStep:
         # frames=(n_frames, hs, ws): the input is hand ROIs on full frames (the docstring); joints_crop takes joints_aug's place
         self.frames = self.boxes = self.frame_index = self.rot = self.mirror = self.joints_crop = self.frame_preds = None
         self.roi_aug, self.oriented = roi_aug, False
+        self.crop_jitter = crop_jitter
         self.antialias = _antialias_taps(antialias)
         self.frame_format = frame_format if frames else None
         if frames:
@@ -346,7 +366,7 @@ class TrainStep:
             self.oriented = bool(oriented) or roi_aug is not None      # a turned ROI needs the oriented launch
             extra = dict(frame_format="nv12", yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout) if frame_format == "nv12" else {}
             self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
-                                                    perturb=roi_aug is not None, **extra)
+                                                    perturb=roi_aug is not None, **extra, **(dict(jitter=True) if crop_jitter else {}))
             self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
             self.rot, self.mirror = self.plan.rot, self.plan.mirror
             self.joints_crop = torch.zeros_like(self.joints)
@@ -590,7 +610,7 @@ class TrainStep:
         """``joints``: [batch, J, >=2]; under ``use_target_weight`` a third column is the visibility (two columns = all visible).
         A step built with ``frames=`` takes ``frames`` / ``boxes`` / ``frame_index`` (and ``rot`` / ``mirror`` under ``oriented`` or
         ``roi_aug``) in place of ``images``, copied into the static buffers as InferStep does; its ``joints`` are frame coordinates.
-        ``aug`` (bool [batch], optional; uint8 input with color_jitter only): which samples are jittered this step
+        ``aug`` (bool [batch], optional; uint8 input with color_jitter, or frames with crop_jitter): which samples are jittered this step
         (the reference's fixed --ratio_of_aug subset, src/tools/dataset.py:133); None = all of them."""
         if getattr(self.model, "_lh_generation", 0) != self._model_generation:
             raise LightHandError("the model's parameter storages were re-created (.to() / .cuda() / .float()) after this TrainStep "
@@ -611,6 +631,10 @@ class TrainStep:
             g = self.roi_aug                       # read by the replay from the plan's buffer, never baked into the graph
             self.plan.roi_aug.copy_(sample_roi_aug(self.joints.shape[0], g["rotation"], g["scale"], g["shift"], g["mirror_prob"],
                                                    prob=g["prob"], generator=g["generator"]), non_blocking=True)
+        if self.crop_jitter is not None:
+            f, o = sample_color_jitter(self.joints.shape[0], *self.crop_jitter, mask=aug)
+            self.plan.jitter_factors.copy_(f, non_blocking=True)
+            self.plan.jitter_order.copy_(o, non_blocking=True)
         if images is not None:
             (self.images_u8 if images.dtype == torch.uint8 and self.images_u8 is not None else self.images).copy_(images, non_blocking=True)
         if self.color_jitter is not None and self.images_u8 is not None:

@@ -42,6 +42,8 @@ are the joints in FRAME coordinates and whose bounds are the hand box (tools.syn
 the frame is sampled once, so the margin of a turned or shrunk crop is real context), ``--oriented``, ``--antialias [N]`` and
 ``--frame_format nv12 [--yuv_matrix --yuv_range --chroma_siting]`` are InferStep's crop options, so the model trains on the crop it is
 deployed behind; validation crops the un-augmented ROI with the same options and scores loss / PCK / EPE in crop coordinates.
+``--ratio_of_aug`` > 0 turns on ColorJitter(0.5 x 4) on the crops (TrainStep(crop_jitter=)) for the samples with
+``idx < len(dataset) * ratio_of_aug``, as on raw uint8 images; validation never jitters.
 
 Datasets (src/tools/train.py:24-38 builds them from files this repository cannot ship): ``main(args, train_set=,
 val_set=)`` takes any ``torch.utils.data.Dataset`` whose samples are tuples starting with ``(image, joint_2d)`` --
@@ -249,6 +251,19 @@ class _WithAugFlag(torch.utils.data.Dataset):
     def __getitem__(self, i):
         s = self.base[i]
         return s[0], torch.as_tensor(s[1], dtype=torch.float32)[:, :3], i < self.limit
+
+
+class _FramesWithAugFlag(torch.utils.data.Dataset):
+    """(frame, joint_2d, box) -> (frame, joint_2d, box, jitter?): _WithAugFlag's rule for the samples of --frame_size."""
+
+    def __init__(self, base, ratio_of_aug):
+        self.base, self.limit = base, len(base) * ratio_of_aug
+
+    def __len__(self):
+        return len(self.base)
+
+    def __getitem__(self, i):
+        return tuple(self.base[i]) + (i < self.limit,)
 
 
 def _sample_kind(ds):
@@ -503,6 +518,7 @@ def main(args, train_set=None, val_set=None):
         kind = val_kind = "frames"
         raw_hw = val_hw = None
         workers = 0
+        train_set = _FramesWithAugFlag(train_set, args.ratio_of_aug)
     else:
         kind, raw_hw = _sample_kind(train_set)
         val_kind, val_hw = _sample_kind(val_set)
@@ -528,13 +544,16 @@ def main(args, train_set=None, val_set=None):
     sync = parallel.GradSync(world) if world > 1 else None
     # raw uint8 frames: ToTensor / Resize / ColorJitter(0.5, 0.5, 0.5, 0.5) / Normalize fused on the device (dataset.py:128-159)
     jitter = (0.5, 0.5, 0.5, 0.5) if kind == "u8" and args.ratio_of_aug > 0 else None
+    crop_jitter = (0.5, 0.5, 0.5, 0.5) if kind == "frames" and args.ratio_of_aug > 0 else None      # the same chain on the frame crops
     loss_kw = dict(use_target_weight=args.use_target_weight, ohkm_topk=args.ohkm_topk,
                    target_encoding="unbiased" if args.unbiased_target else "quantised",
                    coord_loss_weight=args.coord_loss_weight, soft_argmax_beta=args.soft_argmax_beta)
 
     def frame_kw(b):
-        """--frame_size: one frame per slot (frame_index stays the plan's arange), the crop options and the ROI augmentation."""
-        return dict(frames=(b,) + tuple(frame_size), roi_aug=roi_aug(args), **frame_options(args)) if frame_size is not None else {}
+        """--frame_size: one frame per slot (frame_index stays the plan's arange), the crop options and the two augmentations."""
+        if frame_size is None:
+            return {}
+        return dict(frames=(b,) + tuple(frame_size), roi_aug=roi_aug(args), crop_jitter=crop_jitter, **frame_options(args))
 
     step = TrainStep(model, args.batch_size, args.size, args.size, optimizer=optimizer, use_graph=not args.no_graph, grad_sync=sync,
                      input_u8=raw_hw, color_jitter=jitter, loss_scale=loss_scale, geometric_aug=geo, **loss_kw, **frame_kw(args.batch_size))
@@ -563,11 +582,14 @@ def main(args, train_set=None, val_set=None):
         return val_steps[b]
 
     def train_batch(it, batch):
+        if frame_size is not None:                 # (frame, joints in frame coordinates, box, jitter?)
+            images, joints, boxes, aug = batch
+            st = step_for(images.shape[0])
+            st(frames=images.cuda(non_blocking=True), boxes=boxes.cuda(non_blocking=True), joints=joints.cuda(non_blocking=True),
+               aug=aug if crop_jitter else None)
+            return lambda: st.loss
         images, joints, aug = batch
         st = step_for(images.shape[0])
-        if frame_size is not None:                 # (frame, joints in frame coordinates, box)
-            st(frames=images.cuda(non_blocking=True), boxes=aug.cuda(non_blocking=True), joints=joints.cuda(non_blocking=True))
-            return lambda: st.loss
         st(images.cuda(non_blocking=True), joints.cuda(non_blocking=True), aug=aug if jitter else None)
         return lambda: st.loss
 

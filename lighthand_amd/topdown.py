@@ -23,7 +23,11 @@ and tests.
 Training on frames (lh_roi_perturb / lh_affine_points_inv, runtime.TrainStep(frames=..., roi_aug=...)): ``roi_perturb`` turns the
 caller's ROI and a drawn row (c, s, k, tx, ty, flip) into the ROI the crop uses, ``affine_points_inv`` takes frame coordinates into
 the crop through the inverse of the crop matrix (``POINT_OFF`` for a slot that has none); ``roi_perturb_host`` /
-``affine_points_inv_host`` restate them in numpy, in fp32 or, as the yardstick, in fp64."""
+``affine_points_inv_host`` restate them in numpy, in fp32 or, as the yardstick, in fp64.
+
+ColorJitter on the crop (lh_frames_crop_jitter_to_nhwc4, runtime.TrainStep(frames=..., crop_jitter=...)): ``frames_crop(...,
+jitter=(factors, order))`` is the launch, ``frames_crop_jitter_host`` its rule in numpy -- the host crop stopped in front of
+Normalize, csrc/color_jitter.h's four ops (``color_jitter_host``), Normalize -- in fp32 or, as the yardstick, in fp64."""
 import numpy as np
 
 F = np.float32
@@ -84,18 +88,29 @@ def _sample_host(img, hs, ws, fx, fy):
     return np.where(inside, top + (bot - top) * wy, F(0)).astype(np.float32), inside
 
 
+def _normalise_host(c, mean, std, dtype=np.float32):
+    """(c - mean) * (1 / std) per channel on [b][3][h][w], the crop kernels' Normalize (1 / std is formed in fp32)."""
+    mean = np.asarray(mean, np.float32).astype(dtype)[None, :, None, None]
+    istd = (F(1) / np.asarray(std, np.float32)).astype(dtype)[None, :, None, None]
+    return ((c - mean) * istd).astype(dtype)
+
+
 def frames_crop_host(frames, mat, src_frame, size, max_taps=1, mean=MEAN, std=STD):
     """uint8 frames [n][hs][ws][3], mat [b][6], src_frame [b], size = (h, w) of the crop -> normalised fp32 [b][3][h][w];
     lh_frames_crop_area_to_nhwc4 in numpy (``max_taps=1``: lh_frames_crop_to_nhwc4), fp32 in the kernel's order: per slot
     (kx, ky) = crop_taps_host, per pixel the kx * ky samples at ux = ox + (2*i + 1 - kx) / (2*kx), uy likewise (j outside, i inside)
     are summed on the raw 0..255 values, a sample outside the frame adding 0, then (acc * (1 / (kx*ky))) * (1/255) and Normalize."""
+    return _normalise_host(_crop_unit_host(frames, mat, src_frame, size, max_taps), mean, std)
+
+
+def _crop_unit_host(frames, mat, src_frame, size, max_taps=1):
+    """frames_crop_host stopped in front of Normalize: the pixels' c in 0..1, fp32 [b][3][h][w]."""
     frames = np.asarray(frames)
     n, hs, ws = frames.shape[:3]
     h, w = int(size[0]), int(size[1])
     mat = np.asarray(mat, np.float32).reshape(-1, 6)
     src = np.asarray(src_frame, np.int32).reshape(-1)
     taps = crop_taps_host(mat, max_taps)
-    mean, istd = np.asarray(mean, np.float32)[:, None, None], F(1) / np.asarray(std, np.float32)[:, None, None]
     oy, ox = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
     out = np.empty((len(src), 3, h, w), np.float32)
     for s in range(len(src)):
@@ -112,8 +127,7 @@ def frames_crop_host(frames, mat, src_frame, size, max_taps=1, mean=MEAN, std=ST
                         acc += _sample_host(img, hs, ws, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5)[0]
         else:
             kx = ky = 1
-        c = (acc * (F(1) / F(kx * ky))) * (F(1) / F(255))
-        out[s] = (c - mean) * istd
+        out[s] = (acc * (F(1) / F(kx * ky))) * (F(1) / F(255))
     return out
 
 
@@ -250,6 +264,13 @@ def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("b
     frames_crop_host's tap loop with the NV12 sample (csrc/topdown.hip's header comment) in the RGB one's place.  ``yuv`` is
     (standard, range) or the 12 coefficients, ``chroma_siting`` "left" or "center".  ``dtype=np.float64``: the same operations in fp64
     on the same fp32 matrices and coefficients (the tap counts stay crop_taps_host's) -- what the fp32 order is measured against."""
+    return _normalise_host(_crop_unit_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv, chroma_siting, max_taps, layout, dtype),
+                           mean, std, dtype)
+
+
+def _crop_unit_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("bt709", "limited"), chroma_siting="left", max_taps=1,
+                         layout=None, dtype=np.float32):
+    """frames_crop_nv12_host stopped in front of Normalize: the pixels' c in 0..1, [b][3][h][w] of ``dtype``."""
     T = np.dtype(dtype).type
     hs, ws = int(frame_size[0]), int(frame_size[1])
     pitch, uv_offset, frame_stride, rows = _check_layout(hs, ws, layout)
@@ -264,7 +285,6 @@ def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("b
     mat = np.asarray(mat, np.float32).reshape(-1, 6)
     src = np.asarray(src_frame, np.int32).reshape(-1)
     taps = crop_taps_host(mat, max_taps)
-    mean, istd = np.asarray(mean, np.float32).astype(dtype)[:, None, None], (F(1) / np.asarray(std, np.float32)).astype(dtype)[:, None, None]
     oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
     out = np.empty((len(src), 3, h, w), dtype)
     for s in range(len(src)):
@@ -282,9 +302,86 @@ def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("b
                                                  (m3 * ux + m4 * uy) + m5, T)[0]
         else:
             kx = ky = 1
-        c = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
-        out[s] = (c - mean) * istd
+        out[s] = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
     return out
+
+
+# ---- ColorJitter on the crop: csrc/color_jitter.h's four ops in numpy, in the kernel's order of operations (T = the evaluation type)
+def _cj_clamp01(v, T):
+    return np.minimum(np.maximum(v, T(0)), T(1))
+
+
+def _cj_gray(c, T):
+    return (T(F(0.2989)) * c[0] + T(F(0.587)) * c[1]) + T(F(0.114)) * c[2]
+
+
+def _cj_blend(c, o, r, T):
+    """clamp(r * c + (1 - r) * o) per channel; ``o`` is a scalar or one plane."""
+    return np.stack([_cj_clamp01(r * c[ch] + (T(1) - r) * o, T) for ch in range(3)])
+
+
+def _cj_hue(c, f, T):
+    r, g, b = c
+    maxc, minc = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    eq = maxc == minc
+    cr = maxc - minc
+    s = cr / np.where(eq, T(1), maxc)
+    div = np.where(eq, T(1), cr)
+    rc, gc, bc = (maxc - r) / div, (maxc - g) / div, (maxc - b) / div
+    h = np.where(maxc == r, bc - gc, np.where(maxc == g, (T(2) + rc) - bc, (T(4) + gc) - rc))
+    h = np.fmod(h / T(6) + T(1), T(1))
+    h = np.fmod(h + f, T(1))
+    h = np.where(h < T(0), h + T(1), h)
+    h6 = h * T(6)
+    fl = np.floor(h6)
+    fr = h6 - fl
+    i = fl.astype(np.int32) % 6
+    v = maxc
+    p = _cj_clamp01(v * (T(1) - s), T)
+    q = _cj_clamp01(v * (T(1) - s * fr), T)
+    t = _cj_clamp01(v * (T(1) - s * (T(1) - fr)), T)
+    return np.stack([np.choose(i, [v, q, p, p, t, v]), np.choose(i, [t, v, v, q, p, p]), np.choose(i, [p, p, t, v, v, q])])
+
+
+def color_jitter_host(c, factors, order, dtype=np.float32):
+    """One crop c [3][h][w] in 0..1 through the ops of ``order`` (ids 0..3 = brightness, contrast, saturation, hue; negative = skip)
+    with ``factors`` [4]: cj_apply of csrc/color_jitter.h on every pixel, the contrast op's mean = the crop's grey mean when the op
+    runs, summed in fp64 and rounded once ((float)(sum / (h*w)); the kernels sum partials, so the last bit of the mean may differ)."""
+    T = np.dtype(dtype).type
+    c = np.asarray(c, dtype)
+    f = np.asarray(factors, np.float32).astype(dtype)
+    with np.errstate(all="ignore"):
+        for op in (int(v) for v in order):
+            if op == 0:
+                c = _cj_blend(c, T(0), f[0], T)
+            elif op == 1:
+                mean = T(np.float32(_cj_gray(c, T).astype(np.float64).sum() / (c.shape[1] * c.shape[2]))) if T is np.float32 else \
+                    T(_cj_gray(c, T).sum() / (c.shape[1] * c.shape[2]))
+                c = _cj_blend(c, mean, f[1], T)
+            elif op == 2:
+                c = _cj_blend(c, _cj_gray(c, T), f[2], T)
+            elif op == 3:
+                c = _cj_hue(c, f[3], T)
+    return c.astype(dtype)
+
+
+def frames_crop_jitter_host(frames, mat, src_frame, size, factors, order, max_taps=1, mean=MEAN, std=STD, frame_format="rgb",
+                            frame_size=None, yuv=("bt709", "limited"), chroma_siting="left", layout=None, dtype=np.float32):
+    """lh_frames_crop_jitter_to_nhwc4 in numpy: frames_crop_host (``frame_format="nv12"``: frames_crop_nv12_host, with ``frame_size``,
+    ``yuv``, ``chroma_siting`` and ``layout`` as there) stopped in front of Normalize, then per slot the ops of ``order`` int [b][4]
+    with ``factors`` fp32 [b][4] (color_jitter_host), then Normalize -> [b][3][h][w].  fp32 in the kernel's order; a slot whose order
+    is all negative is the un-jittered host crop bit for bit.  ``dtype=np.float64``: the jitter and Normalize (and, for NV12, the
+    sampling) evaluated in fp64 on the same inputs -- what the fp32 order is measured against."""
+    if frame_format not in ("rgb", "nv12"):
+        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
+    if frame_format == "nv12":
+        c = _crop_unit_nv12_host(frames, frame_size, mat, src_frame, size, yuv, chroma_siting, max_taps, layout, dtype)
+    else:
+        c = _crop_unit_host(frames, mat, src_frame, size, max_taps).astype(dtype)
+    factors = np.asarray(factors, np.float32).reshape(c.shape[0], 4)
+    order = np.asarray(order, np.int32).reshape(c.shape[0], 4)
+    c = np.stack([color_jitter_host(c[s], factors[s], order[s], dtype) for s in range(c.shape[0])])
+    return _normalise_host(c, mean, std, dtype)
 
 
 def boxes_from_keypoints_host(preds, maxvals, boxes, src_frame, min_score=0.1, min_joints=8, min_side=16.0):
@@ -522,13 +619,15 @@ def box_affine(boxes, frame_index, n_frames, size, padding=1.25):
 
 
 def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD, frame_format="rgb", frame_size=None,
-                yuv=("bt709", "limited"), chroma_siting="left", layout=None):
+                yuv=("bt709", "limited"), chroma_siting="left", layout=None, jitter=None):
     """Device tensors frames uint8 [n][hs][ws][3], mat fp32 [b][6], src_frame int32 [b] -> the normalised crops as NHWC4
     [b][h][w][4] of ``dtype`` (torch.float32 by default; no padding, channel 3 is 0) for an h x w = ``size`` crop: one
     lh_frames_crop_area_to_nhwc4 launch on the current stream.  ``max_taps`` 1..8: the most samples per crop pixel and axis that a
     minified ROI averages (crop_taps_host); 1 is the plain crop.  ``frame_format="nv12"``: frames uint8 [n][rows][pitch] of
     ``frame_size`` = (hs, ws) in ``layout`` (nv12_layout's tuple; None: tight), converted per sample with ``yuv`` ((standard, range)
-    or 12 coefficients) and ``chroma_siting`` ("left" / "center"): one lh_frames_crop_yuv_to_nhwc4 launch."""
+    or 12 coefficients) and ``chroma_siting`` ("left" / "center"): one lh_frames_crop_yuv_to_nhwc4 launch.  ``jitter=(factors, order)``
+    (device tensors fp32 [b][4] and int32 [b][4], runtime.sample_color_jitter's draw): ColorJitter between the sample and Normalize,
+    lh_frames_crop_jitter_to_nhwc4 for either format (the grey-mean launch, then the crop)."""
     import ctypes as C
     import torch
     from . import _lib
@@ -541,6 +640,15 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
     mat = mat.to(torch.float32).contiguous()
     src_frame = src_frame.to(torch.int32).contiguous()
     b = mat.shape[0]
+    jit = None
+    if jitter is not None:
+        factors, order = (t.contiguous() for t in jitter)
+        if (factors.dtype != torch.float32 or order.dtype != torch.int32 or tuple(factors.shape) != (b, 4) or tuple(order.shape) != (b, 4)
+                or factors.device != mat.device or order.device != mat.device or not mat.is_cuda):
+            raise _lib.LightHandError(f"frames_crop: jitter = (factors fp32 [b, 4], order int32 [b, 4]) on the crop's device, got "
+                                      f"{tuple(factors.shape)} {factors.dtype} / {tuple(order.shape)} {order.dtype}")
+        ws_j = torch.empty(max(1, _lib.load().lh_frames_crop_jitter_workspace_bytes(b) // 8), dtype=torch.float64, device=mat.device)
+        jit = (factors.data_ptr(), order.data_ptr(), ws_j.data_ptr())
     if frame_format == "nv12":
         if not (isinstance(frame_size, (tuple, list)) and len(frame_size) == 2):
             raise ValueError(f"frame_format='nv12' needs frame_size=(hs, ws), not {frame_size!r}")
@@ -555,6 +663,12 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
         out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
         m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         with torch.cuda.device(frames.device):
+            if jit is not None:
+                _lib.check(_lib.load().lh_frames_crop_jitter_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, frames.shape[0], hs, ws, pitch,
+                                                                      uv_offset, frame_stride, siting, csc, h, w, 0, w, m3, s3, mat.data_ptr(),
+                                                                      src_frame.data_ptr(), max_taps, *jit, _lib.dtype_code(dtype), _stream()),
+                           "lh_frames_crop_jitter_to_nhwc4")
+                return out
             _lib.check(_lib.load().lh_frames_crop_yuv_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, frames.shape[0], hs, ws, pitch, uv_offset,
                                                                frame_stride, siting, csc, h, w, 0, w, m3, s3, mat.data_ptr(),
                                                                src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
@@ -569,6 +683,11 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
     out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     with torch.cuda.device(frames.device):
+        if jit is not None:
+            _lib.check(_lib.load().lh_frames_crop_jitter_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, n, hs, ws, 0, 0, 0, 0, None, h, w, 0, w, m3,
+                                                                  s3, mat.data_ptr(), src_frame.data_ptr(), max_taps, *jit,
+                                                                  _lib.dtype_code(dtype), _stream()), "lh_frames_crop_jitter_to_nhwc4")
+            return out
         _lib.check(_lib.load().lh_frames_crop_area_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, n, hs, ws, h, w, 0, w, m3, s3, mat.data_ptr(),
                                                             src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
                    "lh_frames_crop_area_to_nhwc4")

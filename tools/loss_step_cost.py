@@ -8,8 +8,9 @@ median over the rounds.  --coord_loss_weight L adds a leg: the plain step plus t
 --frames times another pair instead, by the same method: the step on ready uint8 crops, TrainStep(input_u8=(256, 256)), against the step
 that crops its hand ROIs from 32 full frames of 1080 x 1920 on the device, TrainStep(frames=(32, 1080, 1920)) (lh_box_affine +
 lh_frames_crop_to_nhwc4 in the uint8 kernel's place, lh_affine_points_inv in front of the target render, lh_affine_points behind the
-decode), and the same with roi_aug=(30, 0.25, 0.1, 0.5) (lh_roi_perturb + lh_roi_affine, a new draw copied in per replay): seeded boxes of
-200..400 frame pixels, two per frame.
+decode), the same with roi_aug=(30, 0.25, 0.1, 0.5) (lh_roi_perturb + lh_roi_affine, a new draw copied in per replay), and both with
+crop_jitter=(0.5, 0.5, 0.5, 0.5) (lh_frames_crop_jitter_to_nhwc4: the grey-mean launch and ColorJitter in the crop, a new draw per
+replay): seeded boxes of 200..400 frame pixels, two per frame.
 usage (GPU box): python tools/loss_step_cost.py [steps] [rounds] [--coord_loss_weight L | --frames]"""
 import os
 import statistics
@@ -62,6 +63,10 @@ def frames_main():
     legs = [("uint8 crops", dict(input_u8=(256, 256)), lambda st: st(crops, crop_joints)),
             ("frames", dict(frames=(n, hs, ws)), lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt)),
             ("frames+roi_aug", dict(frames=(n, hs, ws), roi_aug=(30.0, 0.25, 0.1, 0.5)),
+             lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt)),
+            ("frames+crop_jitter", dict(frames=(n, hs, ws), crop_jitter=(0.5, 0.5, 0.5, 0.5)),
+             lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt)),
+            ("frames+roi_aug+crop_jitter", dict(frames=(n, hs, ws), roi_aug=(30.0, 0.25, 0.1, 0.5), crop_jitter=(0.5, 0.5, 0.5, 0.5)),
              lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt))]
     forms = {}
     for tag, kw, first in legs:
@@ -76,7 +81,7 @@ def frames_main():
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} 256^2 bf16, {n} frames of {hs} x {ws} ({frames.numel() / 1e6:.0f} MB) against {crops.numel() / 1e6:.1f} MB of crops:", flush=True)
     for tag, v in ms.items():
-        print(f"  {tag:16s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops; rounds: "
+        print(f"  {tag:26s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops; rounds: "
               f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
 
 
