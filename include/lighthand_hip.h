@@ -153,6 +153,42 @@ int lh_frames_crop_jitter_to_nhwc4(const unsigned char* frames, void* out, int b
                                    long frame_stride, int chroma_siting, const float* csc12, int h, int w, int pad, int wp,
                                    const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev, int max_taps,
                                    const float* factors_dev, const int* order_dev, void* workspace, int dtype, void* stream);
+/* Decoder surfaces read in place, and the other 4:2:0 flavours (opt-in; the same kernel, the entries above keep their arguments,
+ * checks and output bits).  The frame source is EITHER frames with frame_stride (frame f starts at byte f * frame_stride, as
+ * lh_frames_crop_yuv_to_nhwc4's buffer) OR surface_table_dev, int64 [n_frames] in device memory, 8-byte aligned: entry f is the device
+ * address of frame f.  The table is read by the launch, so a captured graph follows a rebound table with no recapture; an entry of 0
+ * is an empty frame -- it is tested before any address is formed, and the slot's crop is black as an empty slot's.  Exactly one of
+ * the two is non-NULL.  layout (HOST, copied by value) says where a sample's bytes are, from the frame's first byte:
+ *   format LH_FRAMES_FMT_RGB      packed [hs][ws][3]; nothing else of the struct is read
+ *          LH_FRAMES_FMT_NV12     luma (x, y) at y*pitch + x;    Cb of chroma sample (cx, cy) at cb_offset + cy*c_pitch + 2*cx, Cr = Cb + 1
+ *          LH_FRAMES_FMT_NV21     luma as nv12;                  Cr at cr_offset + cy*c_pitch + 2*cx, Cb = Cr + 1
+ *          LH_FRAMES_FMT_YUV420P  luma y*pitch + x;              Cb at cb_offset + cy*c_pitch + cx, Cr at cr_offset + cy*c_pitch + cx
+ *                                 (cr_offset below cb_offset is YV12)
+ *          LH_FRAMES_FMT_P010     luma y*pitch + 2*x;            Cb at cb_offset + cy*c_pitch + 4*cx, Cr = Cb + 2; samples are
+ *                                 little-endian 16-bit and a texel's value is (float)(u16 >> 6) * 0.25f: the 10 significant bits on the
+ *                                 8-bit scale, exact in fp32; the low 6 bits are never read as data
+ * Everything after the texel fetch is lh_frames_crop_yuv_to_nhwc4's rule in its fp32 order (inside test, clamps, chroma position
+ * from chroma_siting, the two blends, e = yuv - o, the 3 x 3 product, the clip) and from there the RGB entries' handling; NV12 input
+ * gives that entry's bits.  factors_dev / order_dev / workspace: all NULL, or lh_frames_crop_jitter_to_nhwc4's triple (ColorJitter
+ * between the sample and Normalize, its two launches).  Every launch is the fp32 instantiation's, which stores in dtype.
+ * LH_ERR_ARG, before any launch: both sources NULL or both set; an unknown format; odd sides or sides < 2; pitch or c_pitch below a
+ * row's bytes; a chroma plane that starts inside the luma plane; overlapping planar chroma planes; cb_offset / cr_offset not in the
+ * format's relation; planes that end outside frame_bytes or at 2^31 or beyond; frame_stride below the bytes a frame's samples span;
+ * an odd p010 pitch, c_pitch, offset, frames address or frame_stride; chroma_siting outside {0, 1}; a coefficient that is not
+ * finite; and what the entries above refuse. */
+enum { LH_FRAMES_FMT_RGB = 0, LH_FRAMES_FMT_NV12 = 1, LH_FRAMES_FMT_NV21 = 2, LH_FRAMES_FMT_YUV420P = 3, LH_FRAMES_FMT_P010 = 4 };
+typedef struct lh_frames_layout {
+    int format;                 /* LH_FRAMES_FMT_* */
+    int pitch, c_pitch;         /* bytes between luma rows / between chroma rows */
+    int cb_offset, cr_offset;   /* byte offsets of the first Cb and the first Cr sample */
+    int frame_bytes;            /* the bytes of one frame: every plane ends inside them */
+    int chroma_siting;          /* 0 left, 1 center */
+    float csc12[12];            /* k[3][3] row-major, then o[3] */
+} lh_frames_layout;
+int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, void* out, long frame_stride, const long long* surface_table_dev,
+                                     const lh_frames_layout* layout, int b, int n_frames, int hs, int ws, int h, int w, int pad,
+                                     int wp, const float* mean3, const float* std3, const float* mat_dev, const int* src_frame_dev,
+                                     int max_taps, const float* factors_dev, const int* order_dev, void* workspace, int dtype, void* stream);
 /* preds_dev fp32 [b][j][2] (frame coordinates), maxvals_dev fp32 [b][j] -> next_boxes_dev fp32 [b][4], lost_dev int32 [b]: the bounds
  * of the keypoints with maxval >= min_score, each side widened about its centre to at least min_side.  With fewer than min_joints
  * such keypoints, or for an empty slot (src_frame < 0), next_boxes[i] = boxes[i] and lost[i] = 1; otherwise lost[i] = 0.  No

@@ -110,6 +110,14 @@ class PackConv(C.Structure):
                 ("packs", PackOut * 5)]
 
 
+LH_FRAMES_FMT = {"rgb": 0, "nv12": 1, "nv21": 2, "yuv420p": 3, "p010": 4}          # LH_FRAMES_FMT_* of the header
+
+
+class FramesLayout(C.Structure):       # lh_frames_crop_surfaces_to_nhwc4
+    _fields_ = [("format", C.c_int), ("pitch", C.c_int), ("c_pitch", C.c_int), ("cb_offset", C.c_int), ("cr_offset", C.c_int),
+                ("frame_bytes", C.c_int), ("chroma_siting", C.c_int), ("csc12", C.c_float * 12)]
+
+
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/lighthand_hip.h declares
@@ -133,6 +141,8 @@ SIGNATURES = {
     "lh_frames_crop_jitter_workspace_bytes": (_SZ, [_I]),
     "lh_frames_crop_jitter_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _I, C.POINTER(C.c_float), _I, _I, _I, _I, C.POINTER(C.c_float),
                                             C.POINTER(C.c_float), _P, _P, _I, _P, _P, _P, _I, _P]),
+    "lh_frames_crop_surfaces_to_nhwc4": (_I, [_P, _P, _L, _P, C.POINTER(FramesLayout), _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), _P, _P, _I, _P, _P, _P, _I, _P]),
     "lh_keypoints_to_boxes": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _F, _P, _P, _P]),
     "lh_roi_affine": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
     "lh_keypoints_to_rois": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P]),

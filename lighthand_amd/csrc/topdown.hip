@@ -94,7 +94,20 @@ extern "C" int lh_box_affine(const float* boxes_dev, const int* frame_index_dev,
 // the slot's partials in index order once per workgroup, mean = (float)(sum / (h*w)), and runs cj_apply(c, factors, order, 0, 4, mean)
 // between the sample and Normalize.  Order (-1, -1, -1, -1) touches nothing: the un-jittered crop bit for bit.  An empty slot stays
 // black: every op maps black with mean 0 to black.  topdown.py: frames_crop_jitter_host.
-enum { LH_FRAMES_RGB = 0, LH_FRAMES_NV12 = 1 };
+//
+// Decoder surfaces and the other 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4): where a sample's bytes are.  The frame source is the
+// buffer above (frame f at byte f * frame_stride) or a SURFACE TABLE, int64 [n_frames] in device memory: entry f is the device address
+// of frame f, read at every launch -- the surfaces of a captured graph change with no recapture.  The entry is a scalar load (the slot
+// is blockIdx.y) and is tested before any address is formed from it: 0 is an empty frame, the slot's crop is black as an empty slot's.
+// One plane descriptor (format = LH_FRAMES_420, or LH_FRAMES_420W for 16-bit samples) covers NV12, NV21, planar yuv420p and 10-bit
+// P010: luma sample (x, y) at y*pitch + x*sample_bytes, Cb / Cr of chroma sample (cx, cy) at cb_offset / cr_offset + cy*c_pitch +
+// cx*c_step.  A 16-bit sample is little-endian and its texel value is (float)(u16 >> 6) * 0.25f -- the 10 significant bits on the
+// 8-bit scale, exact in fp32, the low 6 bits never data.  Everything after the texel fetch is the NV12 rule above, in the same order
+// (crop_sample_420 is crop_sample_nv12 with the descriptor's addresses), so NV12 through the descriptor gives
+// lh_frames_crop_yuv_to_nhwc4's bits.  The sample width picks the body in front of the pixel loops, as format does.
+// All of it is the fp32 instantiation's (gen != 0), which then stores in jdtype as the ColorJitter apply mode does: the 16-bit
+// instantiations carry none of it.  topdown.py: frames_crop_yuv420_host.
+enum { LH_FRAMES_RGB = 0, LH_FRAMES_NV12 = 1, LH_FRAMES_420 = 2, LH_FRAMES_420W = 3 };
 
 struct CropArgs {
     const unsigned char* src;
@@ -120,9 +133,13 @@ struct CropArgs {
     const int* jorder;                                            // [b][4] op ids, negative = skip
     double* jpartial;                                             // [b][CJ_STRIPS]: written by LH_CROP_GREY_MEAN, read by the apply mode
     int jdtype;                                                   // the apply mode: the dtype of dst (the launch is the fp32 instantiation's)
+    // lh_frames_crop_surfaces_to_nhwc4 (the header comment; gen = 0: none of it is read).  The fp32 instantiation's, stores in jdtype.
+    int gen;
+    const long long* table;                                       // [n_frames] device addresses (0 = empty), or null: src + f * frame_stride
+    int dsc[4];                                                   // LH_FRAMES_420 / 420W: c_pitch, cb_offset, cr_offset, c_step (with pitch, siting)
 };
 enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3 };
-enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2 };
+enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2, LH_JIT_STORE = 3 };      // STORE: no jitter, the store is jit.dtype's
 
 // What a jittered launch carries into the pixel loops: the slot's factors and order, then the grey mean (LH_JIT_APPLY) or the number
 // of ops in front of contrast (LH_JIT_MEAN).
@@ -205,6 +222,61 @@ __device__ __forceinline__ bool crop_sample_nv12(const CropArgs& p, const float*
     return true;
 }
 
+// The descriptor's sibling (LH_FRAMES_420 / 420W; the header comment): crop_sample_nv12's operations in its order, the texels through
+// the plane descriptor.  U = unsigned char: 8-bit samples; unsigned short: P010's.  Offsets are 32-bit (a frame is below 2^31 bytes).
+// csc[12..15] hold the bits of c_pitch, cb_offset, cr_offset, c_step: in VECTOR registers like the coefficients in front of them
+// (crop_slot) -- as scalars they are more than the kernel has, and the compiler spills scalars to scratch.
+template <typename U>
+__device__ __forceinline__ float crop_texel(const unsigned char* plane, int off) {
+    if constexpr (sizeof(U) == 2) return (float)(*reinterpret_cast<const unsigned short*>(plane + off) >> 6) * 0.25f;
+    else return (float)plane[off];
+}
+
+template <typename U>
+__device__ __forceinline__ bool crop_sample_420(const CropArgs& p, const float* csc, const unsigned char* base, float fx, float fy,
+                                                float s[3]) {
+    constexpr int SH = sizeof(U) == 2 ? 1 : 0;
+    const int hs = p.hs, ws = p.ws, pitch = p.pitch;
+    if (!(fx >= -0.5f && fx <= ws - 0.5f && fy >= -0.5f && fy <= hs - 0.5f)) return false;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    float yuv[3];
+    {
+        const int y0 = min((int)fy, hs - 1), x0 = min((int)fx, ws - 1);
+        const int y1 = y0 + 1 < hs ? y0 + 1 : hs - 1, x1 = x0 + 1 < ws ? x0 + 1 : ws - 1;
+        const float wy = fy - y0, wx = fx - x0;
+        const float a00 = crop_texel<U>(base, y0 * pitch + (x0 << SH)), a01 = crop_texel<U>(base, y0 * pitch + (x1 << SH));
+        const float a10 = crop_texel<U>(base, y1 * pitch + (x0 << SH)), a11 = crop_texel<U>(base, y1 * pitch + (x1 << SH));
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        yuv[0] = top + (bot - top) * wy;
+    }
+    const int hc = hs >> 1, wc = ws >> 1;
+    float gx = p.siting == 0 ? fx * 0.5f : (fx - 0.5f) * 0.5f, gy = (fy - 0.5f) * 0.5f;
+    gx = fminf(fmaxf(gx, 0.f), (float)(wc - 1));
+    gy = fminf(fmaxf(gy, 0.f), (float)(hc - 1));
+    const int y0 = min((int)gy, hc - 1), x0 = min((int)gx, wc - 1);
+    const int y1 = min(y0 + 1, hc - 1), x1 = min(x0 + 1, wc - 1);
+    const float wy = gy - y0, wx = gx - x0;
+    const int c_pitch = __float_as_int(csc[12]), c_step = __float_as_int(csc[15]);
+    const int o00 = y0 * c_pitch + x0 * c_step, o01 = y0 * c_pitch + x1 * c_step;
+    const int o10 = y1 * c_pitch + x0 * c_step, o11 = y1 * c_pitch + x1 * c_step;
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+        int plane = __float_as_int(csc[13 + ch]);                 // one scalar base and a 32-bit offset per load
+        // Cr's four offsets are formed once Cb is blended: with all eight chroma loads in flight beside luma's four the tap bodies
+        // take 75 vector registers and the kernel drops from 7 waves a SIMD to 6 (71 this way; EXPERIMENTS.md)
+        if (ch == 1) asm volatile("" : "+v"(plane) : "v"(yuv[1]));
+        const float a00 = crop_texel<U>(base, plane + o00), a01 = crop_texel<U>(base, plane + o01);
+        const float a10 = crop_texel<U>(base, plane + o10), a11 = crop_texel<U>(base, plane + o11);
+        const float top = a00 + (a01 - a00) * wx, bot = a10 + (a11 - a10) * wx;
+        yuv[1 + ch] = top + (bot - top) * wy;
+    }
+    const float e0 = yuv[0] - csc[9], e1 = yuv[1] - csc[10], e2 = yuv[2] - csc[11];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c] = fminf(fmaxf((csc[c * 3] * e0 + csc[c * 3 + 1] * e1) + csc[c * 3 + 2] * e2, 0.f), 255.f);
+    return true;
+}
+
 __device__ __forceinline__ int crop_taps(float a, float b, int max_taps) {
     const float s = sqrtf(a * a + b * b);
     return s > 1.015625f && isfinite(s) ? min(max_taps, (int)ceilf(fminf(s, 64.f))) : 1;
@@ -212,16 +284,18 @@ __device__ __forceinline__ int crop_taps(float a, float b, int max_taps) {
 
 // The pixels of one slot.  AREA = false is the plain crop, one sample at the pixel's centre: the loop the kernel always had, kept apart
 // from the tap loops so that it compiles to what it was.  AREA = true: a live slot, kx x ky samples over the pixel's footprint.
-// NV12 picks the sample function, nothing else: the walk, the tap offsets, the accumulation and the store are shared.
-template <bool NV12>
+// FMT (LH_FRAMES_*) picks the sample function, nothing else: the walk, the tap offsets, the accumulation and the store are shared.
+template <int FMT>
 __device__ __forceinline__ bool crop_sample_of(const CropArgs& p, const float* csc, const unsigned char* base, float fx, float fy, float s[3]) {
-    if constexpr (NV12) return crop_sample_nv12(p, csc, base, fx, fy, s);
+    if constexpr (FMT == LH_FRAMES_420) return crop_sample_420<unsigned char>(p, csc, base, fx, fy, s);
+    else if constexpr (FMT == LH_FRAMES_420W) return crop_sample_420<unsigned short>(p, csc, base, fx, fy, s);
+    else if constexpr (FMT == LH_FRAMES_NV12) return crop_sample_nv12(p, csc, base, fx, fy, s);
     else return crop_sample(base, p.hs, p.ws, fx, fy, s);
 }
 
 // JIT = LH_JIT_APPLY: ColorJitter between the sample and Normalize.  LH_JIT_MEAN: nothing is stored, the interior pixels' grey levels
 // (after the ops in front of contrast) are summed in the order of the walk: the return value (0 otherwise).
-template <typename T, bool AREA, bool NV12, int JIT = LH_JIT_NONE>
+template <typename T, bool AREA, int FMT, int JIT = LH_JIT_NONE>
 __device__ __forceinline__ double crop_pixels(const CropArgs& p, const unsigned char* base, bool live, T* dst, int first, int stride,
                                             int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky,
                                             bool tiled, const float* csc = nullptr, const CropJit jit = {}) {
@@ -248,7 +322,7 @@ __device__ __forceinline__ double crop_pixels(const CropArgs& p, const unsigned 
             float c[3] = {0.f, 0.f, 0.f};
             if constexpr (!AREA) {
                 float s[3];
-                if (live && crop_sample_of<NV12>(p, csc, base, (m0 * ox + m1 * oy) + m2, (m3 * ox + m4 * oy) + m5, s)) {   // NaN: black
+                if (live && crop_sample_of<FMT>(p, csc, base, (m0 * ox + m1 * oy) + m2, (m3 * ox + m4 * oy) + m5, s)) {   // NaN: black
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) c[ch] = s[ch] * (1.f / 255.f);
                 }
@@ -259,7 +333,7 @@ __device__ __forceinline__ double crop_pixels(const CropArgs& p, const unsigned 
                     for (int t = 0; t < kx; ++t) {
                         const float ux = (float)ox + (float)(2 * t + 1 - kx) / fkx2;
                         float s[3];
-                        if (crop_sample_of<NV12>(p, csc, base, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, s)) {
+                        if (crop_sample_of<FMT>(p, csc, base, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, s)) {
 #pragma unroll
                             for (int ch = 0; ch < 3; ++ch) acc[ch] += s[ch];
                         }
@@ -277,7 +351,7 @@ __device__ __forceinline__ double crop_pixels(const CropArgs& p, const unsigned 
             for (int ch = 0; ch < 3; ++ch) v[ch] = (c[ch] - p.mean[ch]) * p.istd[ch];
         }
         if constexpr (JIT == LH_JIT_MEAN) continue;
-        if constexpr (JIT == LH_JIT_APPLY) {                      // the fp32 instantiation stores for all three dtypes (uniform)
+        if constexpr (JIT == LH_JIT_APPLY || JIT == LH_JIT_STORE) {      // the fp32 instantiation stores for all three dtypes (uniform)
             if (jit.dtype == LH_BF16) crop_store((bf16*)dst, i, v);
             else if (jit.dtype == LH_F16) crop_store((f16*)dst, i, v);
             else crop_store((float*)dst, i, v);
@@ -359,25 +433,40 @@ __device__ __forceinline__ void crop_aux_modes(const CropArgs& p) {
     else affine_points_inv_point(i, p.in0, p.pstride, p.in1, p.iin, p.out0, p.ostride, p.j);
 }
 
-// One slot's pixels through the body its format and tap counts select; JIT as in crop_pixels.
+// One slot's pixels through the body its format (LH_FRAMES_*) and tap counts select; JIT as in crop_pixels.
 template <typename T, int JIT>
-__device__ __forceinline__ double crop_slot(const CropArgs& p, const unsigned char* base, bool live, bool nv12, T* dst, int first, int stride,
+__device__ __forceinline__ double crop_slot(const CropArgs& p, const unsigned char* base, bool live, int fmt, T* dst, int first, int stride,
                                           int per_slot, float m0, float m1, float m2, float m3, float m4, float m5, int kx, int ky, bool tiled,
                                           const CropJit jit) {
-    if (nv12) {
+    if (fmt != LH_FRAMES_RGB) {
         // the 12 coefficients live in vector registers: as scalars they take the kernel past 100 SGPRs, and the RGB entries, which never
         // read them, from 8 waves a SIMD to 7 (measured on the turned legs of tools/topdown_cost.py: EXPERIMENTS.md)
-        float csc[12];
+        float csc[sizeof(T) == 4 ? 16 : 12];
 #pragma unroll
         for (int c = 0; c < 12; ++c) {
             csc[c] = c < 9 ? p.k[c] : p.o[c - 9];
             asm volatile("" : "+v"(csc[c]));
         }
-        if (kx * ky == 1) return crop_pixels<T, false, true, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc, jit);
-        return crop_pixels<T, true, true, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc, jit);
+        if constexpr (sizeof(T) == 4) {                           // the plane descriptor: the fp32 instantiation's alone
+            if (fmt >= LH_FRAMES_420) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    csc[12 + c] = __int_as_float(p.dsc[c]);
+                    asm volatile("" : "+v"(csc[12 + c]));
+                }
+                if (fmt == LH_FRAMES_420) {
+                    if (kx * ky == 1) return crop_pixels<T, false, LH_FRAMES_420, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc, jit);
+                    return crop_pixels<T, true, LH_FRAMES_420, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc, jit);
+                }
+                if (kx * ky == 1) return crop_pixels<T, false, LH_FRAMES_420W, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc, jit);
+                return crop_pixels<T, true, LH_FRAMES_420W, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc, jit);
+            }
+        }
+        if (kx * ky == 1) return crop_pixels<T, false, LH_FRAMES_NV12, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, csc, jit);
+        return crop_pixels<T, true, LH_FRAMES_NV12, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, csc, jit);
     }
-    if (kx * ky == 1) return crop_pixels<T, false, false, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, nullptr, jit);
-    return crop_pixels<T, true, false, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, nullptr, jit);
+    if (kx * ky == 1) return crop_pixels<T, false, LH_FRAMES_RGB, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, 1, 1, false, nullptr, jit);
+    return crop_pixels<T, true, LH_FRAMES_RGB, JIT>(p, base, live, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, nullptr, jit);
 }
 
 template <typename T>
@@ -392,9 +481,22 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     const float* m = p.mat + slot * 6;
     const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
     const int sf = p.src_frame[slot];
-    const bool live = sf >= 0 && sf < p.n_frames;                 // anything else is an empty slot: never an address
+    bool live = sf >= 0 && sf < p.n_frames;                       // anything else is an empty slot: never an address
     const bool nv12 = p.format == LH_FRAMES_NV12;                 // workgroup-uniform: one branch in front of the pixel loops
+    int fmt = nv12 ? LH_FRAMES_NV12 : LH_FRAMES_RGB;
     const unsigned char* base = p.src + (nv12 ? (long)(live ? sf : 0) * p.frame_stride : (long)(live ? sf : 0) * p.hs * p.ws * 3);
+    if constexpr (sizeof(T) == 4) {
+        if (p.gen) {                                              // the surfaces entry: where the frame is, and which sample reads it
+            fmt = p.format;
+            if (p.table) {
+                const long long at = live ? p.table[sf] : 0;      // a scalar load; tested before it becomes an address
+                live = live && at != 0;
+                base = reinterpret_cast<const unsigned char*>(live ? at : 0);
+            } else {
+                base = p.src + (long)(live ? sf : 0) * p.frame_stride;
+            }
+        }
+    }
     const int per_slot = p.hp * p.wp;
     T* dst = (T*)p.dst + (long)slot * per_slot * 4;
     int kx = 1, ky = 1;                                           // workgroup-uniform; the plain entry never pays for the square roots
@@ -414,7 +516,7 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
                 if (threadIdx.x == 0) p.jpartial[slot * CJ_STRIPS + blockIdx.x] = 0.0;
                 return;
             }
-            red[threadIdx.x] = crop_slot<T, LH_JIT_MEAN>(p, base, live, nv12, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
+            red[threadIdx.x] = crop_slot<T, LH_JIT_MEAN>(p, base, live, fmt, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
             __syncthreads();
             for (int o = 128; o > 0; o >>= 1) {
                 if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
@@ -428,11 +530,17 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
             for (int k = 0; k < CJ_STRIPS; ++k) sum += p.jpartial[slot * CJ_STRIPS + k];
             const CropJit jit = {p.jfactors + slot * 4, p.jorder + slot * 4, (float)(sum / ((double)p.h * p.w)), 4, p.jdtype};
             T* out = (T*)((char*)p.dst + (long)slot * per_slot * (p.jdtype == LH_F32 ? 16 : 8));      // the slot's pixels in dst's dtype
-            crop_slot<T, LH_JIT_APPLY>(p, base, live, nv12, out, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
+            crop_slot<T, LH_JIT_APPLY>(p, base, live, fmt, out, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
+            return;
+        }
+        if (p.gen) {                                              // the surfaces entry without ColorJitter: this instantiation stores in jdtype
+            const CropJit jit = {nullptr, nullptr, 0.f, 4, p.jdtype};
+            T* out = (T*)((char*)p.dst + (long)slot * per_slot * (p.jdtype == LH_F32 ? 16 : 8));
+            crop_slot<T, LH_JIT_STORE>(p, base, live, fmt, out, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, jit);
             return;
         }
     }
-    crop_slot<T, LH_JIT_NONE>(p, base, live, nv12, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, CropJit{});
+    crop_slot<T, LH_JIT_NONE>(p, base, live, fmt, dst, first, stride, per_slot, m0, m1, m2, m3, m4, m5, kx, ky, tiled, CropJit{});
 }
 
 // What the NV12 entry adds to the RGB ones' arguments.
@@ -470,6 +578,7 @@ static int frames_crop_launch(const char* who, const unsigned char* frames_u8, v
     a.op = LH_CROP; a.n = a.j = a.pstride = a.ostride = 0;
     a.in0 = a.in1 = a.in2 = nullptr; a.iin = nullptr; a.out0 = a.out1 = nullptr; a.iout = nullptr;
     a.jfactors = nullptr; a.jorder = nullptr; a.jpartial = nullptr; a.jdtype = dtype;
+    a.gen = 0; a.table = nullptr; a.dsc[0] = a.dsc[1] = a.dsc[2] = a.dsc[3] = 0;
     a.format = yuv ? LH_FRAMES_NV12 : LH_FRAMES_RGB;
     a.pitch = a.uv_offset = a.siting = 0; a.frame_stride = 0;
     for (int c = 0; c < 9; ++c) a.k[c] = 0.f;
@@ -544,6 +653,89 @@ extern "C" int lh_frames_crop_jitter_to_nhwc4(const unsigned char* frames, void*
     const CropJitter jitter = {factors_dev, order_dev, workspace};
     return frames_crop_launch("lh_frames_crop_jitter_to_nhwc4", frames, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev,
                               src_frame_dev, max_taps, dtype, stream, csc12 ? &yuv : nullptr, &jitter);
+}
+
+// ------------------------------------------------------------------------------------------------ decoder surfaces, 4:2:0 flavours
+// The entry of the surface table and the plane descriptor (the header comment).  Every launch is the fp32 instantiation's, which
+// stores in ``dtype``.  All of the layout is checked here, in front of any launch: the kernel trusts it.
+extern "C" int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, void* out, long frame_stride, const long long* surface_table_dev,
+                                                const lh_frames_layout* layout, int b, int n_frames, int hs, int ws, int h, int w,
+                                                int pad, int wp, const float* mean3, const float* std3, const float* mat_dev,
+                                                const int* src_frame_dev, int max_taps, const float* factors_dev, const int* order_dev,
+                                                void* workspace, int dtype, void* stream) {
+    const char* who = "lh_frames_crop_surfaces_to_nhwc4";
+    LH_REQUIRE(frames || surface_table_dev, "%s: no frame source (frames and surface_table_dev are both null)", who);
+    LH_REQUIRE(!(frames && surface_table_dev), "%s: two frame sources (pass frames or surface_table_dev, not both)", who);
+    LH_REQUIRE(layout && out && mean3 && std3 && mat_dev && src_frame_dev && b > 0 && b <= 65535 && n_frames > 0 && hs > 0 && ws > 0 && h > 0
+               && w > 0 && pad >= 0 && wp >= w + 2 * pad, "%s: bad arguments", who);
+    const bool jitter = factors_dev || order_dev || workspace;
+    LH_REQUIRE(!jitter || (factors_dev && order_dev && workspace), "%s: bad arguments (factors_dev, order_dev or workspace is null)", who);
+    LH_REQUIRE(!jitter || ((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+    LH_REQUIRE(max_taps >= 1 && max_taps <= 8, "%s: max_taps must be 1..8, not %d", who, max_taps);
+    LH_REQUIRE(lh_dtype_size(dtype) > 0, "%s: unsupported dtype %d", who, dtype);
+    LH_REQUIRE(((uintptr_t)out & 7) == 0, "%s: out must be 8-byte aligned", who);
+    LH_REQUIRE(!surface_table_dev || ((uintptr_t)surface_table_dev & 7) == 0, "%s: surface_table_dev must be 8-byte aligned", who);
+    LH_REQUIRE((long)(h + 2 * pad) * wp < (1L << 29), "%s: crop too large for 32-bit pixel indices", who);
+    const int f = layout->format;
+    LH_REQUIRE(f >= LH_FRAMES_FMT_RGB && f <= LH_FRAMES_FMT_P010, "%s: unknown format code %d", who, f);
+    CropArgs a = {};
+    a.src = frames; a.table = surface_table_dev; a.gen = 1;
+    a.dst = out; a.mat = mat_dev; a.src_frame = src_frame_dev;
+    a.n_frames = n_frames; a.hs = hs; a.ws = ws; a.h = h; a.w = w; a.pad = pad; a.hp = h + 2 * pad; a.wp = wp;
+    a.max_taps = max_taps; a.op = LH_CROP; a.jdtype = dtype;
+    long need;                                                    // the highest byte a sample can touch, plus one
+    if (f == LH_FRAMES_FMT_RGB) {
+        need = (long)hs * ws * 3;
+        a.format = LH_FRAMES_RGB;
+    } else {
+        const int sb = f == LH_FRAMES_FMT_P010 ? 2 : 1, hc = hs / 2, wc = ws / 2;
+        const long pitch = layout->pitch, c_pitch = layout->c_pitch, cb = layout->cb_offset, cr = layout->cr_offset;
+        LH_REQUIRE(hs >= 2 && ws >= 2 && hs % 2 == 0 && ws % 2 == 0, "%s: 4:2:0 frames have even sides >= 2, not %d x %d", who, hs, ws);
+        LH_REQUIRE(pitch >= (long)ws * sb, "%s: pitch %ld is below a luma row's %ld bytes", who, pitch, (long)ws * sb);
+        const bool planar = f == LH_FRAMES_FMT_YUV420P;
+        const long c_row = planar ? wc : (long)wc * 2 * sb;       // the bytes of one chroma row that are samples
+        LH_REQUIRE(c_pitch >= c_row, "%s: c_pitch %ld is below a chroma row's %ld bytes", who, c_pitch, c_row);
+        LH_REQUIRE(f != LH_FRAMES_FMT_NV12 || cr == cb + 1, "%s: nv12 has cr_offset = cb_offset + 1, not %ld / %ld", who, cb, cr);
+        LH_REQUIRE(f != LH_FRAMES_FMT_NV21 || cb == cr + 1, "%s: nv21 has cb_offset = cr_offset + 1, not %ld / %ld", who, cb, cr);
+        LH_REQUIRE(f != LH_FRAMES_FMT_P010 || cr == cb + 2, "%s: p010 has cr_offset = cb_offset + 2, not %ld / %ld", who, cb, cr);
+        LH_REQUIRE(sb == 1 || (pitch % 2 == 0 && c_pitch % 2 == 0 && cb % 2 == 0 && cr % 2 == 0),
+                   "%s: p010 samples are 16-bit: pitch %ld, c_pitch %ld, cb_offset %ld and cr_offset %ld must be even", who, pitch, c_pitch, cb, cr);
+        const long luma_end = (long)(hs - 1) * pitch + (long)ws * sb;
+        const long c_lo = cb < cr ? cb : cr, c_hi = cb < cr ? cr : cb;
+        LH_REQUIRE(c_lo >= luma_end, "%s: a chroma plane (cb_offset %ld, cr_offset %ld) lies inside the luma plane (%ld bytes)", who, cb, cr,
+                   luma_end);
+        const long plane = (long)(hc - 1) * c_pitch + (planar ? wc : (long)(wc - 1) * 2 * sb + sb);      // one plane's extent from its offset
+        LH_REQUIRE(!planar || c_hi >= c_lo + plane, "%s: the chroma planes overlap (cb_offset %ld, cr_offset %ld, %ld bytes each)", who, cb, cr,
+                   plane);
+        need = c_hi + plane;
+        LH_REQUIRE(layout->frame_bytes >= need && need < (1L << 31), "%s: the planes end at byte %ld, outside frame_bytes %d (< 2^31)", who, need,
+                   layout->frame_bytes);
+        LH_REQUIRE(layout->chroma_siting == 0 || layout->chroma_siting == 1, "%s: chroma_siting must be 0 (left) or 1 (center), not %d", who,
+                   layout->chroma_siting);
+        for (int c = 0; c < 12; ++c) LH_REQUIRE(layout->csc12[c] - layout->csc12[c] == 0.f, "%s: csc12[%d] is not finite", who, c);
+        a.format = sb == 2 ? LH_FRAMES_420W : LH_FRAMES_420;
+        a.pitch = (int)pitch; a.siting = layout->chroma_siting;
+        a.dsc[0] = (int)c_pitch; a.dsc[1] = (int)cb; a.dsc[2] = (int)cr; a.dsc[3] = planar ? 1 : 2 * sb;
+        for (int c = 0; c < 9; ++c) a.k[c] = layout->csc12[c];
+        for (int c = 0; c < 3; ++c) a.o[c] = layout->csc12[9 + c];
+        LH_REQUIRE(sb == 1 || !frames || (((uintptr_t)frames | (uintptr_t)frame_stride) & 1) == 0,
+                   "%s: p010 samples are 16-bit: frames and frame_stride must be even", who);
+    }
+    LH_REQUIRE(need < (1L << 31), "%s: a frame of %ld bytes does not fit 32-bit byte indices", who, need);
+    LH_REQUIRE(!frames || frame_stride >= need, "%s: frame_stride %ld is below the %ld bytes a frame's samples span", who, frame_stride, need);
+    a.frame_stride = frames ? frame_stride : 0;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.istd[c] = 1.f / std3[c]; }
+    const int chunks = lh_grid((long)a.hp * wp, 1024);
+    if (jitter) {
+        a.jfactors = factors_dev; a.jorder = order_dev; a.jpartial = (double*)workspace;
+        a.op = LH_CROP_GREY_MEAN;
+        hipLaunchKernelGGL((frames_crop_kernel<float>), dim3(CJ_STRIPS, b), dim3(256), 0, (hipStream_t)stream, a);
+        LH_LAUNCH_CHECK("frames_crop_surfaces_to_nhwc4 grey-mean launch");
+        a.op = LH_CROP;
+    }
+    hipLaunchKernelGGL((frames_crop_kernel<float>), dim3(chunks, b), dim3(256), 0, (hipStream_t)stream, a);
+    LH_LAUNCH_CHECK("frames_crop_surfaces_to_nhwc4 launch");
+    return LH_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ training on frames: the two modes

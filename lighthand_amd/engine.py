@@ -949,7 +949,7 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
 
     def use_frame_input(self, n_frames, hs, ws, padding=1.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), oriented=False,
                         max_taps=1, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, perturb=False,
-                        jitter=False):
+                        jitter=False, surfaces=False):
         """Switch the plan's input to hand boxes on full camera frames (top-down inference; the sibling of ``use_uint8_input``): the
         plan owns ``frames_u8`` (uint8 [n_frames][hs][ws][3], shared by all n slots), ``boxes`` (fp32 [n][4] = x0 y0 x1 y1 in frame
         pixel-index coordinates, the whole frame until the caller writes them) and ``frame_index`` (int32 [n], arange % n_frames),
@@ -972,13 +972,30 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         frames with ColorJitter): the plan also owns ``jitter_factors`` (fp32 [n][4]) and ``jitter_order`` (int32 [n][4], identity
         factors and order -1 until the caller draws: ``runtime.sample_color_jitter``), as ``use_uint8_input(jitter=True)`` does, and
         the image launch is lh_frames_crop_jitter_to_nhwc4 for every ``frame_format`` and ``max_taps``: the grey-mean launch and the
-        crop, one entry.  False: launches, buffers and bits as above.  Returns the frame buffer."""
+        crop, one entry.  False: launches, buffers and bits as above.  ``frame_format`` "nv21" / "yuv420p" / "p010" (or "nv12" with
+        a topdown.Yuv420Layout), and ``surfaces=True`` for every format: the image launch is lh_frames_crop_surfaces_to_nhwc4 (with
+        ``jitter`` its two launches), which finds a sample through the plane descriptor ``frame_layout`` (topdown.frame_layout_of's
+        rules; kept as ``self.frame_layout``).  Without ``surfaces`` ``frames_u8`` is uint8 [n_frames][frame_bytes]; with it the plan
+        owns no frame buffer (``frames_u8`` is None) but ``surface_table`` (int64 [n_frames], zeros: every frame unbound), the device
+        addresses of the frames, read by the launch at every replay.  Returns the frame buffer (None with ``surfaces``)."""
         from . import topdown
         if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
             raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
-        if frame_format not in ("rgb", "nv12"):
-            raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
-        if frame_format == "nv12":
+        topdown.check_frame_format(frame_format)
+        self.surface_table = self.frame_layout = None
+        descriptor = bool(surfaces) or frame_format not in ("rgb", "nv12") or isinstance(frame_layout, topdown.Yuv420Layout)
+        if descriptor:
+            self.frame_layout = topdown.frame_layout_of(frame_format, hs, ws, frame_layout)
+            desc = topdown._frames_layout_struct(self.frame_layout, yuv, chroma_siting)
+            self.keep.append(desc)
+            if surfaces:
+                self.frames_u8 = None
+                self.surface_table = self._alloc(n_frames, dtype=torch.int64, zero=True)
+                source = (None, 0, self.surface_table.data_ptr())          # (frames, frame_stride, table)
+            else:
+                self.frames_u8 = self._alloc(n_frames, self.frame_layout.frame_bytes, dtype=torch.uint8, zero=True)
+                source = (self.frames_u8.data_ptr(), self.frame_layout.frame_bytes, None)
+        elif frame_format == "nv12":
             pitch, uv_offset, frame_stride, rows = topdown._check_layout(hs, ws, frame_layout)
             csc, siting = (C.c_float * 12)(*topdown._csc12(yuv).tolist()), topdown.chroma_siting_code(chroma_siting)
             self.keep.append(csc)
@@ -1002,6 +1019,14 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             self.jitter_order = torch.full((self.n, 4), -1, dtype=torch.int32, device=self.device)
             ws_j = self._alloc(self.lib.lh_frames_crop_jitter_workspace_bytes(self.n), dtype=torch.uint8)
             self.keep.append(self.jitter_order)
+        if descriptor:
+            jit = (self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr()) if jitter else (None, None, None)
+            self.fwd[i] = _Call(self.lib.lh_frames_crop_surfaces_to_nhwc4, (source[0], self.img_nhwc4.data_ptr()) + source[1:] + (
+                C.byref(desc), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3, s3,
+                self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps) + jit + (self.dt,),
+                f"{frame_format} frame crop input pipeline" + (", surface table" if surfaces else "")
+                + (", antialiased" if max_taps > 1 else "") + (" + ColorJitter" if jitter else ""))
+        elif jitter:
             nv12 = (pitch, uv_offset, frame_stride, siting, csc) if frame_format == "nv12" else (0, 0, 0, 0, None)
             self.fwd[i] = _Call(self.lib.lh_frames_crop_jitter_to_nhwc4, (
                 self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws) + nv12 + (

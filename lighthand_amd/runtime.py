@@ -115,16 +115,19 @@ def _is_frame_default(key, value):
 
 
 def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, min_side, antialias=False, frame_format="rgb",
-                  yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
-    """InferStep / InferPipeline(frames=, box_padding=, track*=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=): refuse
-    what cannot run, before any device work.  Returns the (n_frames, hs, ws) tuple of ints, or None."""
+                  yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, surfaces=False):
+    """InferStep / InferPipeline(frames=, box_padding=, track*=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=,
+    surfaces=): refuse what cannot run, before any device work.  Returns the (n_frames, hs, ws) tuple of ints, or None."""
     taps = _antialias_taps(antialias)
     given = dict(frame_format=frame_format, yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout)
-    if not isinstance(frame_format, str) or frame_format not in ("rgb", "nv12"):
-        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
+    topdown.check_frame_format(frame_format)
     topdown._csc12(yuv)
     topdown.chroma_siting_code(chroma_siting)
+    if not isinstance(surfaces, bool):
+        raise ValueError(f"surfaces must be False or True, not {surfaces!r}")
     if frames is None:
+        if surfaces:
+            raise ValueError("surfaces=True reads full frames in place: pass frames=(n_frames, hs, ws)")
         for key, value in given.items():
             if not _is_frame_default(key, value):
                 raise ValueError(f"{key}={value!r} describes full frames: pass frames=(n_frames, hs, ws)")
@@ -141,12 +144,12 @@ def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, m
         raise ValueError(f"frames must be (n_frames, hs, ws), three positive integers, not {frames!r}")
     if not _is_number(box_padding) or box_padding <= 0:
         raise ValueError(f"box_padding must be a finite number > 0, not {box_padding!r}")
-    if frame_format == "nv12":
-        topdown._check_layout(int(frames[1]), int(frames[2]), frame_layout)
+    if frame_format != "rgb":
+        topdown.frame_layout_of(frame_format, int(frames[1]), int(frames[2]), frame_layout)
     else:
         for key in ("yuv", "chroma_siting", "frame_layout"):
             if not _is_frame_default(key, given[key]):
-                raise ValueError(f"{key}={given[key]!r} describes NV12 frames: pass frame_format='nv12'")
+                raise ValueError(f"{key}={given[key]!r} describes NV12 frames: pass frame_format='nv12' (or 'nv21' / 'yuv420p' / 'p010')")
     if track:
         if not _is_number(min_score):
             raise ValueError(f"track_min_score must be a finite number, not {min_score!r}")
@@ -155,6 +158,59 @@ def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, m
         if not _is_number(min_side) or min_side < 0:
             raise ValueError(f"track_min_side must be a finite number >= 0, not {min_side!r}")
     return tuple(int(v) for v in frames)
+
+
+class _SurfaceBinding:
+    """bind_surfaces / unbind_surfaces of a step built with ``frames=..., surfaces=True``: the step owns no frame buffer but
+    ``plan.surface_table`` (int64 [n_frames] on the device), the addresses of the frames, which its crop launch reads at every
+    replay -- so the surfaces change between replays of one captured graph with no recapture."""
+
+    surfaces = False
+    _surface_refs = None
+
+    def _own_surfaces(self, n_frames):
+        self.surfaces = True
+        self._surface_refs = [None] * n_frames                     # a bound tensor lives until its entry is rebound or cleared
+
+    def bind_surfaces(self, surfaces, start=0):
+        """Frame ``start + i`` <- ``surfaces[i]``: a sequence of CUDA uint8 tensors, or one tensor [k][...] bound row by row.  Each is
+        checked on the host (topdown.check_surface: on the step's device, uint8, contiguous, at least topdown.surface_bytes(layout)
+        bytes, 2-byte aligned for 16-bit samples); any violation raises ValueError and writes nothing.  The addresses reach the table
+        with one stream-ordered copy on the current stream.  A surface may be overwritten or freed only after that stream has passed
+        the replay that reads it; the step holds a reference until the entry is rebound or cleared.  A tensor of more than one
+        dimension is always k surfaces, one per row: ONE surface shaped [rows][pitch] goes in as ``[surface]`` (or flattened)."""
+        if not self.surfaces:
+            raise ValueError("surfaces are the input of a step built with frames=(n_frames, hs, ws), surfaces=True")
+        table = self.plan.surface_table
+        rows = torch.is_tensor(surfaces) and surfaces.dim() > 1
+        seq = list(surfaces.unbind(0)) if rows else [surfaces] if torch.is_tensor(surfaces) else list(surfaces)
+        if isinstance(start, bool) or not isinstance(start, numbers.Integral) or start < 0 or not seq or start + len(seq) > table.shape[0]:
+            raise ValueError(f"bind_surfaces: {len(seq)} surfaces from frame {start!r} on do not fit the step's {table.shape[0]} frames"
+                             + (f" (a tensor {tuple(surfaces.shape)} is bound row by row: pass one surface as [surface])" if rows else ""))
+        try:
+            addresses = [topdown.check_surface(t, table.device, self.plan.frame_layout) for t in seq]
+        except ValueError as e:
+            if rows:                                                # name the likely cause: one surface taken for k rows
+                raise ValueError(f"{e} (a tensor {tuple(surfaces.shape)} is bound row by row, {len(seq)} surfaces of "
+                                 f"{seq[0].numel()} bytes: pass one surface as [surface])") from None
+            raise
+        table[start:start + len(seq)].copy_(torch.tensor(addresses, dtype=torch.int64), non_blocking=True)      # from pageable memory
+        self._surface_refs[start:start + len(seq)] = seq
+
+    def unbind_surfaces(self, indices=None):
+        """Zero the table entries of ``indices`` (None: all) and drop the references: such a frame is empty, its slots crop black."""
+        if not self.surfaces:
+            raise ValueError("surfaces are the input of a step built with frames=(n_frames, hs, ws), surfaces=True")
+        table = self.plan.surface_table
+        if indices is None:
+            indices = range(table.shape[0])
+        indices = [int(i) for i in indices]
+        if any(i < 0 or i >= table.shape[0] for i in indices):
+            raise ValueError(f"unbind_surfaces: indices within 0..{table.shape[0] - 1}, not {indices!r}")
+        if indices:
+            table[torch.tensor(indices, dtype=torch.int64).to(table.device)] = 0
+        for i in indices:
+            self._surface_refs[i] = None
 
 
 def _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth):
@@ -236,12 +292,13 @@ def _roi_aug_spec(roi_aug):
 
 def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_jitter=None, targets_from_joints=True, box_padding=1.25,
                         oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left",
-                        frame_layout=None, roi_aug=None, coord_loss_weight=0.0, use_target_weight=False, crop_jitter=None):
+                        frame_layout=None, roi_aug=None, coord_loss_weight=0.0, use_target_weight=False, crop_jitter=None, surfaces=False):
     """TrainStep(frames=, box_padding=, oriented=, antialias=, frame_format=, yuv=, chroma_siting=, frame_layout=, roi_aug=,
     crop_jitter=): refuse what cannot run, before any device work (no device is touched here).  The options shared with InferStep
     follow _check_frames' / _check_roi's rules.  Returns (frames as a tuple of ints or None, the roi_aug spec or None), and with the
     ``crop_jitter`` keyword a third value: the validated (brightness, contrast, saturation, hue) tuple of floats, or None."""
-    checked = _check_frames(frames, input_u8, box_padding, False, 0.0, 1, 0.0, antialias, frame_format, yuv, chroma_siting, frame_layout)
+    checked = _check_frames(frames, input_u8, box_padding, False, 0.0, 1, 0.0, antialias, frame_format, yuv, chroma_siting, frame_layout,
+                            surfaces)
     _check_roi(model, checked, oriented, (0, 1), 1.0, None)
     if checked is None:
         if roi_aug is not None:
@@ -271,13 +328,13 @@ def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_
     return checked, spec, tuple(float(v) for v in crop_jitter)
 
 
-class TrainStep:
+class TrainStep(_SurfaceBinding):
     def __init__(self, model, batch, height, width, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  optimizer=None, decode=True, use_graph=True, grad_sync=None, targets_from_joints=True,
                  input_u8=None, color_jitter=None, loss_scale=None, geometric_aug=None, plan_options=None,
                  use_target_weight=False, ohkm_topk=0, target_encoding="quantised", coord_loss_weight=0.0, soft_argmax_beta=100.0,
                  frames=None, box_padding=1.25, oriented=False, antialias=False, frame_format="rgb", yuv=("bt709", "limited"),
-                 chroma_siting="left", frame_layout=None, roi_aug=None, crop_jitter=None):
+                 chroma_siting="left", frame_layout=None, roi_aug=None, crop_jitter=None, surfaces=False):
         """``coord_loss_weight`` = L > 0 (opt-in, integral regression; 0 = the step as it was: the same launches and buffers) adds
         L * mean |soft-arg-max(beta * heat-map) * 4 - joint| to the loss and its gradient to ``plan.dout_nchw`` (lh_integral_l1 right
         behind the MSE kernel, on the joints the target was rendered from, weighted by ``target_weight`` under ``use_target_weight``,
@@ -301,12 +358,15 @@ class TrainStep:
         ``color_jitter``: every call draws factors and an op order per slot (sample_color_jitter, ``aug`` as on the uint8 path) into
         ``plan.jitter_factors`` / ``plan.jitter_order`` and lh_frames_crop_jitter_to_nhwc4 applies them to the crop between the sample
         and Normalize; contrast blends with the grey mean of the slot's own crop, black outside the frame included.  None: the
-        launches and buffers without it."""
+        launches and buffers without it.
+        ``frame_format`` "nv21" / "yuv420p" / "p010" and ``surfaces=True`` (``bind_surfaces`` / ``unbind_surfaces`` /
+        ``step(surfaces=seq, ...)``; ``step.frames`` is then None): as InferStep's, with every option above; the crop launch is
+        lh_frames_crop_surfaces_to_nhwc4, under ``crop_jitter`` with its grey-mean launch in front."""
         if not _is_number(coord_loss_weight) or coord_loss_weight < 0:
             raise ValueError(f"coord_loss_weight must be a finite number >= 0, not {coord_loss_weight!r}")
         checked = _check_train_frames(model, frames, input_u8, geometric_aug, color_jitter, targets_from_joints, box_padding, oriented,
                                       antialias, frame_format, yuv, chroma_siting, frame_layout, roi_aug, coord_loss_weight,
-                                      use_target_weight, crop_jitter)
+                                      use_target_weight, crop_jitter, surfaces)
         frames, roi_aug = checked[:2]
         crop_jitter = checked[2] if crop_jitter is not None else None
         self.lib = _lib.load()
@@ -365,6 +425,12 @@ class TrainStep:
             self.images = None                                         # the inputs of such a step are frames / boxes / frame_index
             self.oriented = bool(oriented) or roi_aug is not None      # a turned ROI needs the oriented launch
             extra = dict(frame_format="nv12", yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout) if frame_format == "nv12" else {}
+            if surfaces or frame_format not in ("rgb", "nv12"):
+                extra = dict(frame_format=frame_format, frame_layout=frame_layout, surfaces=surfaces)
+                if frame_format != "rgb":
+                    extra.update(yuv=yuv, chroma_siting=chroma_siting)
+                if surfaces:
+                    self._own_surfaces(frames[0])
             self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
                                                     perturb=roi_aug is not None, **extra, **(dict(jitter=True) if crop_jitter else {}))
             self.boxes, self.frame_index = self.plan.boxes, self.plan.frame_index
@@ -467,7 +533,7 @@ class TrainStep:
     def _fwd_loss(self, stream):
         # the target only depends on the joints: it is rendered on the weight-pack side stream, under the stem
         # (on frames the joints go through the crop matrix, which the forward list writes: the render follows it on the main stream)
-        side = self._render_target if self.targets_from_joints and self.frames is None else None
+        side = self._render_target if self.targets_from_joints and self.frame_format is None else None
         rendered = self.plan.refresh_packs(stream, overlap=True, side_work=side)
         self.plan.run_forward(stream)
         self._fwd_loss_tail(stream, target_done=rendered)
@@ -603,10 +669,12 @@ class TrainStep:
 
     @property
     def valid(self):
-        """bool [batch]: the slots whose ROI and frame index were usable in the last run (None without ``frames``)."""
-        return None if self.frames is None else self.plan.src_frame >= 0
+        """bool [batch]: the slots whose ROI and frame index were usable in the last run (None without ``frames``).  Under
+        ``surfaces=True`` it does not say whether the frame's surface was bound: that is the caller's matter."""
+        return None if self.frame_format is None else self.plan.src_frame >= 0
 
-    def __call__(self, images=None, joints=None, target=None, aug=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None):
+    def __call__(self, images=None, joints=None, target=None, aug=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None,
+                 surfaces=None):
         """``joints``: [batch, J, >=2]; under ``use_target_weight`` a third column is the visibility (two columns = all visible).
         A step built with ``frames=`` takes ``frames`` / ``boxes`` / ``frame_index`` (and ``rot`` / ``mirror`` under ``oriented`` or
         ``roi_aug``) in place of ``images``, copied into the static buffers as InferStep does; its ``joints`` are frame coordinates.
@@ -615,13 +683,18 @@ class TrainStep:
         if getattr(self.model, "_lh_generation", 0) != self._model_generation:
             raise LightHandError("the model's parameter storages were re-created (.to() / .cuda() / .float()) after this TrainStep "
                                  "was built: its graph still trains the old buffers -- build a new TrainStep")
-        if self.frames is None:
-            if frames is not None or boxes is not None or frame_index is not None or rot is not None or mirror is not None:
+        if self.frame_format is None:
+            if (frames is not None or boxes is not None or frame_index is not None or rot is not None or mirror is not None
+                    or surfaces is not None):
                 raise ValueError("frames / boxes / frame_index / rot / mirror are the inputs of TrainStep(frames=(n_frames, hs, ws))")
         elif images is not None or target is not None:
             raise ValueError("a step built with frames= takes frames / boxes / frame_index and joints, not images or target")
         elif (rot is not None or mirror is not None) and not self.oriented:
             raise ValueError("rot / mirror are the inputs of TrainStep(frames=..., oriented=True) or roi_aug=")
+        if self.surfaces and frames is not None:
+            raise ValueError("a step built with surfaces=True owns no frame buffer: pass surfaces= (or bind_surfaces), not frames=")
+        if surfaces is not None:
+            self.bind_surfaces(surfaces)                            # refuses a step built without surfaces=True
         if self.graphs is not None:
             self.sync_hyper()
         for dst, src in ((self.frames, frames), (self.boxes, boxes), (self.frame_index, frame_index), (self.rot, rot), (self.mirror, mirror)):
@@ -675,7 +748,7 @@ class TrainStep:
         return self.loss
 
 
-class InferStep:
+class InferStep(_SurfaceBinding):
     """Eval-mode forward + arg-max decode as one captured graph (wearable_eval_2d / pred_store path,
     src/utils/argparser.py:246-281).  ``bn_train=True`` reproduces the reference quirk of running
     ``pred_store`` without ``model.eval()`` (batch statistics at evaluation time).
@@ -733,7 +806,18 @@ class InferStep:
     "bt709", "limited" / "full"; or 12 coefficients: topdown.yuv_matrix) picks the conversion, ``chroma_siting`` "left" (H.264 / HEVC)
     or "center" (JPEG / MPEG-1) where the chroma samples sit.  hs and ws must be even.  topdown.frames_crop_nv12_host states the
     rule; the matrix and everything after the crop are untouched, so it composes with every option above.  ``step.frame_format``
-    keeps the choice; "rgb" is the step as it was."""
+    keeps the choice; "rgb" is the step as it was.
+    ``frame_format`` "nv21" (Android camera stacks), "yuv420p" (software decoders: three planes) and "p010" (10-bit HEVC / AV1:
+    16-bit little-endian samples, the 10 data bits on top): ``frames`` is uint8 [n_frames][frame_bytes] in ``frame_layout`` =
+    topdown.yuv420_layout(frame_format, hs, ws, pitch, luma_rows, chroma_pitch) (None: tight), and the crop launch is
+    lh_frames_crop_surfaces_to_nhwc4, which finds every sample through that plane descriptor and then follows the NV12 rule
+    (topdown.frames_crop_yuv420_host); for p010 ``yuv=(standard, range)`` means topdown.yuv_matrix(standard, range, bits=10).
+    ``surfaces=True``, on top of ``frames=`` and for every ``frame_format``: the step owns no frame buffer (``step.frames`` is None)
+    but ``plan.surface_table``, the device addresses of the frames, which the crop launch reads at every replay: a decoder's
+    surfaces are cropped where they lie, with no copy.  ``bind_surfaces(tensors, start=0)`` / ``unbind_surfaces(indices=None)`` fill
+    and clear it, ``step(surfaces=seq, ...)`` binds and replays; the captured graph stays the same.  An unbound frame is empty: its
+    slots crop exactly black (``valid`` keeps meaning ``src_frame >= 0``: whether a surface is bound is the caller's matter).  A
+    surface may be overwritten or freed only after the step's stream has passed the replay that reads it."""
 
     _serial = 0
 
@@ -741,13 +825,13 @@ class InferStep:
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
                  frames=None, box_padding=1.25, track=False, track_min_score=0.1, track_min_joints=8, track_min_side=16.0,
                  oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None, antialias=False, frame_format="rgb",
-                 yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
+                 yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, surfaces=False):
         if not shift_heatmap and not flip_test:
             raise ValueError("shift_heatmap=False applies to the flip test: pass flip_test=True")
         frames = _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias,
-                               frame_format, yuv, chroma_siting, frame_layout)
+                               frame_format, yuv, chroma_siting, frame_layout, surfaces)
         self.antialias = _antialias_taps(antialias)                 # samples per crop pixel and axis at most; 1 = the plain crop
-        self.frame_format = frame_format if frames else None        # "rgb" / "nv12": what ``frames`` holds
+        self.frame_format = frame_format if frames else None        # what the frames hold; None: the step takes no frames
         smooth = _check_roi(model, frames, oriented, track_axis, track_min_axis, smooth)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
@@ -771,7 +855,15 @@ class InferStep:
             self.track_axis, self.track_min_axis = (int(track_axis[0]), int(track_axis[1])), float(track_min_axis)
         if frames:
             self.images = None                                      # the inputs of such a step are frames / boxes / frame_index
-            if frame_format == "nv12":                              # the RGB step calls use_frame_input as it always did
+            if surfaces or frame_format not in ("rgb", "nv12"):
+                extra = dict(frame_format=frame_format, frame_layout=frame_layout, surfaces=surfaces)
+                if frame_format != "rgb":
+                    extra.update(yuv=yuv, chroma_siting=chroma_siting)
+                self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
+                                                        **extra)
+                if surfaces:
+                    self._own_surfaces(frames[0])
+            elif frame_format == "nv12":                            # the RGB step calls use_frame_input as it always did
                 self.frames = self.plan.use_frame_input(*frames, padding=float(box_padding), oriented=self.oriented, max_taps=self.antialias,
                                                         frame_format="nv12", yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout)
             else:
@@ -806,7 +898,7 @@ class InferStep:
         self.plan.run_forward(s)
         out, hm = self.plan.out_nchw, self.heatmaps
         bj, h, w = out.shape[0] * out.shape[1], out.shape[2], out.shape[3]
-        preds = self.preds if self.frames is None else self.crop_preds      # the decode works in crop coordinates
+        preds = self.preds if self.frame_format is None else self.crop_preds      # the decode works in crop coordinates
         if self.flip_test:
             hm.copy_(out)
             self.plan.run_forward(s, mirrored=True)
@@ -825,7 +917,7 @@ class InferStep:
         elif self.post_process == "soft":
             check(self.lib.lh_heatmap_soft_argmax(hm.data_ptr(), bj, h, w, self.soft_argmax_beta, self.scale, preds.data_ptr(), s),
                   "lh_heatmap_soft_argmax")
-        if self.frames is not None:
+        if self.frame_format is not None:
             p = self.plan
             check(self.lib.lh_affine_points(preds.data_ptr(), 2, p.crop_mat.data_ptr(), self.preds.data_ptr(), 2, out.shape[0], out.shape[1], s),
                   "lh_affine_points")
@@ -847,8 +939,9 @@ class InferStep:
 
     @property
     def valid(self):
-        """bool [batch]: the slots whose box and frame index were usable in the last run (None without ``frames``)."""
-        return None if self.frames is None else self.plan.src_frame >= 0
+        """bool [batch]: the slots whose box and frame index were usable in the last run (None without ``frames``).  Under
+        ``surfaces=True`` it does not say whether the frame's surface was bound: that is the caller's matter."""
+        return None if self.frame_format is None else self.plan.src_frame >= 0
 
     def advance(self):
         """boxes <- next_boxes (and rot <- next_rot with ``oriented=True``), on the device (``track=True``): the next call crops where
@@ -875,12 +968,16 @@ class InferStep:
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
         self._packed = True
 
-    def __call__(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None):
-        if self.frames is None:
-            if frames is not None or boxes is not None or frame_index is not None:
+    def __call__(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None, surfaces=None):
+        if self.frame_format is None:
+            if frames is not None or boxes is not None or frame_index is not None or surfaces is not None:
                 raise ValueError("frames / boxes / frame_index are the inputs of InferStep(frames=(n_frames, hs, ws))")
         elif images is not None:
             raise ValueError("a step built with frames= takes frames / boxes / frame_index, not images")
+        if self.surfaces and frames is not None:
+            raise ValueError("a step built with surfaces=True owns no frame buffer: pass surfaces= (or bind_surfaces), not frames=")
+        if surfaces is not None:
+            self.bind_surfaces(surfaces)                            # refuses a step built without surfaces=True
         if (rot is not None or mirror is not None) and not self.oriented:
             raise ValueError("rot / mirror are the inputs of InferStep(frames=..., oriented=True)")
         if dt is not None and not self.smooth:
@@ -925,6 +1022,8 @@ class InferPipeline:
     (one slot is one video stream: ``submit(rot=, mirror=, dt=)``, ``steps[i].smooth_preds`` / ``next_rot`` / ``reset_filter()``).
     ``antialias``: as InferStep's, for every slot.
     ``frame_format`` / ``yuv`` / ``chroma_siting`` / ``frame_layout``: as InferStep's; every slot owns its NV12 buffer.
+    ``surfaces``: as InferStep's; every slot owns its surface table, and ``submit(surfaces=seq, ...)`` binds on the slot that runs
+    the ticket (the slot keeps the references until it is bound again, ``depth`` submits later).
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
@@ -934,11 +1033,11 @@ class InferPipeline:
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
                  blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
                  track_min_joints=8, track_min_side=16.0, oriented=False, track_axis=(0, 9), track_min_axis=4.0, smooth=None,
-                 antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None):
+                 antialias=False, frame_format="rgb", yuv=("bt709", "limited"), chroma_siting="left", frame_layout=None, surfaces=False):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         _check_roi(model, _check_frames(frames, input_u8, box_padding, track, track_min_score, track_min_joints, track_min_side, antialias,
-                                        frame_format, yuv, chroma_siting, frame_layout),
+                                        frame_format, yuv, chroma_siting, frame_layout, surfaces),
                    oriented, track_axis, track_min_axis, smooth)
         self.steps = [InferStep(model, batch, height, width, bn_train=False, input_u8=input_u8, slot=i, flip_test=flip_test,
                                 shift_heatmap=shift_heatmap, post_process=post_process, blur_kernel=blur_kernel,
@@ -946,7 +1045,7 @@ class InferPipeline:
                                 track_min_score=track_min_score, track_min_joints=track_min_joints, track_min_side=track_min_side,
                                 oriented=oriented, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth,
                                 antialias=antialias, frame_format=frame_format, yuv=yuv, chroma_siting=chroma_siting,
-                                frame_layout=frame_layout)
+                                frame_layout=frame_layout, surfaces=surfaces)
                       for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
@@ -957,17 +1056,22 @@ class InferPipeline:
         for s in self.steps:
             s._packed = False
 
-    def submit(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None):
+    def submit(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None, surfaces=None):
         i = self.count % len(self.steps)
         st = self.streams[i]
         st.wait_stream(torch.cuda.current_stream())          # the caller's copy of `images` into place is ordered before
-        for t in (images, frames, boxes, frame_index, rot, mirror, dt):
+        # the surfaces are READ by the slot's replay on `st` (nothing copies them): the same rule, or the allocator hands a surface's
+        # block out once the slot drops its reference at its next submit while this replay may still be reading it
+        bound = [surfaces] if torch.is_tensor(surfaces) else list(surfaces) if surfaces is not None else []
+        if surfaces is not None and not torch.is_tensor(surfaces):
+            surfaces = bound                                  # (an iterator is walked once)
+        for t in [images, frames, boxes, frame_index, rot, mirror, dt] + bound:
             if torch.is_tensor(t) and t.is_cuda:
                 # the slot's copy of an input runs on `st`: tell the caching allocator, or a caller that drops the batch right
                 # after submit() gets the same block back for the next batch while this copy is still queued
                 t.record_stream(st)
         with torch.cuda.stream(st):
-            self.steps[i](images, frames, boxes, frame_index, rot, mirror, dt)
+            self.steps[i](images, frames, boxes, frame_index, rot, mirror, dt, surfaces)
             self.events[i] = st.record_event()
         self.count += 1
         return self.count - 1

@@ -5,7 +5,8 @@ captured graph plus one device-to-device copy per frame, no host arithmetic in b
 
     track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
                     [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME] [--antialias [N]]
-                    [--frame_format nv12 [--yuv_matrix bt601|bt709] [--yuv_range limited|full] [--chroma_siting left|center]]
+                    [--frame_format nv12|nv21|yuv420p|p010 [--yuv_matrix bt601|bt709] [--yuv_range limited|full]
+                     [--chroma_siting left|center]] [--surfaces]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -22,7 +23,10 @@ filters the keypoints (InferStep(smooth=...)); the line then also gives the mean
 out) samples per axis over each crop pixel's footprint where a ROI is minified (InferStep(antialias=N)).  ``--frame_format nv12`` hands
 the step what a video decoder does: the synthetic frames are encoded to NV12 on the host (topdown.rgb_to_nv12_host, with
 ``--yuv_matrix`` / ``--yuv_range``) and the crop converts each sample back (InferStep(frame_format="nv12", yuv=..., chroma_siting=...)).
-With none of the six the sequence and the line are what they were; the new keys appear only with the new options."""
+``--frame_format nv21 | yuv420p | p010`` encode with topdown.rgb_to_yuv420_host in the tight layout of that format.  ``--surfaces``
+allocates one device tensor per synthetic frame, as a decoder on the same GPU leaves its surfaces, and binds the frame's tensor in
+front of every replay in place of the copy into ``step.frames`` (InferStep(surfaces=True), ``step(surfaces=[tensor])``).
+With none of these the sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
 import time
@@ -47,10 +51,12 @@ def build_parser():
     ap.add_argument("--spin", default=0.0, type=float, metavar="DEG_PER_FRAME", help="turn each synthetic constellation about its centre")
     ap.add_argument("--antialias", nargs="?", type=int, const=8, default=None, metavar="N",
                     help="area sampling of minified ROIs: at most N (1..8, default 8) samples per crop pixel and axis")
-    ap.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12"], help="what the frame buffer holds: packed RGB or NV12")
+    ap.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12", "nv21", "yuv420p", "p010"],
+                    help="what the frame buffer holds: packed RGB or a 4:2:0 format under its decoder's name")
     ap.add_argument("--yuv_matrix", default="bt709", choices=["bt601", "bt709"], help="luma coefficients of NV12 frames")
     ap.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
     ap.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
+    ap.add_argument("--surfaces", action="store_true", help="one device tensor per frame, bound in place (no copy into a frame buffer)")
     return ap
 
 
@@ -86,12 +92,25 @@ def main(argv=None):
             ap.error("--frame_format nv12 needs even frame sides")
         frames = rgb_to_nv12_host(frames, args.yuv_matrix, args.yuv_range)
         options.update(frame_format="nv12", yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
+    elif args.frame_format != "rgb":
+        from lighthand_amd.topdown import rgb_to_yuv420_host
+        if hs % 2 or ws % 2:
+            ap.error(f"--frame_format {args.frame_format} needs even frame sides")
+        frames = rgb_to_yuv420_host(frames, args.frame_format, args.yuv_matrix, args.yuv_range)
+        options.update(frame_format=args.frame_format, yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
     elif (args.yuv_matrix, args.yuv_range, args.chroma_siting) != ("bt709", "limited", "left"):
         ap.error("--yuv_matrix / --yuv_range / --chroma_siting need --frame_format nv12")
+    if args.surfaces:
+        options["surfaces"] = True
     mirror = torch.arange(args.hands, dtype=torch.int32) % 2 if args.mirror else None
     seq = torch.from_numpy(frames).pin_memory()
+    if args.surfaces:                                              # what a decoder on this GPU leaves behind: one tensor per frame
+        surfaces = [f.cuda().reshape(-1) for f in seq]
+        feed = lambda t: dict(surfaces=surfaces[t:t + 1])          # noqa: E731
+    else:
+        feed = lambda t: dict(frames=seq[t:t + 1])                 # noqa: E731
     probe = InferStep(model, args.hands, args.size, args.size, **options)
-    probe(frames=seq[:1], boxes=torch.from_numpy(boxes), mirror=mirror)
+    probe(boxes=torch.from_numpy(boxes), mirror=mirror, **feed(0))
     score = float(probe.maxvals.median())                          # random weights: see the module docstring
     del probe
     if args.one_euro:
@@ -100,7 +119,7 @@ def main(argv=None):
     step.boxes.copy_(torch.from_numpy(boxes))
     lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
     moved = torch.zeros((), dtype=torch.float64, device=step.lost.device)
-    step(frames=seq[:1], mirror=mirror)                            # capture; the loop below starts from the first frame's boxes again
+    step(mirror=mirror, **feed(0))                                 # capture; the loop below starts from the first frame's boxes again
     step.boxes.copy_(torch.from_numpy(boxes))
     if args.oriented:
         step.rot.copy_(torch.tensor([1.0, 0.0]).expand(args.hands, 2))
@@ -109,7 +128,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(args.synthetic):
-        step(frames=seq[t:t + 1])
+        step(**feed(t))
         lost += step.lost
         if args.one_euro:
             moved += (step.smooth_preds - step.preds).norm(dim=-1).mean().double()
@@ -130,8 +149,10 @@ def main(argv=None):
         result["spin"] = args.spin
     if args.antialias is not None:
         result["antialias"] = args.antialias
-    if args.frame_format == "nv12":
-        result.update(frame_format="nv12", yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range, chroma_siting=args.chroma_siting)
+    if args.frame_format != "rgb":
+        result.update(frame_format=args.frame_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range, chroma_siting=args.chroma_siting)
+    if args.surfaces:
+        result["surfaces"] = True
     print(json.dumps(result))
     return result
 

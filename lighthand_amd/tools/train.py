@@ -125,15 +125,19 @@ def parse_args(argv=None, phase="train"):
     p.add_argument("--oriented", action="store_true", help="oriented ROI launch of the frame crop (needs --frame_size)")
     p.add_argument("--antialias", nargs="?", type=int, const=8, default=None, metavar="N",
                    help="area sampling of minified ROIs: at most N (1..8, default 8) samples per crop pixel and axis (needs --frame_size)")
-    p.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12"], help="what the frame buffer holds (needs --frame_size)")
+    p.add_argument("--frame_format", default="rgb", choices=["rgb", "nv12", "nv21", "yuv420p", "p010"],
+                   help="what the frame buffer holds: packed RGB or a 4:2:0 format under its decoder's name (needs --frame_size)")
     p.add_argument("--yuv_matrix", default="bt709", choices=["bt601", "bt709"], help="luma coefficients of NV12 frames")
     p.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
     p.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
+    p.add_argument("--surfaces", action="store_true",
+                   help="bind each batch's frames in place as surfaces instead of copying them into the step's buffer (needs --frame_size)")
     args = p.parse_args(argv)
     roi_flags = any((args.roi_rot, args.roi_scale, args.roi_shift, args.roi_mirror))
     if args.frame_size is None:
-        if roi_flags or args.oriented or args.antialias is not None or args.frame_format != "rgb":
-            p.error("--roi_rot / --roi_scale / --roi_shift / --roi_mirror / --oriented / --antialias / --frame_format need --frame_size HSxWS")
+        if roi_flags or args.oriented or args.antialias is not None or args.frame_format != "rgb" or args.surfaces:
+            p.error("--roi_rot / --roi_scale / --roi_shift / --roi_mirror / --oriented / --antialias / --frame_format / --surfaces need "
+                    "--frame_size HSxWS")
     else:
         if not args.synthetic:
             p.error("--frame_size renders synthetic frames: pass --synthetic N")
@@ -143,11 +147,11 @@ def parse_args(argv=None, phase="train"):
             p.error("--coord_loss_weight with --frame_size needs --use_target_weight")
         if args.antialias is not None and not 1 <= args.antialias <= 8:
             p.error("--antialias takes 1..8")
-        if args.frame_format == "nv12" and (args.frame_size[0] % 2 or args.frame_size[1] % 2):
-            p.error("--frame_format nv12 needs even frame sides")
+        if args.frame_format != "rgb" and (args.frame_size[0] % 2 or args.frame_size[1] % 2):
+            p.error(f"--frame_format {args.frame_format} needs even frame sides")
         if min(args.roi_rot, args.roi_scale, args.roi_shift, args.roi_mirror) < 0 or args.roi_scale >= 1 or args.roi_mirror > 1:
             p.error("--roi_rot, --roi_shift >= 0, 0 <= --roi_scale < 1, 0 <= --roi_mirror <= 1")
-    if args.frame_format != "nv12" and (args.yuv_matrix, args.yuv_range, args.chroma_siting) != ("bt709", "limited", "left"):
+    if args.frame_format == "rgb" and (args.yuv_matrix, args.yuv_range, args.chroma_siting) != ("bt709", "limited", "left"):
         p.error("--yuv_matrix / --yuv_range / --chroma_siting need --frame_format nv12")
     if args.soft_decode and args.dark_decode:
         p.error("--soft_decode and --dark_decode are two decodes: pass one")
@@ -195,15 +199,16 @@ class SyntheticHands(torch.utils.data.Dataset):
 
 
 class SyntheticFrames(torch.utils.data.Dataset):
-    """Seeded full frames of one hand each (--frame_size): (frame uint8 [hs, ws, 3] -- or NV12 [rows, ws] with ``nv12=(matrix, range)``
-    --, joint_2d[21, 2] in FRAME coordinates, box[4] = the joints' bounds).  ``invisible``: as SyntheticHands'."""
+    """Seeded full frames of one hand each (--frame_size): (frame uint8 [hs, ws, 3] -- or NV12 [rows, ws] with ``nv12=(matrix, range)``,
+    or the bytes of ``frame_format`` "nv21" / "yuv420p" / "p010" in its tight layout with that pair --, joint_2d[21, 2] in FRAME
+    coordinates, box[4] = the joints' bounds).  ``invisible``: as SyntheticHands'."""
 
-    def __init__(self, n, frame_size, seed, invisible=None, nv12=None):
+    def __init__(self, n, frame_size, seed, invisible=None, nv12=None, frame_format="nv12"):
         from lighthand_amd.tools.synthetic_frames import synthetic_sequence
-        from lighthand_amd.topdown import rgb_to_nv12_host
+        from lighthand_amd.topdown import rgb_to_yuv420_host
         frames, _, joints = synthetic_sequence(n, frame_size[0], frame_size[1], 1, seed, return_joints=True)
         joints = joints[:, 0]
-        self.frames = torch.from_numpy(rgb_to_nv12_host(frames, *nv12) if nv12 else frames)
+        self.frames = torch.from_numpy(rgb_to_yuv420_host(frames, frame_format, *nv12) if nv12 else frames)
         self.boxes = torch.from_numpy(np.concatenate([joints.min(1), joints.max(1)], 1).astype(np.float32))
         self.joints = torch.from_numpy(joints)
         if invisible is not None:
@@ -222,9 +227,16 @@ def frame_options(args):
     opt = dict(oriented=bool(args.oriented))
     if args.antialias is not None:
         opt["antialias"] = args.antialias
-    if args.frame_format == "nv12":
-        opt.update(frame_format="nv12", yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
+    if args.frame_format != "rgb":
+        opt.update(frame_format=args.frame_format, yuv=(args.yuv_matrix, args.yuv_range), chroma_siting=args.chroma_siting)
+    if getattr(args, "surfaces", False):
+        opt["surfaces"] = True
     return opt
+
+
+def _frames_feed(st, frames):
+    """A batch of frames on the device as the step's input: copied into its buffer, or under --surfaces bound row by row where it lies."""
+    return dict(surfaces=frames.reshape(frames.shape[0], -1)) if st.surfaces else dict(frames=frames)
 
 
 def roi_aug(args):
@@ -430,7 +442,7 @@ def validate(model, loader, args, u8_step=None, frames_step=None):
                 from lighthand_amd.topdown import affine_points_inv
                 st = frames_step(images.shape[0])
                 st.refresh_weights()
-                st(frames=images, boxes=batch[2].cuda(non_blocking=True))
+                st(boxes=batch[2].cuda(non_blocking=True), **_frames_feed(st, images))
                 pred = st.heatmaps
                 joints = affine_points_inv(joints, st.plan.crop_mat, st.plan.src_frame)
                 joints3 = torch.cat([joints, joints3[..., 2:]], 2)
@@ -502,10 +514,11 @@ def main(args, train_set=None, val_set=None):
     if frame_size is not None:
         if train_set is not None or val_set is not None:
             raise SystemExit("--frame_size renders its own synthetic frames: it takes no train_set / val_set")
-        nv12 = (args.yuv_matrix, args.yuv_range) if args.frame_format == "nv12" else None
-        train_set = SyntheticFrames(args.synthetic, frame_size, seed + rank, invisible=invisible, nv12=nv12)
+        nv12 = (args.yuv_matrix, args.yuv_range) if args.frame_format != "rgb" else None
+        fmt = dict(frame_format=args.frame_format) if args.frame_format not in ("rgb", "nv12") else {}
+        train_set = SyntheticFrames(args.synthetic, frame_size, seed + rank, invisible=invisible, nv12=nv12, **fmt)
         val_set = SyntheticFrames(args.val_synthetic or max(args.batch_size, max(args.synthetic, args.batch_size * 8) // 8), frame_size,
-                                  seed + 1000, invisible=invisible, nv12=nv12)
+                                  seed + 1000, invisible=invisible, nv12=nv12, **fmt)
     if train_set is None:
         if not args.synthetic:
             raise SystemExit("the reference's datasets (LightHand99K / FreiHAND / ...) are not shipped: pass --synthetic N, or call "
@@ -585,8 +598,8 @@ def main(args, train_set=None, val_set=None):
         if frame_size is not None:                 # (frame, joints in frame coordinates, box, jitter?)
             images, joints, boxes, aug = batch
             st = step_for(images.shape[0])
-            st(frames=images.cuda(non_blocking=True), boxes=boxes.cuda(non_blocking=True), joints=joints.cuda(non_blocking=True),
-               aug=aug if crop_jitter else None)
+            st(boxes=boxes.cuda(non_blocking=True), joints=joints.cuda(non_blocking=True), aug=aug if crop_jitter else None,
+               **_frames_feed(st, images.cuda(non_blocking=True)))
             return lambda: st.loss
         images, joints, aug = batch
         st = step_for(images.shape[0])

@@ -27,10 +27,19 @@ the crop through the inverse of the crop matrix (``POINT_OFF`` for a slot that h
 
 ColorJitter on the crop (lh_frames_crop_jitter_to_nhwc4, runtime.TrainStep(frames=..., crop_jitter=...)): ``frames_crop(...,
 jitter=(factors, order))`` is the launch, ``frames_crop_jitter_host`` its rule in numpy -- the host crop stopped in front of
-Normalize, csrc/color_jitter.h's four ops (``color_jitter_host``), Normalize -- in fp32 or, as the yardstick, in fp64."""
+Normalize, csrc/color_jitter.h's four ops (``color_jitter_host``), Normalize -- in fp32 or, as the yardstick, in fp64.
+
+Decoder surfaces in place and the other 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4, InferStep / TrainStep(frames=...,
+surfaces=True, frame_format="nv21" | "yuv420p" | "p010")): ``yuv420_layout`` gives the plane descriptor of a format (``Yuv420Layout``),
+``surface_bytes`` what a surface must hold, ``check_surface`` / ``surface_table`` the host checks and the table of addresses,
+``yuv_matrix(..., bits=10)`` the matrix of p010's texels, ``frames_crop(..., surfaces=[...])`` the launch, ``frames_crop_yuv420_host``
+its rule in numpy -- the NV12 rule behind another texel fetch -- and ``rgb_to_yuv420_host`` an encoder for the tools and tests."""
+import collections
+
 import numpy as np
 
 F = np.float32
+_range = range          # several functions below take a parameter named ``range`` (the YUV range)
 
 
 def box_affine_host(boxes, frame_index, n_frames, size, padding):
@@ -136,21 +145,27 @@ _YUV_RANGE = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16.0), "full": (1.0, 1.0
 _SITING = {"left": 0, "center": 1}
 
 
-def _yuv_matrix64(standard, range):
+def _yuv_matrix64(standard, range, bits=8):
     if not (isinstance(standard, str) and isinstance(range, str)) or standard not in _YUV_K or range not in _YUV_RANGE:
         raise ValueError(f"yuv_matrix: standard is one of {sorted(_YUV_K)} and range one of {sorted(_YUV_RANGE)}, not {standard!r} / {range!r}")
+    if isinstance(bits, bool) or bits not in (8, 10):
+        raise ValueError(f"yuv_matrix: bits is 8 or 10, not {bits!r}")
     kr, kb = _YUV_K[standard]
     kg = 1.0 - kr - kb
     ys, cs, o0 = _YUV_RANGE[range]
     k = np.array([[ys, 0.0, 2 * (1 - kr) * cs], [ys, -2 * (1 - kb) * kb / kg * cs, -2 * (1 - kr) * kr / kg * cs], [ys, 2 * (1 - kb) * cs, 0.0]])
+    if bits == 10 and range == "full":                                 # 0..1023 on the v/4 scale is 0..255.75
+        k = k * (255.0 / 255.75)
     return k, np.array([o0, 128.0, 128.0])
 
 
-def yuv_matrix(standard="bt709", range="limited"):
+def yuv_matrix(standard="bt709", range="limited", bits=8):
     """float32 [12] = k[3][3] row-major then o[3], lh_frames_crop_yuv_to_nhwc4's csc12: rgb = k (yuv - o) on 8-bit values, for the
     luma coefficients of ``standard`` ("bt601": Kr, Kb = 0.299, 0.114; "bt709": 0.2126, 0.0722; Kg = 1 - Kr - Kb) and ``range``
-    ("limited": Y in 16..235, CbCr in 16..240; "full": 0..255).  Computed in fp64 and rounded once."""
-    k, o = _yuv_matrix64(standard, range)
+    ("limited": Y in 16..235, CbCr in 16..240; "full": 0..255).  Computed in fp64 and rounded once.  ``bits=10``: for 10-bit samples on
+    the v/4 scale a p010 texel has -- "limited" is the 8-bit matrix unchanged (64..940 is 4 x 16..235), "full" the 8-bit full-range
+    matrix times 255/255.75 with offsets (0, 128, 128)."""
+    k, o = _yuv_matrix64(standard, range, bits)
     return np.concatenate([k.ravel(), o]).astype(np.float32)
 
 
@@ -161,10 +176,10 @@ def chroma_siting_code(chroma_siting):
     return _SITING[chroma_siting]
 
 
-def _csc12(yuv):
-    """yuv = (standard, range) or 12 numbers -> float32 [12]."""
+def _csc12(yuv, bits=8):
+    """yuv = (standard, range) or 12 numbers -> float32 [12]; ``bits`` is the samples' (10: p010), for the (standard, range) form."""
     if isinstance(yuv, (tuple, list)) and len(yuv) == 2 and all(isinstance(v, str) for v in yuv):
-        return yuv_matrix(*yuv)
+        return yuv_matrix(*yuv, bits=bits)
     if isinstance(yuv, str):
         raise ValueError(f"yuv is (standard, range) or 12 coefficients, not {yuv!r}")
     try:
@@ -306,6 +321,272 @@ def _crop_unit_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("bt
     return out
 
 
+# ---- decoder surfaces and the 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4): one plane descriptor for nv12 / nv21 / yuv420p / p010
+FRAME_FORMATS = ("rgb", "nv12", "nv21", "yuv420p", "p010")          # the decoders' own pixel-format names
+_FMT_CODE = {"rgb": 0, "nv12": 1, "nv21": 2, "yuv420p": 3, "p010": 4}          # LH_FRAMES_FMT_* of the header
+
+Yuv420Layout = collections.namedtuple("Yuv420Layout", "code sample_bytes shift pitch c_pitch cb_offset cr_offset c_step frame_bytes hs ws")
+Yuv420Layout.__doc__ = """Where the samples of one hs x ws frame are, from its first byte (yuv420_layout builds it): ``code`` the format
+(LH_FRAMES_FMT_*), ``sample_bytes`` 1 or 2 (little-endian), ``shift`` the low bits of a sample that are not data (6 for p010: the
+texel is (u16 >> 6) * 0.25), luma (x, y) at y*pitch + x*sample_bytes, Cb / Cr of chroma sample (cx, cy) at cb_offset / cr_offset +
+cy*c_pitch + cx*c_step, ``frame_bytes`` what one frame occupies."""
+
+
+def check_frame_format(frame_format):
+    if not isinstance(frame_format, str) or frame_format not in FRAME_FORMATS:
+        raise ValueError(f"frame_format is one of {', '.join(repr(f) for f in FRAME_FORMATS)}, not {frame_format!r}")
+    return frame_format
+
+
+def _plane_ends(L):
+    """(luma end, one chroma plane's extent from its offset) of a Yuv420Layout: the closed forms surface_bytes and the checks share."""
+    hc, wc = L.hs // 2, L.ws // 2
+    luma = (L.hs - 1) * L.pitch + L.ws * L.sample_bytes
+    plane = (hc - 1) * L.c_pitch + (wc if L.code == 3 else (wc - 1) * L.c_step + L.sample_bytes)
+    return luma, plane
+
+
+def check_yuv420_layout(layout, hs=None, ws=None, frame_format=None):
+    """A Yuv420Layout (yuv420_layout's, or one edited with ``_replace``: yuv420p with cb_offset and cr_offset swapped is YV12) ->
+    the layout, or ValueError: what lh_frames_crop_surfaces_to_nhwc4 refuses, and a layout of another size or format than asked for."""
+    L = layout
+    if not isinstance(L, Yuv420Layout) or not all(_is_int(v) for v in L) or L.code not in (1, 2, 3, 4):
+        raise ValueError(f"frame layout must be topdown.yuv420_layout(...)'s named tuple, not {layout!r}")
+    name = FRAME_FORMATS[L.code]
+    if frame_format is not None and name != frame_format:
+        raise ValueError(f"frame layout is a {name!r} layout, the frames are {frame_format!r}")
+    if (hs is not None and L.hs != hs) or (ws is not None and L.ws != ws):
+        raise ValueError(f"frame layout describes {L.hs} x {L.ws} frames, not {hs} x {ws}")
+    sb = 2 if L.code == 4 else 1
+    if L.hs < 2 or L.ws < 2 or L.hs % 2 or L.ws % 2:
+        raise ValueError(f"yuv420_layout: 4:2:0 frames have even integer sides >= 2, not {L.hs!r} x {L.ws!r}")
+    if L.sample_bytes != sb or L.shift != (6 if sb == 2 else 0) or L.c_step != (1 if L.code == 3 else 2 * sb):
+        raise ValueError(f"yuv420_layout: {name} has sample_bytes {sb}, shift {6 if sb == 2 else 0} and c_step {1 if L.code == 3 else 2 * sb}, not "
+                         f"{L.sample_bytes} / {L.shift} / {L.c_step}")
+    wc = L.ws // 2
+    if L.pitch < L.ws * sb or L.c_pitch < (wc if L.code == 3 else wc * 2 * sb):
+        raise ValueError(f"yuv420_layout: pitch {L.pitch} / c_pitch {L.c_pitch} are below a row's bytes ({L.ws * sb} luma, "
+                         f"{wc if L.code == 3 else wc * 2 * sb} chroma)")
+    if sb == 2 and (L.pitch % 2 or L.c_pitch % 2 or L.cb_offset % 2 or L.cr_offset % 2):
+        raise ValueError(f"yuv420_layout: p010 samples are 16-bit: pitch {L.pitch}, c_pitch {L.c_pitch} and the offsets must be even")
+    delta = {1: 1, 2: -1, 4: 2}.get(L.code)
+    if delta is not None and L.cr_offset - L.cb_offset != delta:
+        raise ValueError(f"yuv420_layout: {name} has cr_offset - cb_offset = {delta}, not {L.cr_offset - L.cb_offset}")
+    luma, plane = _plane_ends(L)
+    lo, hi = min(L.cb_offset, L.cr_offset), max(L.cb_offset, L.cr_offset)
+    if lo < luma or (L.code == 3 and hi < lo + plane):
+        raise ValueError(f"yuv420_layout: the planes overlap (luma ends at byte {luma}, cb_offset {L.cb_offset}, cr_offset {L.cr_offset}, "
+                         f"{plane} bytes a chroma plane)")
+    if L.frame_bytes < hi + plane or L.frame_bytes >= 1 << 31:
+        raise ValueError(f"yuv420_layout: a frame of {L.frame_bytes} bytes does not hold its planes (they end at byte {hi + plane}) or does "
+                         f"not fit 32-bit byte indices")
+    return L
+
+
+def yuv420_layout(frame_format, hs, ws, pitch=None, luma_rows=None, chroma_pitch=None):
+    """The layout of hs x ws frames of ``frame_format`` ("nv12", "nv21", "yuv420p", "p010") as a Yuv420Layout: ``luma_rows`` (>= hs,
+    default hs) rows of luma on a row pitch of ``pitch`` bytes (default: the row's own bytes), then the chroma: hs/2 rows of
+    interleaved pairs on ``chroma_pitch`` (default ``pitch``) for nv12 (Cb first), nv21 (Cr first) and p010 (16-bit samples, Cb
+    first), or a Cb plane and then a Cr plane of hs/2 rows on ``chroma_pitch`` (default pitch/2, rounded up) for yuv420p.  The defaults
+    are the tight layout; a decoder's surface passes its pitch and aligned height.  (YV12 is yuv420p with the two offsets swapped:
+    ``layout._replace(cb_offset=layout.cr_offset, cr_offset=layout.cb_offset)``.)"""
+    if not isinstance(frame_format, str) or frame_format not in FRAME_FORMATS[1:]:
+        raise ValueError(f"yuv420_layout: frame_format is one of {FRAME_FORMATS[1:]}, not {frame_format!r}")
+    code = _FMT_CODE[frame_format]
+    sb = 2 if code == 4 else 1
+    if not all(_is_int(v) for v in (hs, ws)) or hs < 2 or ws < 2 or hs % 2 or ws % 2:
+        raise ValueError(f"yuv420_layout: 4:2:0 frames have even integer sides >= 2, not {hs!r} x {ws!r}")
+    pitch = ws * sb if pitch is None else pitch
+    luma_rows = hs if luma_rows is None else luma_rows
+    chroma_pitch = ((pitch + 1) // 2 if code == 3 else pitch) if chroma_pitch is None and _is_int(pitch) else chroma_pitch
+    if not all(_is_int(v) for v in (pitch, luma_rows, chroma_pitch)):
+        raise ValueError(f"yuv420_layout: pitch, luma_rows and chroma_pitch are integers, not {pitch!r} / {luma_rows!r} / {chroma_pitch!r}")
+    hc = hs // 2
+    cb = pitch * luma_rows
+    if code == 3:
+        cr, frame_bytes = cb + chroma_pitch * hc, cb + 2 * chroma_pitch * hc
+    else:
+        cb, cr = (cb + 1, cb) if code == 2 else (cb, cb + sb)
+        frame_bytes = pitch * luma_rows + chroma_pitch * hc
+    return check_yuv420_layout(Yuv420Layout(code, sb, 6 if sb == 2 else 0, int(pitch), int(chroma_pitch), int(cb), int(cr),
+                                            1 if code == 3 else 2 * sb, int(frame_bytes), int(hs), int(ws)))
+
+
+def _rgb_layout(hs, ws):
+    if hs * ws * 3 >= 1 << 31:
+        raise ValueError(f"a packed RGB frame of {hs} x {ws} does not fit 32-bit byte indices")
+    return Yuv420Layout(0, 1, 0, ws * 3, 0, 0, 0, 0, hs * ws * 3, int(hs), int(ws))
+
+
+def frame_layout_of(frame_format, hs, ws, layout=None):
+    """The Yuv420Layout a step or a launch uses for hs x ws frames of ``frame_format``: ``layout`` None is the tight one; "nv12" also
+    takes nv12_layout's 4-tuple; "rgb" has no layout to pass (packed [hs][ws][3])."""
+    check_frame_format(frame_format)
+    if frame_format == "rgb":
+        if layout is not None:
+            raise ValueError(f"frame_layout={layout!r} describes 4:2:0 frames: packed RGB frames have none")
+        return _rgb_layout(hs, ws)
+    if frame_format == "nv12" and not isinstance(layout, Yuv420Layout):          # nv12_layout's rules and error texts, as they were
+        pitch, _, _, rows = _check_layout(hs, ws, layout)
+        return yuv420_layout("nv12", hs, ws, pitch, rows - hs // 2)
+    if layout is None:
+        return yuv420_layout(frame_format, hs, ws)
+    return check_yuv420_layout(layout, hs, ws, frame_format)
+
+
+def surface_bytes(layout):
+    """The bytes a surface of ``layout`` (a Yuv420Layout) must hold: the highest byte a sample can touch, plus one."""
+    if isinstance(layout, Yuv420Layout) and layout.code == 0:
+        return layout.frame_bytes
+    L = check_yuv420_layout(layout)
+    return max(L.cb_offset, L.cr_offset) + _plane_ends(L)[1]
+
+
+def _frames_layout_struct(L, yuv, chroma_siting):
+    """The lh_frames_layout of a Yuv420Layout (``yuv`` and ``chroma_siting`` as frames_crop's)."""
+    from . import _lib
+    s = _lib.FramesLayout()
+    s.format = L.code
+    if L.code:
+        s.pitch, s.c_pitch, s.cb_offset, s.cr_offset, s.frame_bytes = L.pitch, L.c_pitch, L.cb_offset, L.cr_offset, L.frame_bytes
+        s.chroma_siting = chroma_siting_code(chroma_siting)
+        s.csc12[:] = _csc12(yuv, 10 if L.code == 4 else 8).tolist()
+    return s
+
+
+def rgb_to_yuv420_host(frames_rgb, frame_format="nv12", standard="bt709", range="limited", layout=None):
+    """uint8 RGB frames [n][hs][ws][3] (even hs, ws) -> the frames as ``frame_format`` in ``layout``, uint8 [n][frame_bytes] (for
+    "nv12" with ``layout`` None or nv12_layout's tuple: rgb_to_nv12_host's array, [n][rows][pitch]): rgb_to_nv12_host's rounding --
+    Y = rint per pixel, Cb and Cr = rint of the mean over each 2 x 2 block, clipped -- laid out through the plane descriptor.  "p010"
+    rounds to 10 bits (the code value is 4 x the 8-bit scale's through yuv_matrix(..., bits=10)) and stores them shifted left by 6,
+    little-endian.  The bytes between the planes and beside the rows are 0.  For the tools and the tests."""
+    check_frame_format(frame_format)
+    if frame_format == "nv12" and not isinstance(layout, Yuv420Layout):
+        return rgb_to_nv12_host(frames_rgb, standard, range, layout)
+    frames = np.asarray(frames_rgb)
+    if frame_format == "rgb" or frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
+        raise ValueError(f"rgb_to_yuv420_host: frames uint8 [n][hs][ws][3] to a 4:2:0 format, not {frames.shape} {frames.dtype} to {frame_format!r}")
+    n, hs, ws = frames.shape[:3]
+    L = frame_layout_of(frame_format, hs, ws, layout)
+    bits = 10 if L.code == 4 else 8
+    k, o = _yuv_matrix64(standard, range, bits)
+    yuv = frames.astype(np.float64) @ np.linalg.inv(k).T + o
+    scale, top = (4.0, 1023) if bits == 10 else (1.0, 255)
+    luma = np.clip(np.rint(yuv[..., 0] * scale), 0, top).astype(np.int64) << L.shift
+    chroma = np.clip(np.rint(yuv[..., 1:].reshape(n, hs // 2, 2, ws // 2, 2, 2).mean((2, 4)) * scale), 0, top).astype(np.int64) << L.shift
+    out = np.zeros((n, L.frame_bytes), np.uint8)
+    y, x = np.meshgrid(np.arange(hs), np.arange(ws), indexing="ij")
+    cy, cx = np.meshgrid(np.arange(hs // 2), np.arange(ws // 2), indexing="ij")
+    for byte in _range(L.sample_bytes):                    # little-endian
+        out[:, y * L.pitch + x * L.sample_bytes + byte] = (luma >> (8 * byte)) & 255
+        out[:, L.cb_offset + cy * L.c_pitch + cx * L.c_step + byte] = (chroma[..., 0] >> (8 * byte)) & 255
+        out[:, L.cr_offset + cy * L.c_pitch + cx * L.c_step + byte] = (chroma[..., 1] >> (8 * byte)) & 255
+    return out
+
+
+def _sample_420_host(flat, L, siting, k, o, fx, fy, T):
+    """One sample per element of fx / fy of one frame (``flat``: its bytes, uint8) through the plane descriptor ``L``,
+    lh_frames_crop_surfaces_to_nhwc4's: _sample_nv12_host's operations in its order, the texel fetch apart -> (RGB on 0..255, type T
+    [3][...], inside mask)."""
+    hs, ws = L.hs, L.ws
+    with np.errstate(all="ignore"):
+        inside = (fx >= T(-0.5)) & (fx <= T(ws) - T(0.5)) & (fy >= T(-0.5)) & (fy <= T(hs) - T(0.5))
+    cy = np.where(inside, np.maximum(fy, T(0)), T(0)).astype(T)
+    cx = np.where(inside, np.maximum(fx, T(0)), T(0)).astype(T)
+
+    def tex(off):
+        if L.sample_bytes == 2:
+            u16 = flat[off].astype(np.int32) | (flat[off + 1].astype(np.int32) << 8)
+            return (u16 >> L.shift).astype(T) * T(0.25)
+        return flat[off].astype(T)
+
+    def blend(at, x0, x1, y0, y1, wx, wy):
+        a00, a01, a10, a11 = tex(at(x0, y0)), tex(at(x1, y0)), tex(at(x0, y1)), tex(at(x1, y1))
+        top, bot = a00 + (a01 - a00) * wx, a10 + (a11 - a10) * wx
+        return top + (bot - top) * wy
+
+    y0, x0 = np.minimum(cy.astype(np.int32), hs - 1), np.minimum(cx.astype(np.int32), ws - 1)
+    y1, x1 = np.minimum(y0 + 1, hs - 1), np.minimum(x0 + 1, ws - 1)
+    lum = blend(lambda x, y: y * L.pitch + x * L.sample_bytes, x0, x1, y0, y1, cx - x0.astype(T), cy - y0.astype(T))
+    hc, wc = hs // 2, ws // 2
+    gx = cx * T(0.5) if siting == 0 else (cx - T(0.5)) * T(0.5)
+    gy = (cy - T(0.5)) * T(0.5)
+    gx, gy = np.minimum(np.maximum(gx, T(0)), T(wc - 1)), np.minimum(np.maximum(gy, T(0)), T(hc - 1))
+    v0, u0 = np.minimum(gy.astype(np.int32), hc - 1), np.minimum(gx.astype(np.int32), wc - 1)
+    v1, u1 = np.minimum(v0 + 1, hc - 1), np.minimum(u0 + 1, wc - 1)
+    wx, wy = gx - u0.astype(T), gy - v0.astype(T)
+    cb = blend(lambda x, y: L.cb_offset + y * L.c_pitch + x * L.c_step, u0, u1, v0, v1, wx, wy)
+    cr = blend(lambda x, y: L.cr_offset + y * L.c_pitch + x * L.c_step, u0, u1, v0, v1, wx, wy)
+    e0, e1, e2 = lum - o[0], cb - o[1], cr - o[2]
+    rgb = np.stack([np.minimum(np.maximum((k[c, 0] * e0 + k[c, 1] * e1) + k[c, 2] * e2, T(0)), T(255)) for c in (0, 1, 2)])
+    return np.where(inside, rgb, T(0)).astype(T), inside
+
+
+def _frame_bytes_host(frames_or_surfaces, need, who):
+    """One array [n][...] or a sequence of per-frame byte arrays (None: an unbound surface) -> a list of flat uint8 arrays / None."""
+    seq = list(frames_or_surfaces) if isinstance(frames_or_surfaces, (list, tuple)) else list(np.asarray(frames_or_surfaces))
+    out = []
+    for f in seq:
+        if f is None:
+            out.append(None)
+            continue
+        f = np.asarray(f)
+        if f.dtype != np.uint8 or f.size < need:
+            raise ValueError(f"{who}: a frame is uint8 with at least {need} bytes, not {f.shape} {f.dtype}")
+        out.append(f.reshape(-1))
+    return out
+
+
+def _crop_unit_yuv420_host(frames_or_surfaces, frame_size, mat, src_frame, size, frame_format="nv12", layout=None, yuv=("bt709", "limited"),
+                           chroma_siting="left", max_taps=1, dtype=np.float32):
+    """frames_crop_yuv420_host stopped in front of Normalize: the pixels' c in 0..1, [b][3][h][w] of ``dtype``."""
+    T = np.dtype(dtype).type
+    hs, ws = int(frame_size[0]), int(frame_size[1])
+    L = frame_layout_of(frame_format, hs, ws, layout)
+    frames = _frame_bytes_host(frames_or_surfaces, surface_bytes(L), "frames_crop_yuv420_host")
+    n = len(frames)
+    h, w = int(size[0]), int(size[1])
+    mat = np.asarray(mat, np.float32).reshape(-1, 6)
+    src = np.asarray(src_frame, np.int32).reshape(-1)
+    if L.code == 0:                                                # packed RGB surfaces: the RGB rule, an unbound surface is an empty slot
+        live = np.array([0 <= s < n and frames[s] is not None for s in src])
+        rgb = np.stack([np.zeros(hs * ws * 3, np.uint8) if f is None else f[:hs * ws * 3] for f in frames]).reshape(n, hs, ws, 3)
+        return _crop_unit_host(rgb, mat, np.where(live, src, -1), size, max_taps).astype(dtype)
+    csc = _csc12(yuv, 10 if L.code == 4 else 8).astype(dtype)
+    k, o = csc[:9].reshape(3, 3), csc[9:]
+    siting = chroma_siting_code(chroma_siting)
+    taps = crop_taps_host(mat, max_taps)
+    oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
+    out = np.empty((len(src), 3, h, w), dtype)
+    for s in _range(len(src)):
+        acc = np.zeros((3, h, w), dtype)
+        kx, ky = int(taps[s, 0]), int(taps[s, 1])
+        if 0 <= src[s] < n and frames[src[s]] is not None:
+            m0, m1, m2, m3, m4, m5 = mat[s].astype(dtype)
+            with np.errstate(all="ignore"):
+                for j in _range(ky):
+                    uy = oy + T(2 * j + 1 - ky) / T(2 * ky)
+                    for i in _range(kx):
+                        ux = ox + T(2 * i + 1 - kx) / T(2 * kx)
+                        acc += _sample_420_host(frames[src[s]], L, siting, k, o, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, T)[0]
+        else:
+            kx = ky = 1
+        out[s] = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
+    return out
+
+
+def frames_crop_yuv420_host(frames_or_surfaces, frame_size, mat, src_frame, size, frame_format="nv12", layout=None, yuv=("bt709", "limited"),
+                            chroma_siting="left", max_taps=1, mean=MEAN, std=STD, dtype=np.float32):
+    """lh_frames_crop_surfaces_to_nhwc4 in numpy: ``frames_or_surfaces`` is one uint8 array [n][...] or a sequence of per-frame byte
+    arrays (None: an unbound surface, the slot is black), each at least surface_bytes(layout) long, of ``frame_size`` = (hs, ws) frames
+    of ``frame_format`` in ``layout`` (frame_layout_of's rules; None: tight) -> normalised [b][3][h][w].  frames_crop_nv12_host's
+    operations in its order, the texels through the plane descriptor (a p010 texel is (u16 >> 6) * 0.25); on NV12 input its bits.
+    fp32 in the kernel's order, or with ``dtype=np.float64`` the same operations in fp64 on the same fp32 matrices and coefficients.
+    ``yuv`` = (standard, range) means yuv_matrix(standard, range, bits=10) for p010."""
+    return _normalise_host(_crop_unit_yuv420_host(frames_or_surfaces, frame_size, mat, src_frame, size, frame_format, layout, yuv,
+                                                  chroma_siting, max_taps, dtype), mean, std, dtype)
+
+
 # ---- ColorJitter on the crop: csrc/color_jitter.h's four ops in numpy, in the kernel's order of operations (T = the evaluation type)
 def _cj_clamp01(v, T):
     return np.minimum(np.maximum(v, T(0)), T(1))
@@ -371,11 +652,15 @@ def frames_crop_jitter_host(frames, mat, src_frame, size, factors, order, max_ta
     ``yuv``, ``chroma_siting`` and ``layout`` as there) stopped in front of Normalize, then per slot the ops of ``order`` int [b][4]
     with ``factors`` fp32 [b][4] (color_jitter_host), then Normalize -> [b][3][h][w].  fp32 in the kernel's order; a slot whose order
     is all negative is the un-jittered host crop bit for bit.  ``dtype=np.float64``: the jitter and Normalize (and, for NV12, the
-    sampling) evaluated in fp64 on the same inputs -- what the fp32 order is measured against."""
-    if frame_format not in ("rgb", "nv12"):
-        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
-    if frame_format == "nv12":
+    sampling) evaluated in fp64 on the same inputs -- what the fp32 order is measured against.  ``frame_format`` "nv21" / "yuv420p" /
+    "p010", a Yuv420Layout, or ``frames`` as a list of per-frame byte arrays (surfaces; None: unbound): frames_crop_yuv420_host's crop."""
+    check_frame_format(frame_format)
+    if frame_format == "nv12" and not isinstance(layout, Yuv420Layout) and not isinstance(frames, (list, tuple)):
         c = _crop_unit_nv12_host(frames, frame_size, mat, src_frame, size, yuv, chroma_siting, max_taps, layout, dtype)
+    elif frame_format != "rgb" or isinstance(frames, (list, tuple)):          # the plane descriptor's formats, or a list of surfaces
+        if frame_size is None:
+            frame_size = np.asarray(frames).shape[1:3]
+        c = _crop_unit_yuv420_host(frames, frame_size, mat, src_frame, size, frame_format, layout, yuv, chroma_siting, max_taps, dtype)
     else:
         c = _crop_unit_host(frames, mat, src_frame, size, max_taps).astype(dtype)
     factors = np.asarray(factors, np.float32).reshape(c.shape[0], 4)
@@ -618,8 +903,35 @@ def box_affine(boxes, frame_index, n_frames, size, padding=1.25):
     return mat, src
 
 
+def check_surface(t, device, layout):
+    """One surface of a step or launch on ``device`` whose frames have ``layout`` (a Yuv420Layout): a contiguous uint8 device tensor of
+    at least surface_bytes(layout) bytes, 2-byte aligned where the samples are 16-bit -> its address; ValueError otherwise."""
+    import torch
+    need = surface_bytes(layout)
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != torch.device(device):
+        raise ValueError(f"a surface is a uint8 tensor on {device}, not {type(t).__name__ if not torch.is_tensor(t) else t.device}")
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError(f"a surface is a contiguous uint8 tensor, not {t.dtype} with strides {tuple(t.stride())}")
+    if t.numel() < need:
+        raise ValueError(f"a surface holds at least {need} bytes (topdown.surface_bytes), not {t.numel()}")
+    if layout.sample_bytes == 2 and t.data_ptr() % 2:
+        raise ValueError("a surface of 16-bit samples must be 2-byte aligned")
+    return t.data_ptr()
+
+
+def surface_table(surfaces, layout, device):
+    """A sequence of surfaces (check_surface's rules; None: an unbound frame, entry 0), or one tensor [k][...] taken row by row ->
+    (int64 device tensor [k] of their addresses, the list of tensors to keep alive): the table lh_frames_crop_surfaces_to_nhwc4 reads."""
+    import torch
+    seq = list(surfaces.unbind(0)) if torch.is_tensor(surfaces) else list(surfaces)
+    if not seq:
+        raise ValueError("surfaces is empty")
+    addresses = [0 if t is None else check_surface(t, device, layout) for t in seq]
+    return torch.tensor(addresses, dtype=torch.int64).to(device), [t for t in seq if t is not None]
+
+
 def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD, frame_format="rgb", frame_size=None,
-                yuv=("bt709", "limited"), chroma_siting="left", layout=None, jitter=None):
+                yuv=("bt709", "limited"), chroma_siting="left", layout=None, jitter=None, surfaces=None):
     """Device tensors frames uint8 [n][hs][ws][3], mat fp32 [b][6], src_frame int32 [b] -> the normalised crops as NHWC4
     [b][h][w][4] of ``dtype`` (torch.float32 by default; no padding, channel 3 is 0) for an h x w = ``size`` crop: one
     lh_frames_crop_area_to_nhwc4 launch on the current stream.  ``max_taps`` 1..8: the most samples per crop pixel and axis that a
@@ -627,16 +939,23 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
     ``frame_size`` = (hs, ws) in ``layout`` (nv12_layout's tuple; None: tight), converted per sample with ``yuv`` ((standard, range)
     or 12 coefficients) and ``chroma_siting`` ("left" / "center"): one lh_frames_crop_yuv_to_nhwc4 launch.  ``jitter=(factors, order)``
     (device tensors fp32 [b][4] and int32 [b][4], runtime.sample_color_jitter's draw): ColorJitter between the sample and Normalize,
-    lh_frames_crop_jitter_to_nhwc4 for either format (the grey-mean launch, then the crop)."""
+    lh_frames_crop_jitter_to_nhwc4 for either format (the grey-mean launch, then the crop).
+    ``frame_format`` "nv21" / "yuv420p" / "p010" (or "nv12" with a Yuv420Layout): frames uint8 [n][frame_bytes] in ``layout``
+    (frame_layout_of's rules), one lh_frames_crop_surfaces_to_nhwc4 launch, with or without ``jitter``.  ``surfaces=`` in place of
+    ``frames`` (which is then None), for every format: a sequence of uint8 device tensors, one per frame and each a frame in place
+    (None: an unbound frame, its slots are black), read through a surface table by the same entry; ``frame_size`` is needed."""
     import ctypes as C
     import torch
     from . import _lib
     if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
         raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
-    if frame_format not in ("rgb", "nv12"):
-        raise ValueError(f"frame_format is 'rgb' or 'nv12', not {frame_format!r}")
+    check_frame_format(frame_format)
     dtype = dtype or torch.float32
-    frames = frames.contiguous()
+    through_descriptor = surfaces is not None or frame_format not in ("rgb", "nv12") or isinstance(layout, Yuv420Layout)
+    if (frames is None) == (surfaces is None):
+        raise ValueError("frames_crop: pass frames (one buffer) or surfaces= (one tensor per frame), one of the two")
+    if not through_descriptor:
+        frames = frames.contiguous()
     mat = mat.to(torch.float32).contiguous()
     src_frame = src_frame.to(torch.int32).contiguous()
     b = mat.shape[0]
@@ -649,6 +968,37 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
                                       f"{tuple(factors.shape)} {factors.dtype} / {tuple(order.shape)} {order.dtype}")
         ws_j = torch.empty(max(1, _lib.load().lh_frames_crop_jitter_workspace_bytes(b) // 8), dtype=torch.float64, device=mat.device)
         jit = (factors.data_ptr(), order.data_ptr(), ws_j.data_ptr())
+    if through_descriptor:
+        if tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,) or not mat.is_cuda or src_frame.device != mat.device:
+            raise _lib.LightHandError(f"frames_crop: mat [b, 6] and src_frame [b] on one device, got {tuple(mat.shape)} / {tuple(src_frame.shape)}")
+        if surfaces is None and frame_format == "rgb" and frame_size is None and frames.dim() == 4:
+            frame_size = tuple(frames.shape[1:3])
+        if not (isinstance(frame_size, (tuple, list)) and len(frame_size) == 2):
+            raise ValueError(f"frames_crop: frame_size=(hs, ws) is needed, not {frame_size!r}")
+        hs, ws = int(frame_size[0]), int(frame_size[1])
+        L = frame_layout_of(frame_format, hs, ws, layout)
+        desc = _frames_layout_struct(L, yuv, chroma_siting)
+        keep = None
+        if surfaces is not None:
+            table, keep = surface_table(surfaces, L, mat.device)
+            source, n = (0, table.data_ptr()), table.shape[0]
+        else:
+            if not frames.is_cuda or frames.device != mat.device or frames.dtype != torch.uint8 or frames.dim() < 2 or not frames.is_contiguous():
+                raise _lib.LightHandError(f"frames_crop: frames contiguous uint8 [n, ...] on the crop's device, got {tuple(frames.shape)} {frames.dtype}")
+            n = frames.shape[0]
+            source = (frames.stride(0), None)
+        h, w = int(size[0]), int(size[1])
+        out = torch.empty(b, h, w, 4, dtype=dtype, device=mat.device)
+        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        with torch.cuda.device(mat.device):
+            _lib.check(_lib.load().lh_frames_crop_surfaces_to_nhwc4(None if surfaces is not None else frames.data_ptr(), out.data_ptr(), *source,
+                                                                    C.byref(desc), b, n, hs, ws, h, w, 0, w, m3, s3,
+                                                                    mat.data_ptr(), src_frame.data_ptr(), max_taps, *(jit or (None, None, None)),
+                                                                    _lib.dtype_code(dtype), _stream()), "lh_frames_crop_surfaces_to_nhwc4")
+        if keep:
+            for t in keep:                                         # the launch is queued: the allocator must not hand the surfaces out before it ran
+                t.record_stream(torch.cuda.current_stream())
+        return out
     if frame_format == "nv12":
         if not (isinstance(frame_size, (tuple, list)) and len(frame_size) == 2):
             raise ValueError(f"frame_format='nv12' needs frame_size=(hs, ws), not {frame_size!r}")

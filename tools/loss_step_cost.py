@@ -10,7 +10,8 @@ that crops its hand ROIs from 32 full frames of 1080 x 1920 on the device, Train
 lh_frames_crop_to_nhwc4 in the uint8 kernel's place, lh_affine_points_inv in front of the target render, lh_affine_points behind the
 decode), the same with roi_aug=(30, 0.25, 0.1, 0.5) (lh_roi_perturb + lh_roi_affine, a new draw copied in per replay), and both with
 crop_jitter=(0.5, 0.5, 0.5, 0.5) (lh_frames_crop_jitter_to_nhwc4: the grey-mean launch and ColorJitter in the crop, a new draw per
-replay): seeded boxes of 200..400 frame pixels, two per frame.
+replay), and the frames leg with surfaces=True (the 32 frames bound in place: lh_frames_crop_surfaces_to_nhwc4 through the surface
+table): seeded boxes of 200..400 frame pixels, two per frame.
 usage (GPU box): python tools/loss_step_cost.py [steps] [rounds] [--coord_loss_weight L | --frames]"""
 import os
 import statistics
@@ -67,7 +68,10 @@ def frames_main():
             ("frames+crop_jitter", dict(frames=(n, hs, ws), crop_jitter=(0.5, 0.5, 0.5, 0.5)),
              lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt)),
             ("frames+roi_aug+crop_jitter", dict(frames=(n, hs, ws), roi_aug=(30.0, 0.25, 0.1, 0.5), crop_jitter=(0.5, 0.5, 0.5, 0.5)),
-             lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt))]
+             lambda st: st(frames=frames, boxes=boxes, frame_index=index, joints=jt)),
+            # the frames leg with the 32 frames bound where they lie (lh_frames_crop_surfaces_to_nhwc4 in the crop's place)
+            ("frames surfaces", dict(frames=(n, hs, ws), surfaces=True),
+             lambda st: st(surfaces=frames.reshape(n, -1), boxes=boxes, frame_index=index, joints=jt))]
     forms = {}
     for tag, kw, first in legs:
         step = TrainStep(bench.build_model(depth=50, precision="bf16"), batch, 256, 256, lr=1e-3, **kw)

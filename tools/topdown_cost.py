@@ -10,8 +10,12 @@ no mirror, which separates the cost of the two sibling launches from that of gat
 antialiased crop (antialias=True: lh_frames_crop_area_to_nhwc4 in the crop's place) against the frames leg: with the boxes above
 (187..625 frame px into 256: 1..3 samples per axis) and with large boxes of half extent 300..500 px (3..5 per axis).  Two legs price
 NV12 frames (frame_format="nv12": lh_frames_crop_yuv_to_nhwc4 in the crop's place, 100 MB of frames, tight layout, BT.709 limited)
-against the frames and the frames+antialias legs, same boxes.  Device events around `steps` replays, after a warm-up; median
-over the rounds.
+against the frames and the frames+antialias legs, same boxes.  Four legs price what reaches the crop from a decoder, against the nv12
+leg: "nv12 copy" pays a device-to-device copy of all 32 frames into ``step.frames`` in front of every replay (what a pipeline whose
+decoder sits on the same GPU pays with a frame buffer), "nv12 surfaces" binds the 32 frames where they lie in front of every replay
+(InferStep(surfaces=True): 32 addresses instead of 99.5 MB), "yuv420p surfaces" and "p010 surfaces" do the same for the planar and the
+10-bit format (lh_frames_crop_surfaces_to_nhwc4 in the crop's place in all three).  Device events around `steps` replays, after a
+warm-up; median over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
 import statistics
@@ -25,11 +29,13 @@ import bench  # noqa: E402
 from lighthand_amd.runtime import InferStep  # noqa: E402
 
 
-def timed(step, n):
+def timed(step, n, feed=None):
+    """``feed``: what every call passes (the legs that copy or bind frames in front of each replay); None: a bare replay."""
+    feed = feed or {}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(n):
-        step()
+        step(**feed)
     b.record()
     b.synchronize()
     return a.elapsed_time(b) / n
@@ -80,15 +86,30 @@ def main():
     for tag in ("frames+antialias", "frames+antialias large"):
         taps = crop_taps_host(forms[tag].plan.crop_mat.cpu().numpy())
         print(f"  {tag}: {int(taps.min())}..{int(taps.max())} samples per axis, {float(taps.prod(1).mean()):.1f} per crop pixel on average", flush=True)
-    for step in forms.values():
-        timed(step, 10)                                                   # warm-up (capture happened in the first call)
+    # what a decoder hands over per replay (after every draw above): the same 99.5 MB as 32 frames of their own, and the RGB bytes
+    # read as 32 tight p010 frames (both are hs * ws * 3 bytes)
+    planes = list(nv12.reshape(n_frames, -1).unbind(0))
+    wide = list(frames.reshape(n_frames, -1).unbind(0))
+    forms["nv12 copy"] = InferStep(model, batch, size, size, frames=(n_frames, hs, ws), frame_format="nv12")
+    feeds = {"nv12 copy": dict(frames=nv12.clone())}
+    for tag, fmt, src in (("nv12 surfaces", "nv12", planes), ("yuv420p surfaces", "yuv420p", planes), ("p010 surfaces", "p010", wide)):
+        forms[tag] = InferStep(model, batch, size, size, frames=(n_frames, hs, ws), frame_format=fmt, surfaces=True)
+        feeds[tag] = dict(surfaces=src)
+    for tag, feed in feeds.items():
+        forms[tag](boxes=boxes, frame_index=index, **feed)
+    for tag, step in forms.items():
+        timed(step, 10, feeds.get(tag))                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
     for _ in range(rounds):
         for tag, step in forms.items():
-            ms[tag].append(timed(step, steps))
+            ms[tag].append(timed(step, steps, feeds.get(tag)))
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
     for tag, v in ms.items():
+        if tag in feeds:
+            print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['nv12']:+.3f} vs nv12; rounds: {', '.join(f'{x:.3f}' for x in v)})",
+                  flush=True)
+            continue
         print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['uint8 crops']:+.3f} vs uint8 crops, {med[tag] - med['frames']:+.3f} "
               f"vs frames, {med[tag] - med['frames+track']:+.3f} vs frames+track; rounds: {', '.join(f'{x:.3f}' for x in v)})", flush=True)
 
