@@ -1,4 +1,4 @@
-// torchvision's ColorJitter on one pixel, shared by the uint8 input kernels (ingest.hip) and the frame crop (topdown.hip).
+// torchvision's ColorJitter on one pixel, shared by the uint8 input kernels (ingest.hip) and the frame crop (frames_crop_kernel.h).
 // The random draw stays on the host (ColorJitter.get_params): per image four factors (brightness, contrast,
 // saturation, hue) and the op order (four op ids 0..3, negative = skip) arrive as device arrays.  Contrast blends
 // with the mean grey level of the WHOLE image as it is when the op runs, so a first pass reduces that mean (of the

@@ -58,7 +58,7 @@ struct U8Args {
 // saturation, hue) and the op order (four op ids 0..3, negative = skip) arrive as device arrays.  Contrast blends
 // with the mean grey level of the WHOLE image as it is when the op runs, so a first kernel reduces that mean (of the
 // image after the ops that precede contrast) into fp64 strip sums, and the second kernel applies everything.
-// The four ops and cj_apply: color_jitter.h, shared with the frame crop (topdown.hip).
+// The four ops and cj_apply: color_jitter.h, shared with the frame crop (frames_crop_kernel.h).
 __device__ __forceinline__ void u8_bilinear(const U8Args& p, int b, int oy, int ox, float* c) {
     const float sy = (float)p.hs / p.h, sx = (float)p.ws / p.w;
     float fy = (oy + 0.5f) * sy - 0.5f, fx = (ox + 0.5f) * sx - 0.5f;

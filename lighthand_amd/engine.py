@@ -978,27 +978,28 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
         rules; kept as ``self.frame_layout``).  Without ``surfaces`` ``frames_u8`` is uint8 [n_frames][frame_bytes]; with it the plan
         owns no frame buffer (``frames_u8`` is None) but ``surface_table`` (int64 [n_frames], zeros: every frame unbound), the device
         addresses of the frames, read by the launch at every replay.  Returns the frame buffer (None with ``surfaces``)."""
-        from . import topdown
+        from . import frame_formats, topdown
         if isinstance(max_taps, bool) or not isinstance(max_taps, int) or not 1 <= max_taps <= 8:
             raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
-        topdown.check_frame_format(frame_format)
+        frame_formats.check_frame_format(frame_format)
         self.surface_table = self.frame_layout = None
-        descriptor = bool(surfaces) or frame_format not in ("rgb", "nv12") or isinstance(frame_layout, topdown.Yuv420Layout)
-        if descriptor:
-            self.frame_layout = topdown.frame_layout_of(frame_format, hs, ws, frame_layout)
-            desc = topdown._frames_layout_struct(self.frame_layout, yuv, chroma_siting)
-            self.keep.append(desc)
+        where = {}                                                # what crop_entry needs to find a sample: desc + source, or nv12
+        if topdown.through_descriptor(frame_format, frame_layout, surfaces):
+            self.frame_layout = frame_formats.frame_layout_of(frame_format, hs, ws, frame_layout)
+            where["desc"] = frame_formats.frames_layout_struct(self.frame_layout, yuv, chroma_siting)
+            self.keep.append(where["desc"])
             if surfaces:
                 self.frames_u8 = None
                 self.surface_table = self._alloc(n_frames, dtype=torch.int64, zero=True)
-                source = (None, 0, self.surface_table.data_ptr())          # (frames, frame_stride, table)
+                where["table"] = self.surface_table.data_ptr()
             else:
                 self.frames_u8 = self._alloc(n_frames, self.frame_layout.frame_bytes, dtype=torch.uint8, zero=True)
-                source = (self.frames_u8.data_ptr(), self.frame_layout.frame_bytes, None)
+                where["frame_stride"] = self.frame_layout.frame_bytes
         elif frame_format == "nv12":
-            pitch, uv_offset, frame_stride, rows = topdown._check_layout(hs, ws, frame_layout)
-            csc, siting = (C.c_float * 12)(*topdown._csc12(yuv).tolist()), topdown.chroma_siting_code(chroma_siting)
+            pitch, uv_offset, frame_stride, rows = frame_formats.check_nv12_layout(hs, ws, frame_layout)
+            csc, siting = (C.c_float * 12)(*frame_formats.csc12(yuv).tolist()), frame_formats.chroma_siting_code(chroma_siting)
             self.keep.append(csc)
+            where["nv12"] = (pitch, uv_offset, frame_stride, siting, csc)
             self.frames_u8 = self._alloc(n_frames, rows, pitch, dtype=torch.uint8, zero=True)
         else:
             self.frames_u8 = self._alloc(n_frames, hs, ws, 3, dtype=torch.uint8, zero=True)
@@ -1019,34 +1020,10 @@ class Plan(Tuner, WgradSchedule, BatchGroups, InferRewrites, WeightPacks, BnGate
             self.jitter_order = torch.full((self.n, 4), -1, dtype=torch.int32, device=self.device)
             ws_j = self._alloc(self.lib.lh_frames_crop_jitter_workspace_bytes(self.n), dtype=torch.uint8)
             self.keep.append(self.jitter_order)
-        if descriptor:
-            jit = (self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr()) if jitter else (None, None, None)
-            self.fwd[i] = _Call(self.lib.lh_frames_crop_surfaces_to_nhwc4, (source[0], self.img_nhwc4.data_ptr()) + source[1:] + (
-                C.byref(desc), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3, s3,
-                self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps) + jit + (self.dt,),
-                f"{frame_format} frame crop input pipeline" + (", surface table" if surfaces else "")
-                + (", antialiased" if max_taps > 1 else "") + (" + ColorJitter" if jitter else ""))
-        elif jitter:
-            nv12 = (pitch, uv_offset, frame_stride, siting, csc) if frame_format == "nv12" else (0, 0, 0, 0, None)
-            self.fwd[i] = _Call(self.lib.lh_frames_crop_jitter_to_nhwc4, (
-                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws) + nv12 + (
-                self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps,
-                self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr(), self.dt),
-                ("NV12 frame crop input pipeline" if frame_format == "nv12" else "frame crop input pipeline")
-                + (", antialiased" if max_taps > 1 else "") + " + ColorJitter")
-        elif frame_format == "nv12":
-            self.fwd[i] = _Call(self.lib.lh_frames_crop_yuv_to_nhwc4, (
-                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, pitch, uv_offset, frame_stride, siting, csc,
-                self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt),
-                "NV12 frame crop input pipeline" + (", antialiased" if max_taps > 1 else ""))
-        elif max_taps > 1:
-            self.fwd[i] = _Call(self.lib.lh_frames_crop_area_to_nhwc4, (
-                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
-                s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), max_taps, self.dt), "antialiased frame crop input pipeline")
-        else:
-            self.fwd[i] = _Call(self.lib.lh_frames_crop_to_nhwc4, (
-                self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws, self.h, self.w, self.img_pad, self.img_wp, m3,
-                s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt), "frame crop input pipeline")
+            where["jit"] = (self.jitter_factors.data_ptr(), self.jitter_order.data_ptr(), ws_j.data_ptr())
+        self.fwd[i] = _Call(*topdown.crop_entry(
+            self.lib, frame_format, max_taps, None if surfaces else self.frames_u8.data_ptr(), self.img_nhwc4.data_ptr(), self.n, n_frames, hs, ws,
+            self.h, self.w, self.img_pad, self.img_wp, m3, s3, self.crop_mat.data_ptr(), self.src_frame.data_ptr(), self.dt, plain=True, **where))
         self.rot = self.mirror = self.roi_aug = self.roi_boxes = self.roi_rot = self.roi_mirror = None
         if oriented or perturb:
             self.rot = self._alloc(self.n, 2, dtype=torch.float32)

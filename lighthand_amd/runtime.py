@@ -121,7 +121,7 @@ def _check_frames(frames, input_u8, box_padding, track, min_score, min_joints, m
     taps = _antialias_taps(antialias)
     given = dict(frame_format=frame_format, yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout)
     topdown.check_frame_format(frame_format)
-    topdown._csc12(yuv)
+    topdown.csc12(yuv)
     topdown.chroma_siting_code(chroma_siting)
     if not isinstance(surfaces, bool):
         raise ValueError(f"surfaces must be False or True, not {surfaces!r}")

@@ -15,10 +15,9 @@ never an angle: the kernels use + - * /, sqrt, abs and comparisons only, which n
 The antialiased crop of minified ROIs (lh_frames_crop_area_to_nhwc4, InferStep(antialias=...)): ``frames_crop`` on device tensors,
 ``crop_taps_host`` / ``frames_crop_host`` in numpy -- with ``max_taps=1`` the plain crop's sampling rule.
 
-NV12 frames (lh_frames_crop_yuv_to_nhwc4, InferStep(frames=..., frame_format="nv12")): ``yuv_matrix`` gives the conversion's 12
-coefficients, ``nv12_layout`` the buffer of a pitched surface, ``frames_crop(..., frame_format="nv12")`` is the launch,
-``frames_crop_nv12_host`` its rule in numpy (fp32, or fp64 with ``dtype=np.float64``) and ``rgb_to_nv12_host`` an encoder for the tools
-and tests.
+NV12 frames (lh_frames_crop_yuv_to_nhwc4, InferStep(frames=..., frame_format="nv12")): ``frames_crop(..., frame_format="nv12")`` is the
+launch, ``frames_crop_nv12_host`` its rule in numpy (fp32, or fp64 with ``dtype=np.float64``).  The pixel formats themselves -- the
+conversion matrix, the layouts, the encoders -- are frame_formats.py's; every public name there is imported here.
 
 Training on frames (lh_roi_perturb / lh_affine_points_inv, runtime.TrainStep(frames=..., roi_aug=...)): ``roi_perturb`` turns the
 caller's ROI and a drawn row (c, s, k, tx, ty, flip) into the ROI the crop uses, ``affine_points_inv`` takes frame coordinates into
@@ -30,16 +29,17 @@ jitter=(factors, order))`` is the launch, ``frames_crop_jitter_host`` its rule i
 Normalize, csrc/color_jitter.h's four ops (``color_jitter_host``), Normalize -- in fp32 or, as the yardstick, in fp64.
 
 Decoder surfaces in place and the other 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4, InferStep / TrainStep(frames=...,
-surfaces=True, frame_format="nv21" | "yuv420p" | "p010")): ``yuv420_layout`` gives the plane descriptor of a format (``Yuv420Layout``),
-``surface_bytes`` what a surface must hold, ``check_surface`` / ``surface_table`` the host checks and the table of addresses,
-``yuv_matrix(..., bits=10)`` the matrix of p010's texels, ``frames_crop(..., surfaces=[...])`` the launch, ``frames_crop_yuv420_host``
-its rule in numpy -- the NV12 rule behind another texel fetch -- and ``rgb_to_yuv420_host`` an encoder for the tools and tests."""
-import collections
-
+surfaces=True, frame_format="nv21" | "yuv420p" | "p010")): ``check_surface`` / ``surface_table`` are the host checks and the table of
+addresses, ``frames_crop(..., surfaces=[...])`` the launch, ``frames_crop_yuv420_host`` its rule in numpy -- the NV12 rule behind
+another texel fetch (frame_formats.py: the plane descriptor ``Yuv420Layout`` and what builds and checks one)."""
 import numpy as np
 
+from .frame_formats import (FRAME_FORMATS, Yuv420Layout, check_frame_format, check_nv12_layout, check_yuv420_layout,  # noqa: F401
+                            chroma_siting_code, csc12, frame_layout_of, frames_layout_struct, nv12_layout, rgb_to_nv12_host,
+                            rgb_to_yuv420_host, surface_bytes, yuv420_layout, yuv_matrix)
+
 F = np.float32
-_range = range          # several functions below take a parameter named ``range`` (the YUV range)
+_frames_layout_struct = frames_layout_struct          # the name tests/test_surfaces_host.py imports
 
 
 def box_affine_host(boxes, frame_index, n_frames, size, padding):
@@ -112,171 +112,53 @@ def frames_crop_host(frames, mat, src_frame, size, max_taps=1, mean=MEAN, std=ST
     return _normalise_host(_crop_unit_host(frames, mat, src_frame, size, max_taps), mean, std)
 
 
-def _crop_unit_host(frames, mat, src_frame, size, max_taps=1):
-    """frames_crop_host stopped in front of Normalize: the pixels' c in 0..1, fp32 [b][3][h][w]."""
-    frames = np.asarray(frames)
-    n, hs, ws = frames.shape[:3]
+def _tap_loop_host(sample_of, mat, src_frame, size, max_taps, dtype=np.float32):
+    """The tap loop of every host crop, stopped in front of Normalize: the pixels' c in 0..1, [b][3][h][w] of ``dtype``, every operation
+    in it.  ``sample_of(f)`` gives frame f's sample, a callable (fx, fy) -> [3][h][w] on 0..255, or None where the slot's frame number
+    names no frame: an empty slot, black."""
+    T = np.dtype(dtype).type
     h, w = int(size[0]), int(size[1])
     mat = np.asarray(mat, np.float32).reshape(-1, 6)
     src = np.asarray(src_frame, np.int32).reshape(-1)
     taps = crop_taps_host(mat, max_taps)
-    oy, ox = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
-    out = np.empty((len(src), 3, h, w), np.float32)
+    oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
+    out = np.empty((len(src), 3, h, w), dtype)
     for s in range(len(src)):
-        acc = np.zeros((3, h, w), np.float32)
+        acc = np.zeros((3, h, w), dtype)
         kx, ky = int(taps[s, 0]), int(taps[s, 1])
-        if 0 <= src[s] < n:
-            m0, m1, m2, m3, m4, m5 = mat[s]
-            img = np.transpose(frames[src[s]].astype(np.float32), (2, 0, 1))
+        sample = sample_of(int(src[s]))
+        if sample is not None:
+            m0, m1, m2, m3, m4, m5 = mat[s].astype(dtype)
             with np.errstate(all="ignore"):
                 for j in range(ky):
-                    uy = oy + F(2 * j + 1 - ky) / F(2 * ky)
+                    uy = oy + T(2 * j + 1 - ky) / T(2 * ky)
                     for i in range(kx):
-                        ux = ox + F(2 * i + 1 - kx) / F(2 * kx)
-                        acc += _sample_host(img, hs, ws, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5)[0]
+                        ux = ox + T(2 * i + 1 - kx) / T(2 * kx)
+                        acc += sample((m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5)
         else:
             kx = ky = 1
-        out[s] = (acc * (F(1) / F(kx * ky))) * (F(1) / F(255))
+        out[s] = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
     return out
 
 
-_YUV_K = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb)
-_YUV_RANGE = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16.0), "full": (1.0, 1.0, 0.0)}          # (luma scale, chroma scale, luma offset)
-_SITING = {"left": 0, "center": 1}
-
-
-def _yuv_matrix64(standard, range, bits=8):
-    if not (isinstance(standard, str) and isinstance(range, str)) or standard not in _YUV_K or range not in _YUV_RANGE:
-        raise ValueError(f"yuv_matrix: standard is one of {sorted(_YUV_K)} and range one of {sorted(_YUV_RANGE)}, not {standard!r} / {range!r}")
-    if isinstance(bits, bool) or bits not in (8, 10):
-        raise ValueError(f"yuv_matrix: bits is 8 or 10, not {bits!r}")
-    kr, kb = _YUV_K[standard]
-    kg = 1.0 - kr - kb
-    ys, cs, o0 = _YUV_RANGE[range]
-    k = np.array([[ys, 0.0, 2 * (1 - kr) * cs], [ys, -2 * (1 - kb) * kb / kg * cs, -2 * (1 - kr) * kr / kg * cs], [ys, 2 * (1 - kb) * cs, 0.0]])
-    if bits == 10 and range == "full":                                 # 0..1023 on the v/4 scale is 0..255.75
-        k = k * (255.0 / 255.75)
-    return k, np.array([o0, 128.0, 128.0])
-
-
-def yuv_matrix(standard="bt709", range="limited", bits=8):
-    """float32 [12] = k[3][3] row-major then o[3], lh_frames_crop_yuv_to_nhwc4's csc12: rgb = k (yuv - o) on 8-bit values, for the
-    luma coefficients of ``standard`` ("bt601": Kr, Kb = 0.299, 0.114; "bt709": 0.2126, 0.0722; Kg = 1 - Kr - Kb) and ``range``
-    ("limited": Y in 16..235, CbCr in 16..240; "full": 0..255).  Computed in fp64 and rounded once.  ``bits=10``: for 10-bit samples on
-    the v/4 scale a p010 texel has -- "limited" is the 8-bit matrix unchanged (64..940 is 4 x 16..235), "full" the 8-bit full-range
-    matrix times 255/255.75 with offsets (0, 128, 128)."""
-    k, o = _yuv_matrix64(standard, range, bits)
-    return np.concatenate([k.ravel(), o]).astype(np.float32)
-
-
-def chroma_siting_code(chroma_siting):
-    """"left" (chroma co-sited with the even luma columns: H.264 / HEVC) -> 0, "center" (between them: JPEG / MPEG-1) -> 1."""
-    if not isinstance(chroma_siting, str) or chroma_siting not in _SITING:
-        raise ValueError(f"chroma_siting is 'left' or 'center', not {chroma_siting!r}")
-    return _SITING[chroma_siting]
-
-
-def _csc12(yuv, bits=8):
-    """yuv = (standard, range) or 12 numbers -> float32 [12]; ``bits`` is the samples' (10: p010), for the (standard, range) form."""
-    if isinstance(yuv, (tuple, list)) and len(yuv) == 2 and all(isinstance(v, str) for v in yuv):
-        return yuv_matrix(*yuv, bits=bits)
-    if isinstance(yuv, str):
-        raise ValueError(f"yuv is (standard, range) or 12 coefficients, not {yuv!r}")
-    try:
-        csc = np.asarray(yuv, np.float32).reshape(-1)
-    except (TypeError, ValueError):
-        csc = np.zeros(0, np.float32)
-    if csc.shape != (12,) or not np.isfinite(csc).all():
-        raise ValueError(f"yuv is (standard, range) or 12 finite coefficients (k[3][3] row-major, then o[3]), not {yuv!r}")
-    return csc
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
-def nv12_layout(hs, ws, pitch=None, luma_rows=None):
-    """The NV12 buffer of hs x ws frames -> (pitch, uv_offset, frame_stride, rows): uint8 [n][rows][pitch] per frame, ``luma_rows``
-    (>= hs, default hs) rows of luma on a row pitch of ``pitch`` (>= ws, default ws) bytes, then hs/2 rows of interleaved CbCr on the
-    same pitch: uv_offset = pitch * luma_rows, rows = luma_rows + hs/2, frame_stride = pitch * rows.  The defaults are the tight layout
-    (ws, hs*ws, hs*ws*3/2, hs*3/2); a decoder's surface passes its pitch and its aligned height."""
-    pitch = ws if pitch is None else pitch
-    luma_rows = hs if luma_rows is None else luma_rows
-    if not all(_is_int(v) for v in (hs, ws, pitch, luma_rows)) or hs < 2 or ws < 2 or hs % 2 or ws % 2:
-        raise ValueError(f"nv12_layout: NV12 frames have even integer sides >= 2, not {hs!r} x {ws!r} (pitch {pitch!r}, luma_rows {luma_rows!r})")
-    if pitch < ws or luma_rows < hs:
-        raise ValueError(f"nv12_layout: pitch {pitch} / luma_rows {luma_rows} are below the frame's {ws} / {hs}")
-    rows = int(luma_rows) + int(hs) // 2
-    if int(pitch) * rows >= 1 << 31:
-        raise ValueError(f"nv12_layout: a frame of {rows} rows of {pitch} bytes does not fit 32-bit byte indices")
-    return int(pitch), int(pitch) * int(luma_rows), int(pitch) * rows, rows
-
-
-def _check_layout(hs, ws, layout):
-    """layout = None (tight) or nv12_layout's tuple for hs x ws frames -> the tuple."""
-    if layout is None:
-        return nv12_layout(hs, ws)
-    ok = isinstance(layout, (tuple, list)) and len(layout) == 4 and all(_is_int(v) for v in layout)
-    if not ok or tuple(layout) != nv12_layout(hs, ws, layout[0], layout[3] - hs // 2):
-        raise ValueError(f"frame layout must be topdown.nv12_layout({hs}, {ws}, pitch, luma_rows)'s (pitch, uv_offset, frame_stride, rows), "
-                         f"not {layout!r}")
-    return tuple(int(v) for v in layout)
-
-
-def rgb_to_nv12_host(frames_rgb, standard="bt709", range="limited", layout=None):
-    """uint8 RGB frames [n][hs][ws][3] (even hs, ws) -> uint8 NV12 [n][rows][pitch] in ``layout`` (nv12_layout's tuple; None: tight),
-    what an encoder of ``standard`` / ``range`` followed by a decoder would hand over: yuv = k^-1 rgb + o of yuv_matrix's fp64 matrix,
-    Y = rint per pixel, Cb and Cr = rint of the mean over each 2 x 2 block, clipped to 0..255.  The bytes between the planes and beside
-    the rows are 0.  For the tools and the tests."""
-    frames = np.asarray(frames_rgb)
-    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
-        raise ValueError(f"rgb_to_nv12_host: frames uint8 [n][hs][ws][3], not {frames.shape} {frames.dtype}")
+def _crop_unit_host(frames, mat, src_frame, size, max_taps=1):
+    """frames_crop_host stopped in front of Normalize: the pixels' c in 0..1, fp32 [b][3][h][w]."""
+    frames = np.asarray(frames)
     n, hs, ws = frames.shape[:3]
-    pitch, uv_offset, _, rows = _check_layout(hs, ws, layout)
-    k, o = _yuv_matrix64(standard, range)
-    yuv = frames.astype(np.float64) @ np.linalg.inv(k).T + o
-    out = np.zeros((n, rows, pitch), np.uint8)
-    out[:, :hs, :ws] = np.clip(np.rint(yuv[..., 0]), 0, 255).astype(np.uint8)
-    chroma = yuv[..., 1:].reshape(n, hs // 2, 2, ws // 2, 2, 2).mean((2, 4))
-    out[:, uv_offset // pitch:, :ws] = np.clip(np.rint(chroma), 0, 255).astype(np.uint8).reshape(n, hs // 2, ws)
-    return out
 
-
-def _sample_nv12_host(flat, hs, ws, pitch, uv_offset, siting, k, o, fx, fy, T):
-    """One sample per element of fx / fy of one NV12 frame (``flat``: its bytes as type T), lh_frames_crop_yuv_to_nhwc4's: -> (RGB on
-    0..255, type T [3][...], inside mask); outside the frame (NaN included) the sample is 0."""
-    with np.errstate(all="ignore"):
-        inside = (fx >= T(-0.5)) & (fx <= T(ws) - T(0.5)) & (fy >= T(-0.5)) & (fy <= T(hs) - T(0.5))
-    cy = np.where(inside, np.maximum(fy, T(0)), T(0)).astype(T)
-    cx = np.where(inside, np.maximum(fx, T(0)), T(0)).astype(T)
-
-    def blend(at, x0, x1, y0, y1, wx, wy):
-        a00, a01, a10, a11 = flat[at(x0, y0)], flat[at(x1, y0)], flat[at(x0, y1)], flat[at(x1, y1)]
-        top, bot = a00 + (a01 - a00) * wx, a10 + (a11 - a10) * wx
-        return top + (bot - top) * wy
-
-    y0, x0 = np.minimum(cy.astype(np.int32), hs - 1), np.minimum(cx.astype(np.int32), ws - 1)
-    y1, x1 = np.minimum(y0 + 1, hs - 1), np.minimum(x0 + 1, ws - 1)
-    lum = blend(lambda x, y: y * pitch + x, x0, x1, y0, y1, cx - x0.astype(T), cy - y0.astype(T))
-    hc, wc = hs // 2, ws // 2
-    gx = cx * T(0.5) if siting == 0 else (cx - T(0.5)) * T(0.5)
-    gy = (cy - T(0.5)) * T(0.5)
-    gx, gy = np.minimum(np.maximum(gx, T(0)), T(wc - 1)), np.minimum(np.maximum(gy, T(0)), T(hc - 1))
-    v0, u0 = np.minimum(gy.astype(np.int32), hc - 1), np.minimum(gx.astype(np.int32), wc - 1)
-    v1, u1 = np.minimum(v0 + 1, hc - 1), np.minimum(u0 + 1, wc - 1)
-    wx, wy = gx - u0.astype(T), gy - v0.astype(T)
-    cb = blend(lambda x, y: uv_offset + y * pitch + 2 * x, u0, u1, v0, v1, wx, wy)
-    cr = blend(lambda x, y: uv_offset + y * pitch + 2 * x + 1, u0, u1, v0, v1, wx, wy)
-    e0, e1, e2 = lum - o[0], cb - o[1], cr - o[2]
-    rgb = np.stack([np.minimum(np.maximum((k[c, 0] * e0 + k[c, 1] * e1) + k[c, 2] * e2, T(0)), T(255)) for c in (0, 1, 2)])
-    return np.where(inside, rgb, T(0)).astype(T), inside
+    def sample_of(f):
+        if not 0 <= f < n:
+            return None
+        img = np.transpose(frames[f].astype(np.float32), (2, 0, 1))
+        return lambda fx, fy: _sample_host(img, hs, ws, fx, fy)[0]
+    return _tap_loop_host(sample_of, mat, src_frame, size, max_taps)
 
 
 def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("bt709", "limited"), chroma_siting="left", max_taps=1,
                           layout=None, mean=MEAN, std=STD, dtype=np.float32):
     """uint8 NV12 frames [n][rows][pitch] of ``frame_size`` = (hs, ws) in ``layout`` (nv12_layout's tuple; None: tight), mat [b][6],
     src_frame [b], size = (h, w) of the crop -> normalised [b][3][h][w]; lh_frames_crop_yuv_to_nhwc4 in numpy, fp32 in the kernel's order:
-    frames_crop_host's tap loop with the NV12 sample (csrc/topdown.hip's header comment) in the RGB one's place.  ``yuv`` is
+    frames_crop_host's tap loop with the NV12 sample (the rule: csrc/frames_crop_kernel.h, above crop_sample_nv12) in the RGB one's place.  ``yuv`` is
     (standard, range) or the 12 coefficients, ``chroma_siting`` "left" or "center".  ``dtype=np.float64``: the same operations in fp64
     on the same fp32 matrices and coefficients (the tap counts stay crop_taps_host's) -- what the fp32 order is measured against."""
     return _normalise_host(_crop_unit_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv, chroma_siting, max_taps, layout, dtype),
@@ -286,208 +168,34 @@ def frames_crop_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("b
 def _crop_unit_nv12_host(frames_nv12, frame_size, mat, src_frame, size, yuv=("bt709", "limited"), chroma_siting="left", max_taps=1,
                          layout=None, dtype=np.float32):
     """frames_crop_nv12_host stopped in front of Normalize: the pixels' c in 0..1, [b][3][h][w] of ``dtype``."""
-    T = np.dtype(dtype).type
     hs, ws = int(frame_size[0]), int(frame_size[1])
-    pitch, uv_offset, frame_stride, rows = _check_layout(hs, ws, layout)
+    pitch, _, _, rows = check_nv12_layout(hs, ws, layout)
     frames = np.asarray(frames_nv12)
     if frames.dtype != np.uint8 or frames.ndim != 3 or frames.shape[1:] != (rows, pitch):
         raise ValueError(f"frames_crop_nv12_host: frames uint8 [n][{rows}][{pitch}], not {frames.shape} {frames.dtype}")
-    n = frames.shape[0]
-    h, w = int(size[0]), int(size[1])
-    csc = _csc12(yuv).astype(dtype)
+    # the same bytes through the plane descriptor: c_pitch = pitch, cb_offset = uv_offset, cr_offset = uv_offset + 1, c_step = 2
+    L = yuv420_layout("nv12", hs, ws, pitch, rows - hs // 2)
+    return _crop_unit_420_host([f.reshape(-1) for f in frames], L, mat, src_frame, size, yuv, chroma_siting, max_taps, dtype)
+
+
+def _crop_unit_420_host(frames, L, mat, src_frame, size, yuv, chroma_siting, max_taps, dtype):
+    """The tap loop on 4:2:0 frames: ``frames`` a list of flat uint8 arrays (None: an unbound surface, an empty slot) in the layout L."""
+    T = np.dtype(dtype).type
+    csc = csc12(yuv, 10 if L.code == 4 else 8).astype(dtype)
     k, o = csc[:9].reshape(3, 3), csc[9:]
     siting = chroma_siting_code(chroma_siting)
-    mat = np.asarray(mat, np.float32).reshape(-1, 6)
-    src = np.asarray(src_frame, np.int32).reshape(-1)
-    taps = crop_taps_host(mat, max_taps)
-    oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
-    out = np.empty((len(src), 3, h, w), dtype)
-    for s in range(len(src)):
-        acc = np.zeros((3, h, w), dtype)
-        kx, ky = int(taps[s, 0]), int(taps[s, 1])
-        if 0 <= src[s] < n:
-            m0, m1, m2, m3, m4, m5 = mat[s].astype(dtype)
-            flat = frames[src[s]].reshape(-1).astype(dtype)
-            with np.errstate(all="ignore"):
-                for j in range(ky):
-                    uy = oy + T(2 * j + 1 - ky) / T(2 * ky)
-                    for i in range(kx):
-                        ux = ox + T(2 * i + 1 - kx) / T(2 * kx)
-                        acc += _sample_nv12_host(flat, hs, ws, pitch, uv_offset, siting, k, o, (m0 * ux + m1 * uy) + m2,
-                                                 (m3 * ux + m4 * uy) + m5, T)[0]
-        else:
-            kx = ky = 1
-        out[s] = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
-    return out
 
-
-# ---- decoder surfaces and the 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4): one plane descriptor for nv12 / nv21 / yuv420p / p010
-FRAME_FORMATS = ("rgb", "nv12", "nv21", "yuv420p", "p010")          # the decoders' own pixel-format names
-_FMT_CODE = {"rgb": 0, "nv12": 1, "nv21": 2, "yuv420p": 3, "p010": 4}          # LH_FRAMES_FMT_* of the header
-
-Yuv420Layout = collections.namedtuple("Yuv420Layout", "code sample_bytes shift pitch c_pitch cb_offset cr_offset c_step frame_bytes hs ws")
-Yuv420Layout.__doc__ = """Where the samples of one hs x ws frame are, from its first byte (yuv420_layout builds it): ``code`` the format
-(LH_FRAMES_FMT_*), ``sample_bytes`` 1 or 2 (little-endian), ``shift`` the low bits of a sample that are not data (6 for p010: the
-texel is (u16 >> 6) * 0.25), luma (x, y) at y*pitch + x*sample_bytes, Cb / Cr of chroma sample (cx, cy) at cb_offset / cr_offset +
-cy*c_pitch + cx*c_step, ``frame_bytes`` what one frame occupies."""
-
-
-def check_frame_format(frame_format):
-    if not isinstance(frame_format, str) or frame_format not in FRAME_FORMATS:
-        raise ValueError(f"frame_format is one of {', '.join(repr(f) for f in FRAME_FORMATS)}, not {frame_format!r}")
-    return frame_format
-
-
-def _plane_ends(L):
-    """(luma end, one chroma plane's extent from its offset) of a Yuv420Layout: the closed forms surface_bytes and the checks share."""
-    hc, wc = L.hs // 2, L.ws // 2
-    luma = (L.hs - 1) * L.pitch + L.ws * L.sample_bytes
-    plane = (hc - 1) * L.c_pitch + (wc if L.code == 3 else (wc - 1) * L.c_step + L.sample_bytes)
-    return luma, plane
-
-
-def check_yuv420_layout(layout, hs=None, ws=None, frame_format=None):
-    """A Yuv420Layout (yuv420_layout's, or one edited with ``_replace``: yuv420p with cb_offset and cr_offset swapped is YV12) ->
-    the layout, or ValueError: what lh_frames_crop_surfaces_to_nhwc4 refuses, and a layout of another size or format than asked for."""
-    L = layout
-    if not isinstance(L, Yuv420Layout) or not all(_is_int(v) for v in L) or L.code not in (1, 2, 3, 4):
-        raise ValueError(f"frame layout must be topdown.yuv420_layout(...)'s named tuple, not {layout!r}")
-    name = FRAME_FORMATS[L.code]
-    if frame_format is not None and name != frame_format:
-        raise ValueError(f"frame layout is a {name!r} layout, the frames are {frame_format!r}")
-    if (hs is not None and L.hs != hs) or (ws is not None and L.ws != ws):
-        raise ValueError(f"frame layout describes {L.hs} x {L.ws} frames, not {hs} x {ws}")
-    sb = 2 if L.code == 4 else 1
-    if L.hs < 2 or L.ws < 2 or L.hs % 2 or L.ws % 2:
-        raise ValueError(f"yuv420_layout: 4:2:0 frames have even integer sides >= 2, not {L.hs!r} x {L.ws!r}")
-    if L.sample_bytes != sb or L.shift != (6 if sb == 2 else 0) or L.c_step != (1 if L.code == 3 else 2 * sb):
-        raise ValueError(f"yuv420_layout: {name} has sample_bytes {sb}, shift {6 if sb == 2 else 0} and c_step {1 if L.code == 3 else 2 * sb}, not "
-                         f"{L.sample_bytes} / {L.shift} / {L.c_step}")
-    wc = L.ws // 2
-    if L.pitch < L.ws * sb or L.c_pitch < (wc if L.code == 3 else wc * 2 * sb):
-        raise ValueError(f"yuv420_layout: pitch {L.pitch} / c_pitch {L.c_pitch} are below a row's bytes ({L.ws * sb} luma, "
-                         f"{wc if L.code == 3 else wc * 2 * sb} chroma)")
-    if sb == 2 and (L.pitch % 2 or L.c_pitch % 2 or L.cb_offset % 2 or L.cr_offset % 2):
-        raise ValueError(f"yuv420_layout: p010 samples are 16-bit: pitch {L.pitch}, c_pitch {L.c_pitch} and the offsets must be even")
-    delta = {1: 1, 2: -1, 4: 2}.get(L.code)
-    if delta is not None and L.cr_offset - L.cb_offset != delta:
-        raise ValueError(f"yuv420_layout: {name} has cr_offset - cb_offset = {delta}, not {L.cr_offset - L.cb_offset}")
-    luma, plane = _plane_ends(L)
-    lo, hi = min(L.cb_offset, L.cr_offset), max(L.cb_offset, L.cr_offset)
-    if lo < luma or (L.code == 3 and hi < lo + plane):
-        raise ValueError(f"yuv420_layout: the planes overlap (luma ends at byte {luma}, cb_offset {L.cb_offset}, cr_offset {L.cr_offset}, "
-                         f"{plane} bytes a chroma plane)")
-    if L.frame_bytes < hi + plane or L.frame_bytes >= 1 << 31:
-        raise ValueError(f"yuv420_layout: a frame of {L.frame_bytes} bytes does not hold its planes (they end at byte {hi + plane}) or does "
-                         f"not fit 32-bit byte indices")
-    return L
-
-
-def yuv420_layout(frame_format, hs, ws, pitch=None, luma_rows=None, chroma_pitch=None):
-    """The layout of hs x ws frames of ``frame_format`` ("nv12", "nv21", "yuv420p", "p010") as a Yuv420Layout: ``luma_rows`` (>= hs,
-    default hs) rows of luma on a row pitch of ``pitch`` bytes (default: the row's own bytes), then the chroma: hs/2 rows of
-    interleaved pairs on ``chroma_pitch`` (default ``pitch``) for nv12 (Cb first), nv21 (Cr first) and p010 (16-bit samples, Cb
-    first), or a Cb plane and then a Cr plane of hs/2 rows on ``chroma_pitch`` (default pitch/2, rounded up) for yuv420p.  The defaults
-    are the tight layout; a decoder's surface passes its pitch and aligned height.  (YV12 is yuv420p with the two offsets swapped:
-    ``layout._replace(cb_offset=layout.cr_offset, cr_offset=layout.cb_offset)``.)"""
-    if not isinstance(frame_format, str) or frame_format not in FRAME_FORMATS[1:]:
-        raise ValueError(f"yuv420_layout: frame_format is one of {FRAME_FORMATS[1:]}, not {frame_format!r}")
-    code = _FMT_CODE[frame_format]
-    sb = 2 if code == 4 else 1
-    if not all(_is_int(v) for v in (hs, ws)) or hs < 2 or ws < 2 or hs % 2 or ws % 2:
-        raise ValueError(f"yuv420_layout: 4:2:0 frames have even integer sides >= 2, not {hs!r} x {ws!r}")
-    pitch = ws * sb if pitch is None else pitch
-    luma_rows = hs if luma_rows is None else luma_rows
-    chroma_pitch = ((pitch + 1) // 2 if code == 3 else pitch) if chroma_pitch is None and _is_int(pitch) else chroma_pitch
-    if not all(_is_int(v) for v in (pitch, luma_rows, chroma_pitch)):
-        raise ValueError(f"yuv420_layout: pitch, luma_rows and chroma_pitch are integers, not {pitch!r} / {luma_rows!r} / {chroma_pitch!r}")
-    hc = hs // 2
-    cb = pitch * luma_rows
-    if code == 3:
-        cr, frame_bytes = cb + chroma_pitch * hc, cb + 2 * chroma_pitch * hc
-    else:
-        cb, cr = (cb + 1, cb) if code == 2 else (cb, cb + sb)
-        frame_bytes = pitch * luma_rows + chroma_pitch * hc
-    return check_yuv420_layout(Yuv420Layout(code, sb, 6 if sb == 2 else 0, int(pitch), int(chroma_pitch), int(cb), int(cr),
-                                            1 if code == 3 else 2 * sb, int(frame_bytes), int(hs), int(ws)))
-
-
-def _rgb_layout(hs, ws):
-    if hs * ws * 3 >= 1 << 31:
-        raise ValueError(f"a packed RGB frame of {hs} x {ws} does not fit 32-bit byte indices")
-    return Yuv420Layout(0, 1, 0, ws * 3, 0, 0, 0, 0, hs * ws * 3, int(hs), int(ws))
-
-
-def frame_layout_of(frame_format, hs, ws, layout=None):
-    """The Yuv420Layout a step or a launch uses for hs x ws frames of ``frame_format``: ``layout`` None is the tight one; "nv12" also
-    takes nv12_layout's 4-tuple; "rgb" has no layout to pass (packed [hs][ws][3])."""
-    check_frame_format(frame_format)
-    if frame_format == "rgb":
-        if layout is not None:
-            raise ValueError(f"frame_layout={layout!r} describes 4:2:0 frames: packed RGB frames have none")
-        return _rgb_layout(hs, ws)
-    if frame_format == "nv12" and not isinstance(layout, Yuv420Layout):          # nv12_layout's rules and error texts, as they were
-        pitch, _, _, rows = _check_layout(hs, ws, layout)
-        return yuv420_layout("nv12", hs, ws, pitch, rows - hs // 2)
-    if layout is None:
-        return yuv420_layout(frame_format, hs, ws)
-    return check_yuv420_layout(layout, hs, ws, frame_format)
-
-
-def surface_bytes(layout):
-    """The bytes a surface of ``layout`` (a Yuv420Layout) must hold: the highest byte a sample can touch, plus one."""
-    if isinstance(layout, Yuv420Layout) and layout.code == 0:
-        return layout.frame_bytes
-    L = check_yuv420_layout(layout)
-    return max(L.cb_offset, L.cr_offset) + _plane_ends(L)[1]
-
-
-def _frames_layout_struct(L, yuv, chroma_siting):
-    """The lh_frames_layout of a Yuv420Layout (``yuv`` and ``chroma_siting`` as frames_crop's)."""
-    from . import _lib
-    s = _lib.FramesLayout()
-    s.format = L.code
-    if L.code:
-        s.pitch, s.c_pitch, s.cb_offset, s.cr_offset, s.frame_bytes = L.pitch, L.c_pitch, L.cb_offset, L.cr_offset, L.frame_bytes
-        s.chroma_siting = chroma_siting_code(chroma_siting)
-        s.csc12[:] = _csc12(yuv, 10 if L.code == 4 else 8).tolist()
-    return s
-
-
-def rgb_to_yuv420_host(frames_rgb, frame_format="nv12", standard="bt709", range="limited", layout=None):
-    """uint8 RGB frames [n][hs][ws][3] (even hs, ws) -> the frames as ``frame_format`` in ``layout``, uint8 [n][frame_bytes] (for
-    "nv12" with ``layout`` None or nv12_layout's tuple: rgb_to_nv12_host's array, [n][rows][pitch]): rgb_to_nv12_host's rounding --
-    Y = rint per pixel, Cb and Cr = rint of the mean over each 2 x 2 block, clipped -- laid out through the plane descriptor.  "p010"
-    rounds to 10 bits (the code value is 4 x the 8-bit scale's through yuv_matrix(..., bits=10)) and stores them shifted left by 6,
-    little-endian.  The bytes between the planes and beside the rows are 0.  For the tools and the tests."""
-    check_frame_format(frame_format)
-    if frame_format == "nv12" and not isinstance(layout, Yuv420Layout):
-        return rgb_to_nv12_host(frames_rgb, standard, range, layout)
-    frames = np.asarray(frames_rgb)
-    if frame_format == "rgb" or frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
-        raise ValueError(f"rgb_to_yuv420_host: frames uint8 [n][hs][ws][3] to a 4:2:0 format, not {frames.shape} {frames.dtype} to {frame_format!r}")
-    n, hs, ws = frames.shape[:3]
-    L = frame_layout_of(frame_format, hs, ws, layout)
-    bits = 10 if L.code == 4 else 8
-    k, o = _yuv_matrix64(standard, range, bits)
-    yuv = frames.astype(np.float64) @ np.linalg.inv(k).T + o
-    scale, top = (4.0, 1023) if bits == 10 else (1.0, 255)
-    luma = np.clip(np.rint(yuv[..., 0] * scale), 0, top).astype(np.int64) << L.shift
-    chroma = np.clip(np.rint(yuv[..., 1:].reshape(n, hs // 2, 2, ws // 2, 2, 2).mean((2, 4)) * scale), 0, top).astype(np.int64) << L.shift
-    out = np.zeros((n, L.frame_bytes), np.uint8)
-    y, x = np.meshgrid(np.arange(hs), np.arange(ws), indexing="ij")
-    cy, cx = np.meshgrid(np.arange(hs // 2), np.arange(ws // 2), indexing="ij")
-    for byte in _range(L.sample_bytes):                    # little-endian
-        out[:, y * L.pitch + x * L.sample_bytes + byte] = (luma >> (8 * byte)) & 255
-        out[:, L.cb_offset + cy * L.c_pitch + cx * L.c_step + byte] = (chroma[..., 0] >> (8 * byte)) & 255
-        out[:, L.cr_offset + cy * L.c_pitch + cx * L.c_step + byte] = (chroma[..., 1] >> (8 * byte)) & 255
-    return out
+    def sample_of(f):
+        if not 0 <= f < len(frames) or frames[f] is None:
+            return None
+        return lambda fx, fy: _sample_420_host(frames[f], L, siting, k, o, fx, fy, T)[0]
+    return _tap_loop_host(sample_of, mat, src_frame, size, max_taps, dtype)
 
 
 def _sample_420_host(flat, L, siting, k, o, fx, fy, T):
-    """One sample per element of fx / fy of one frame (``flat``: its bytes, uint8) through the plane descriptor ``L``,
-    lh_frames_crop_surfaces_to_nhwc4's: _sample_nv12_host's operations in its order, the texel fetch apart -> (RGB on 0..255, type T
-    [3][...], inside mask)."""
+    """One sample per element of fx / fy of one 4:2:0 frame (``flat``: its bytes, uint8) through the plane descriptor ``L``,
+    lh_frames_crop_surfaces_to_nhwc4's and, for an NV12 buffer, lh_frames_crop_yuv_to_nhwc4's -> (RGB on 0..255, type T [3][...], inside
+    mask); outside the frame (NaN included) the sample is 0."""
     hs, ws = L.hs, L.ws
     with np.errstate(all="ignore"):
         inside = (fx >= T(-0.5)) & (fx <= T(ws) - T(0.5)) & (fy >= T(-0.5)) & (fy <= T(hs) - T(0.5))
@@ -540,39 +248,16 @@ def _frame_bytes_host(frames_or_surfaces, need, who):
 def _crop_unit_yuv420_host(frames_or_surfaces, frame_size, mat, src_frame, size, frame_format="nv12", layout=None, yuv=("bt709", "limited"),
                            chroma_siting="left", max_taps=1, dtype=np.float32):
     """frames_crop_yuv420_host stopped in front of Normalize: the pixels' c in 0..1, [b][3][h][w] of ``dtype``."""
-    T = np.dtype(dtype).type
     hs, ws = int(frame_size[0]), int(frame_size[1])
     L = frame_layout_of(frame_format, hs, ws, layout)
     frames = _frame_bytes_host(frames_or_surfaces, surface_bytes(L), "frames_crop_yuv420_host")
     n = len(frames)
-    h, w = int(size[0]), int(size[1])
-    mat = np.asarray(mat, np.float32).reshape(-1, 6)
-    src = np.asarray(src_frame, np.int32).reshape(-1)
     if L.code == 0:                                                # packed RGB surfaces: the RGB rule, an unbound surface is an empty slot
+        src = np.asarray(src_frame, np.int32).reshape(-1)
         live = np.array([0 <= s < n and frames[s] is not None for s in src])
         rgb = np.stack([np.zeros(hs * ws * 3, np.uint8) if f is None else f[:hs * ws * 3] for f in frames]).reshape(n, hs, ws, 3)
         return _crop_unit_host(rgb, mat, np.where(live, src, -1), size, max_taps).astype(dtype)
-    csc = _csc12(yuv, 10 if L.code == 4 else 8).astype(dtype)
-    k, o = csc[:9].reshape(3, 3), csc[9:]
-    siting = chroma_siting_code(chroma_siting)
-    taps = crop_taps_host(mat, max_taps)
-    oy, ox = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
-    out = np.empty((len(src), 3, h, w), dtype)
-    for s in _range(len(src)):
-        acc = np.zeros((3, h, w), dtype)
-        kx, ky = int(taps[s, 0]), int(taps[s, 1])
-        if 0 <= src[s] < n and frames[src[s]] is not None:
-            m0, m1, m2, m3, m4, m5 = mat[s].astype(dtype)
-            with np.errstate(all="ignore"):
-                for j in _range(ky):
-                    uy = oy + T(2 * j + 1 - ky) / T(2 * ky)
-                    for i in _range(kx):
-                        ux = ox + T(2 * i + 1 - kx) / T(2 * kx)
-                        acc += _sample_420_host(frames[src[s]], L, siting, k, o, (m0 * ux + m1 * uy) + m2, (m3 * ux + m4 * uy) + m5, T)[0]
-        else:
-            kx = ky = 1
-        out[s] = (acc * (T(1) / T(kx * ky))) * (T(1) / T(255))
-    return out
+    return _crop_unit_420_host(frames, L, mat, src_frame, size, yuv, chroma_siting, max_taps, dtype)
 
 
 def frames_crop_yuv420_host(frames_or_surfaces, frame_size, mat, src_frame, size, frame_format="nv12", layout=None, yuv=("bt709", "limited"),
@@ -930,6 +615,42 @@ def surface_table(surfaces, layout, device):
     return torch.tensor(addresses, dtype=torch.int64).to(device), [t for t in seq if t is not None]
 
 
+def through_descriptor(frame_format, layout, surfaces):
+    """Whether a crop finds its samples through the plane descriptor (crop_entry's ``desc``): surfaces in place of a frame buffer, the
+    formats only the descriptor covers, or "nv12" with a Yuv420Layout."""
+    return bool(surfaces) or frame_format not in ("rgb", "nv12") or isinstance(layout, Yuv420Layout)
+
+
+def crop_entry(lib, frame_format, max_taps, frames, out, b, n_frames, hs, ws, h, w, pad, wp, m3, s3, mat, src_frame, dtype_code, desc=None,
+               frame_stride=0, table=None, nv12=None, jit=None, plain=False):
+    """Which of the five C crop entries a launch is -> (the function of ``lib``, its arguments without the stream, a description): the
+    choice frames_crop and engine.Plan.use_frame_input share.  Pointers are addresses (or None), m3 / s3 the float[3] of Normalize.
+    The first match wins: ``desc`` (an lh_frames_layout: the descriptor path -- surfaces, nv21 / yuv420p / p010, or a Yuv420Layout;
+    ``frames`` + ``frame_stride`` or ``table`` is its source) -> lh_frames_crop_surfaces_to_nhwc4, with or without jitter; ``jit`` =
+    (factors, order, workspace) -> lh_frames_crop_jitter_to_nhwc4; ``nv12`` = (pitch, uv_offset, frame_stride, siting, csc12) ->
+    lh_frames_crop_yuv_to_nhwc4; ``max_taps`` > 1 -> lh_frames_crop_area_to_nhwc4; otherwise the area entry again, or with ``plain``
+    (the plan's rule) lh_frames_crop_to_nhwc4."""
+    import ctypes as C
+    geometry = (h, w, pad, wp, m3, s3, mat, src_frame)
+    taps = ", antialiased" if max_taps > 1 else ""
+    if desc is not None:
+        return (lib.lh_frames_crop_surfaces_to_nhwc4,
+                (frames, out, frame_stride, table, C.byref(desc), b, n_frames, hs, ws) + geometry + (max_taps,) + (jit or (None, None, None))
+                + (dtype_code,),
+                f"{frame_format} frame crop input pipeline" + (", surface table" if table is not None else "") + taps
+                + (" + ColorJitter" if jit else ""))
+    head = (frames, out, b, n_frames, hs, ws)
+    what = "NV12 frame crop input pipeline" if nv12 else "frame crop input pipeline"
+    if jit:
+        return (lib.lh_frames_crop_jitter_to_nhwc4, head + (nv12 or (0, 0, 0, 0, None)) + geometry + (max_taps,) + jit + (dtype_code,),
+                what + taps + " + ColorJitter")
+    if nv12:
+        return lib.lh_frames_crop_yuv_to_nhwc4, head + nv12 + geometry + (max_taps, dtype_code), what + taps
+    if max_taps > 1 or not plain:
+        return lib.lh_frames_crop_area_to_nhwc4, head + geometry + (max_taps, dtype_code), ("antialiased " if max_taps > 1 else "") + what
+    return lib.lh_frames_crop_to_nhwc4, head + geometry + (dtype_code,), what
+
+
 def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN, std=STD, frame_format="rgb", frame_size=None,
                 yuv=("bt709", "limited"), chroma_siting="left", layout=None, jitter=None, surfaces=None):
     """Device tensors frames uint8 [n][hs][ws][3], mat fp32 [b][6], src_frame int32 [b] -> the normalised crops as NHWC4
@@ -951,10 +672,10 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
         raise ValueError(f"max_taps must be an integer 1..8, not {max_taps!r}")
     check_frame_format(frame_format)
     dtype = dtype or torch.float32
-    through_descriptor = surfaces is not None or frame_format not in ("rgb", "nv12") or isinstance(layout, Yuv420Layout)
+    descriptor = through_descriptor(frame_format, layout, surfaces is not None)
     if (frames is None) == (surfaces is None):
         raise ValueError("frames_crop: pass frames (one buffer) or surfaces= (one tensor per frame), one of the two")
-    if not through_descriptor:
+    if not descriptor:
         frames = frames.contiguous()
     mat = mat.to(torch.float32).contiguous()
     src_frame = src_frame.to(torch.int32).contiguous()
@@ -968,7 +689,9 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
                                       f"{tuple(factors.shape)} {factors.dtype} / {tuple(order.shape)} {order.dtype}")
         ws_j = torch.empty(max(1, _lib.load().lh_frames_crop_jitter_workspace_bytes(b) // 8), dtype=torch.float64, device=mat.device)
         jit = (factors.data_ptr(), order.data_ptr(), ws_j.data_ptr())
-    if through_descriptor:
+    desc = table = nv12 = None
+    frame_stride, keep = 0, ()
+    if descriptor:
         if tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,) or not mat.is_cuda or src_frame.device != mat.device:
             raise _lib.LightHandError(f"frames_crop: mat [b, 6] and src_frame [b] on one device, got {tuple(mat.shape)} / {tuple(src_frame.shape)}")
         if surfaces is None and frame_format == "rgb" and frame_size is None and frames.dim() == 4:
@@ -977,70 +700,42 @@ def frames_crop(frames, mat, src_frame, size, max_taps=1, dtype=None, mean=MEAN,
             raise ValueError(f"frames_crop: frame_size=(hs, ws) is needed, not {frame_size!r}")
         hs, ws = int(frame_size[0]), int(frame_size[1])
         L = frame_layout_of(frame_format, hs, ws, layout)
-        desc = _frames_layout_struct(L, yuv, chroma_siting)
-        keep = None
+        desc = frames_layout_struct(L, yuv, chroma_siting)
+        device = mat.device
         if surfaces is not None:
-            table, keep = surface_table(surfaces, L, mat.device)
-            source, n = (0, table.data_ptr()), table.shape[0]
+            table_dev, keep = surface_table(surfaces, L, device)
+            table, n = table_dev.data_ptr(), table_dev.shape[0]
         else:
             if not frames.is_cuda or frames.device != mat.device or frames.dtype != torch.uint8 or frames.dim() < 2 or not frames.is_contiguous():
                 raise _lib.LightHandError(f"frames_crop: frames contiguous uint8 [n, ...] on the crop's device, got {tuple(frames.shape)} {frames.dtype}")
-            n = frames.shape[0]
-            source = (frames.stride(0), None)
-        h, w = int(size[0]), int(size[1])
-        out = torch.empty(b, h, w, 4, dtype=dtype, device=mat.device)
-        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        with torch.cuda.device(mat.device):
-            _lib.check(_lib.load().lh_frames_crop_surfaces_to_nhwc4(None if surfaces is not None else frames.data_ptr(), out.data_ptr(), *source,
-                                                                    C.byref(desc), b, n, hs, ws, h, w, 0, w, m3, s3,
-                                                                    mat.data_ptr(), src_frame.data_ptr(), max_taps, *(jit or (None, None, None)),
-                                                                    _lib.dtype_code(dtype), _stream()), "lh_frames_crop_surfaces_to_nhwc4")
-        if keep:
-            for t in keep:                                         # the launch is queued: the allocator must not hand the surfaces out before it ran
-                t.record_stream(torch.cuda.current_stream())
-        return out
-    if frame_format == "nv12":
+            n, frame_stride = frames.shape[0], frames.stride(0)
+    elif frame_format == "nv12":
         if not (isinstance(frame_size, (tuple, list)) and len(frame_size) == 2):
             raise ValueError(f"frame_format='nv12' needs frame_size=(hs, ws), not {frame_size!r}")
         hs, ws = int(frame_size[0]), int(frame_size[1])
-        pitch, uv_offset, frame_stride, rows = _check_layout(hs, ws, layout)
-        csc, siting = (C.c_float * 12)(*_csc12(yuv).tolist()), chroma_siting_code(chroma_siting)
+        pitch, uv_offset, stride, rows = check_nv12_layout(hs, ws, layout)
+        nv12 = (pitch, uv_offset, stride, chroma_siting_code(chroma_siting), (C.c_float * 12)(*csc12(yuv).tolist()))
         if (frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (rows, pitch) or frames.dim() != 3 or tuple(mat.shape) != (b, 6)
                 or tuple(src_frame.shape) != (b,) or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
             raise _lib.LightHandError(f"frames_crop: NV12 frames uint8 [n, {rows}, {pitch}], mat [b, 6] and src_frame [b] on one device, got "
                                       f"{tuple(frames.shape)} {frames.dtype} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
-        h, w = int(size[0]), int(size[1])
-        out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
-        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        with torch.cuda.device(frames.device):
-            if jit is not None:
-                _lib.check(_lib.load().lh_frames_crop_jitter_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, frames.shape[0], hs, ws, pitch,
-                                                                      uv_offset, frame_stride, siting, csc, h, w, 0, w, m3, s3, mat.data_ptr(),
-                                                                      src_frame.data_ptr(), max_taps, *jit, _lib.dtype_code(dtype), _stream()),
-                           "lh_frames_crop_jitter_to_nhwc4")
-                return out
-            _lib.check(_lib.load().lh_frames_crop_yuv_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, frames.shape[0], hs, ws, pitch, uv_offset,
-                                                               frame_stride, siting, csc, h, w, 0, w, m3, s3, mat.data_ptr(),
-                                                               src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
-                       "lh_frames_crop_yuv_to_nhwc4")
-        return out
-    if (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,)
-            or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
-        raise _lib.LightHandError(f"frames_crop: frames uint8 [n, hs, ws, 3], mat [b, 6] and src_frame [b] on one device, got "
-                                  f"{tuple(frames.shape)} {frames.dtype} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
-    n, hs, ws = frames.shape[:3]
+        n, device = frames.shape[0], frames.device
+    else:
+        if (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or tuple(mat.shape) != (b, 6) or tuple(src_frame.shape) != (b,)
+                or not frames.is_cuda or mat.device != frames.device or src_frame.device != frames.device):
+            raise _lib.LightHandError(f"frames_crop: frames uint8 [n, hs, ws, 3], mat [b, 6] and src_frame [b] on one device, got "
+                                      f"{tuple(frames.shape)} {frames.dtype} / {tuple(mat.shape)} / {tuple(src_frame.shape)}")
+        (n, hs, ws), device = frames.shape[:3], frames.device
     h, w = int(size[0]), int(size[1])
-    out = torch.empty(b, h, w, 4, dtype=dtype, device=frames.device)
+    out = torch.empty(b, h, w, 4, dtype=dtype, device=device)
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    with torch.cuda.device(frames.device):
-        if jit is not None:
-            _lib.check(_lib.load().lh_frames_crop_jitter_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, n, hs, ws, 0, 0, 0, 0, None, h, w, 0, w, m3,
-                                                                  s3, mat.data_ptr(), src_frame.data_ptr(), max_taps, *jit,
-                                                                  _lib.dtype_code(dtype), _stream()), "lh_frames_crop_jitter_to_nhwc4")
-            return out
-        _lib.check(_lib.load().lh_frames_crop_area_to_nhwc4(frames.data_ptr(), out.data_ptr(), b, n, hs, ws, h, w, 0, w, m3, s3, mat.data_ptr(),
-                                                            src_frame.data_ptr(), max_taps, _lib.dtype_code(dtype), _stream()),
-                   "lh_frames_crop_area_to_nhwc4")
+    fn, args, _ = crop_entry(_lib.load(), frame_format, max_taps, None if surfaces is not None else frames.data_ptr(), out.data_ptr(), b, n, hs, ws,
+                             h, w, 0, w, m3, s3, mat.data_ptr(), src_frame.data_ptr(), _lib.dtype_code(dtype), desc=desc,
+                             frame_stride=frame_stride, table=table, nv12=nv12, jit=jit)
+    with torch.cuda.device(device):
+        _lib.check(fn(*args, _stream()), fn.__name__)
+    for t in keep:                                                 # the launch is queued: the allocator must not hand the surfaces out before it ran
+        t.record_stream(torch.cuda.current_stream())
     return out
 
 

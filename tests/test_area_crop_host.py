@@ -1,5 +1,5 @@
 """CPU: the host side of the antialiased frame crop -- the numpy restatements crop_taps_host / frames_crop_host of
-lighthand_amd.topdown (the sampling rule of lh_frames_crop_area_to_nhwc4: csrc/topdown.hip's header comment) against a hand-written
+lighthand_amd.topdown (the sampling rule of lh_frames_crop_area_to_nhwc4: csrc/frames_crop_kernel.h, above crop_taps) against a hand-written
 table, the exact block mean, the plain crop's reference and a white-noise property; the entry's argument validation and the refusals
 of InferStep / InferPipeline(antialias=) without a GPU.  The kernel is checked against frames_crop_host in tests/test_gpu_area_crop.py."""
 import ctypes as C

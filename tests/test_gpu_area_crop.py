@@ -1,6 +1,6 @@
 """GPU: the antialiased frame crop -- lh_frames_crop_area_to_nhwc4 against lh_frames_crop_to_nhwc4 (one tap: the same bits), the
-exact block mean, the numpy restatement frames_crop_host of lighthand_amd.topdown (the sampling rule: csrc/topdown.hip's header
-comment), and InferStep / InferPipeline(antialias=) and the track_frames tool on top of it.  3 frames of 150 x 210, crop 24 x 40,
+exact block mean, the numpy restatement frames_crop_host of lighthand_amd.topdown (the sampling rule: csrc/frames_crop_kernel.h,
+above crop_taps), and InferStep / InferPipeline(antialias=) and the track_frames tool on top of it.  3 frames of 150 x 210, crop 24 x 40,
 pad 3; 96 x 96 frames for the aligned cases; the tolerance scheme is tests/test_gpu_topdown.py::test_crops_match_the_numpy_sampling_rule's."""
 import ctypes as C
 

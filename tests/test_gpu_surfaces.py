@@ -1,5 +1,5 @@
 """GPU: decoder surfaces and the 4:2:0 flavours of the frame crop -- lh_frames_crop_surfaces_to_nhwc4 against the numpy restatement
-(topdown.frames_crop_yuv420_host; the rule: csrc/topdown.hip's header comment) for rgb / nv12 / nv21 / yuv420p / p010, from a frame
+(topdown.frames_crop_yuv420_host; the rule: csrc/frames_crop_kernel.h, above crop_texel) for rgb / nv12 / nv21 / yuv420p / p010, from a frame
 buffer and through a surface table; separate surfaces against one contiguous buffer; rebinding under one captured graph; the options
 composed; InferPipeline; TrainStep; ColorJitter on a new format; the refusals that need tensors; and the launch lists of steps built
 without the new arguments.  Inputs: tests/surfaces_data.py (3 frames of 36 x 52, crop 24 x 40) and, for the steps, R18 at batch 4 on

@@ -1,6 +1,6 @@
 """GPU: the frame crop on NV12 frames -- lh_frames_crop_yuv_to_nhwc4 against the RGB entries on grey frames (the same bits), a pitched
-surface against the tight layout, the numpy restatement frames_crop_nv12_host of lighthand_amd.topdown (the rule: csrc/topdown.hip's
-header comment), and InferStep / InferPipeline(frame_format="nv12") and the track_frames tool on top of it.  Shapes and slots are
+surface against the tight layout, the numpy restatement frames_crop_nv12_host of lighthand_amd.topdown (the rule: csrc/frames_crop_kernel.h,
+above crop_sample_nv12), and InferStep / InferPipeline(frame_format="nv12") and the track_frames tool on top of it.  Shapes and slots are
 tests/test_gpu_area_crop.py's: 3 frames of 150 x 210, crop 24 x 40, pad 3, 32 slots; so is the tolerance scheme (assert_close)."""
 import ctypes as C
 

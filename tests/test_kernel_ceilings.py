@@ -1,7 +1,7 @@
 """The table in force (tests/golden/kernel_ceilings.json, what tests/test_kernel_resources.py holds every built kernel to) only extends
 the first table, tests/golden/kernel_resources.json, which stays frozen as committed: every entry of the frozen table is in the table in
 force with [scratch bytes, spilled VGPRs] no higher.  A change that adds kernels adds entries; no entry rises.  The kernels of top-down
-inference on full frames (csrc/topdown.hip) are listed, with no scratch memory and no spills.  Reads the two JSON files only: no GPU."""
+inference on full frames (csrc/roi_track.hip, csrc/frames_crop.hip) are listed, with no scratch memory and no spills.  Reads the two JSON files only: no GPU."""
 import importlib.util
 import json
 import os

@@ -284,7 +284,7 @@ def test_entries_are_exported_declared_and_validate_arguments_without_gpu():
 
 
 def test_the_two_entries_add_no_kernel_symbol():
-    """lh_roi_perturb and lh_affine_points_inv run as modes of frames_crop_kernel's fp32 instantiation (csrc/topdown.hip: CropArgs.op):
+    """lh_roi_perturb and lh_affine_points_inv run as modes of frames_crop_kernel's fp32 instantiation (csrc/frames_crop_kernel.h: CropArgs.op):
     the library's kernel symbols are those of the resource table in force, which tests/test_kernel_resources.py holds to [0, 0] scratch
     and spills for that kernel -- the table and tools/kernel_resources.py stay as they are."""
     import importlib.util

@@ -135,6 +135,31 @@ def test_nv12_input_gives_the_nv12_restatement_bit_for_bit(siting, dtype):
     assert not np.array_equal(nv12_reference("left", dtype), nv12_reference("center", dtype))
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("siting", ["left", "center"])
+def test_nv12_restatements_reproduce_the_recorded_crops_bit_for_bit(siting, dtype):
+    """frames_crop_nv12_host and frames_crop_yuv420_host share one sampler, so the test above compares a function with itself; this one
+    holds both to tests/golden/nv12_crop_host.npz, the outputs of frames_crop_nv12_host while it still had a sampler of its own.  The
+    recording (inputs included: ``frames``, ``mat``, ``src``; outputs ``{siting}_{fp32|fp64}_taps{1|4}``): layout = nv12_layout(12,
+    16, 24, 14), frames = RandomState(11).randint(0, 256, (2, 20, 24)) as uint8, c, s = cos, sin of pi / 6, mat fp32 = (1, 0, 2.25, 0,
+    1, 1.5) upright at scale 1, (3, 0, -3.5, 0, 3, -5.5) minified by 3, (c, -s, 9, s, c, -2) turned and partly outside, zeros with
+    src = -1 empty; src = (0, 1, 0, -1); frames_crop_nv12_host(frames, (12, 16), mat, src, (8, 8), chroma_siting=siting, max_taps=taps,
+    layout=layout, dtype=dtype) with the default yuv, mean and std."""
+    from lighthand_amd.topdown import frames_crop_nv12_host, frames_crop_yuv420_host, nv12_layout
+    rec = np.load(os.path.join(ROOT, "tests", "golden", "nv12_crop_host.npz"))
+    layout = nv12_layout(12, 16, 24, 14)
+    frames, mat, src = rec["frames"], rec["mat"], rec["src"]
+    assert frames.shape == (2, layout[3], layout[0]) and frames.dtype == np.uint8 and list(src) == [0, 1, 0, -1]
+    for taps in (1, 4):
+        want = rec[f"{siting}_{'fp32' if dtype is np.float32 else 'fp64'}_taps{taps}"]
+        assert want.dtype == np.dtype(dtype) and want.shape == (4, 3, 8, 8)
+        nv12 = frames_crop_nv12_host(frames, (12, 16), mat, src, (8, 8), chroma_siting=siting, max_taps=taps, layout=layout, dtype=dtype)
+        y420 = frames_crop_yuv420_host(frames, (12, 16), mat, src, (8, 8), "nv12", layout, chroma_siting=siting, max_taps=taps, dtype=dtype)
+        assert nv12.dtype == y420.dtype == want.dtype
+        assert np.array_equal(_bits(nv12), _bits(want)) and np.array_equal(_bits(y420), _bits(want)), taps
+    assert not np.array_equal(rec[f"{siting}_fp32_taps1"][1], rec[f"{siting}_fp32_taps4"][1])          # the minified slot takes the taps
+
+
 @pytest.mark.parametrize("siting", ["left", "center"])
 @pytest.mark.parametrize("fmt,low", [("nv21", None), ("yuv420p", None), ("yv12", None), ("p010", "zero"), ("p010", "random")])
 def test_formats_give_the_nv12_bits_on_the_same_samples(fmt, low, siting):
@@ -310,6 +335,49 @@ def test_entry_is_declared_bound_and_validates_without_a_device():
         assert ENTRY.encode() in err and word in err, (kw, err)
     null = lib.lh_frames_crop_surfaces_to_nhwc4(p[0], p[1], 0, None, None, 4, 2, hs, ws, 64, 64, 1, 66, m3, s3, p[2], p[3], 1, None, None, None, 0, None)
     assert null == -1 and b"bad arguments" in lib.lh_last_error()
+
+
+@pytest.mark.parametrize("plain", [False, True], ids=["eager", "plan"])
+def test_the_choice_of_crop_entry(plain):
+    """topdown.crop_entry, the one place that picks among the five C crop entries, over formats x buffer / surfaces x jitter x max_taps:
+    the descriptor path first (with or without jitter), then jitter, NV12, the area entry; what is left is lh_frames_crop_to_nhwc4 for
+    the plan (``plain``) at max_taps = 1 and the area entry for the eager launch.  The arguments are the entry's but for the stream.
+    Nothing is called: the pointers are dummies."""
+    from lighthand_amd import _lib
+    from lighthand_amd.topdown import FRAME_FORMATS, crop_entry, frame_layout_of, frames_layout_struct, nv12_layout, through_descriptor
+    lib = _lib.load()
+    hs, ws = 96, 128
+    m3, s3, csc = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 12)()
+    seen = set()
+    taps_at = {"lh_frames_crop_surfaces_to_nhwc4": -5, "lh_frames_crop_jitter_to_nhwc4": -5, "lh_frames_crop_yuv_to_nhwc4": -2,
+               "lh_frames_crop_area_to_nhwc4": -2}                 # max_taps from the end: in front of (jitter triple,) dtype
+    cases = [(fmt, None, surfaces) for fmt in FRAME_FORMATS for surfaces in (False, True)] + [("nv12", frame_layout_of("nv12", hs, ws), False)]
+    for fmt, layout, surfaces in cases:
+        for jitter in (False, True):
+            for taps in (1, 4):
+                where = {}
+                if through_descriptor(fmt, layout, surfaces):
+                    assert surfaces or fmt in ("nv21", "yuv420p", "p010") or layout is not None
+                    where["desc"] = frames_layout_struct(frame_layout_of(fmt, hs, ws, layout), ("bt709", "limited"), "left")
+                    where.update(dict(table=0x9000) if surfaces else dict(frame_stride=hs * ws * 3))
+                    want = "lh_frames_crop_surfaces_to_nhwc4"
+                else:
+                    assert fmt in ("rgb", "nv12")
+                    if fmt == "nv12":
+                        where["nv12"] = nv12_layout(hs, ws)[:3] + (0, csc)
+                    want = ("lh_frames_crop_jitter_to_nhwc4" if jitter else "lh_frames_crop_yuv_to_nhwc4" if fmt == "nv12" else
+                            "lh_frames_crop_area_to_nhwc4" if taps > 1 or not plain else "lh_frames_crop_to_nhwc4")
+                if jitter:
+                    where["jit"] = (0x5000, 0x6000, 0x7000)
+                fn, args, what = crop_entry(lib, fmt, taps, None if surfaces else 0x1000, 0x2000, 4, 2, hs, ws, 64, 64, 1, 66, m3, s3, 0x3000, 0x4000,
+                                            0, plain=plain, **where)
+                assert fn.__name__ == want and fn is getattr(lib, want), (fmt, surfaces, jitter, taps, fn.__name__)
+                assert len(args) == len(_lib.SIGNATURES[want][1]) - 1, (want, len(args))
+                assert args[1] == 0x2000 and args[-1] == 0 and ("ColorJitter" in what) == jitter and ("antialiased" in what) == (taps > 1)
+                assert want not in taps_at or args[taps_at[want]] == taps
+                assert ("surface table" in what) == surfaces
+                seen.add(want)
+    assert len(seen) == (5 if plain else 4)
 
 
 # ------------------------------------------------------------------------------------------------ 6. the constructors' refusals

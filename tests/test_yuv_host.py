@@ -1,5 +1,5 @@
 """CPU: the host side of top-down inference on NV12 frames -- yuv_matrix / nv12_layout / rgb_to_nv12_host and the numpy restatement
-frames_crop_nv12_host of lighthand_amd.topdown (the rule of lh_frames_crop_yuv_to_nhwc4: csrc/topdown.hip's header comment) against
+frames_crop_nv12_host of lighthand_amd.topdown (the rule of lh_frames_crop_yuv_to_nhwc4: csrc/frames_crop_kernel.h, above crop_sample_nv12) against
 the standards' colour bars, the RGB restatement on grey frames and the chroma siting formed by hand; the entry's argument checks and
 the refusals of InferStep / InferPipeline without a GPU.  The kernel is checked against frames_crop_nv12_host in tests/test_gpu_yuv_crop.py."""
 import ctypes as C
