@@ -120,7 +120,7 @@ def test_crop_jitter_rules_before_any_device_work():
     got = check(None, fr, crop_jitter=(0.5, 0.5, 0.5, 0.5))
     assert got == (fr, None, (0.5, 0.5, 0.5, 0.5)) and all(isinstance(v, float) for v in got[2])
     assert check(None, fr, roi_aug=(30, 0.25, 0.1, 0.5), crop_jitter=[0.4, 0, 0.2, 0.1])[2] == (0.4, 0.0, 0.2, 0.1)
-    assert check(None, fr) == (fr, None)                                             # without the option: the two values as before
+    assert check(None, fr) == (fr, None, None)                                       # without the option: the same three values
     with pytest.raises(ValueError, match="crop_jitter"):
         check(None, None, crop_jitter=(0.5, 0.5, 0.5, 0.5))
     for bad in ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5, 0.5, 0.5), (0.5, -0.5, 0.5, 0.5), (0.5, 0.5, 0.5, -0.1), (0.5, 0.5, 0.5, 0.6), 0.5, "0.5",

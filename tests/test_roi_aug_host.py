@@ -307,9 +307,9 @@ def test_train_step_refusals_before_any_device_work():
     """One assertion per rule, through the validation function TrainStep calls first (no model, no device)."""
     from lighthand_amd.runtime import TrainStep, _check_train_frames as check
     fr = (4, 96, 128)
-    assert check(None, None) == (None, None)
-    got, spec = check(None, fr, roi_aug=(30, 0.2, 0.1))
-    assert got == fr and spec["rotation"] == 30 and spec["mirror_prob"] == 0.0 and spec["prob"] == 1.0 and spec["generator"] is None
+    assert check(None, None) == (None, None, None)
+    got, spec, jitter = check(None, fr, roi_aug=(30, 0.2, 0.1))
+    assert got == fr and jitter is None and spec["rotation"] == 30 and spec["mirror_prob"] == 0.0 and spec["prob"] == 1.0 and spec["generator"] is None
     assert check(None, fr, roi_aug=(30, 0.2, 0.1, 0.5))[1]["mirror_prob"] == 0.5
     assert check(None, fr, roi_aug=dict(rotation=10, prob=0.5))[1]["prob"] == 0.5
     with pytest.raises(ValueError, match="input_u8"):
