@@ -610,7 +610,9 @@ int lh_fuse_bwd_plan(const lh_fuse_bwd_desc* d, int n, int h, int w, int c, void
  * pose_resnet.py:151-156 and the first four lines of PoseResNet.forward.  img: the zero-padded NHWC4 image the engine's input
  * transforms write ([n][hp][wp][4], image pixel (y, x) at (y + 3, x + 3)); wpack: the stem's weight pack (64 channels, one tap
  * per kernel ROW, K run = 8 pixels x 4 channels); out = [n][ph][pw][64] with ph = (conv_h - 1) / 2 + 1.  relu must be 1 (the
- * pool's padding is realised as zeros).  16-bit types.  Bit-identical to lh_igemm + lh_maxpool3x3s2_fwd on the same operands. */
+ * pool's padding is realised as zeros).  16-bit types.  Bit-identical to lh_igemm + lh_maxpool3x3s2_fwd on the same operands.
+ * lh_stem_pool_grid: the workgroups the launch takes (persistent over tiles of 8 x 8 pooled pixels; host arithmetic only). */
+int lh_stem_pool_grid(int n, int conv_h, int conv_w);
 int lh_stem_pool(const void* img, int n, int hp, int wp, const void* wpack, const float* bias, const float* scale,
                  const float* shift, void* out, int conv_h, int conv_w, int relu, int dtype, void* stream);
 
@@ -621,8 +623,10 @@ int lh_stem_pool(const void* img, int n, int hp, int wp, const void* wpack, cons
  * blocks with stride 1 (pytorch and caffe style alike).  x = [n][h][w][cin], residual and out = [n][h][w][256] (residual = x for an
  * identity shortcut, the projection's output otherwise; out may alias neither).  w1 / w2 / w3: the weight packs lh_pack_weight makes
  * for those three convolutions (K-major rows, taps in (r, s) order).  16-bit types.  Only x and the residual are read and out is
- * written -- the two 64-channel intermediates stay in LDS.  Bit-identical to the three lh_igemm launches with the same folds. */
+ * written -- the two 64-channel intermediates stay in LDS.  Bit-identical to the three lh_igemm launches with the same folds.
+ * lh_bottleneck_infer_grid: the workgroups the launch takes (persistent over 16 x 16 tiles; host arithmetic only, 0 for an empty problem). */
 typedef struct { int n, h, w, cin, mid, cout; } lh_bottleneck_desc;
+int lh_bottleneck_infer_grid(const lh_bottleneck_desc* d);
 int lh_bottleneck_infer(const lh_bottleneck_desc* d, const void* x, const void* w1, const void* w2, const void* w3,
                         const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
                         const void* residual, void* out, int dtype, void* stream);
@@ -631,7 +635,8 @@ int lh_bottleneck_infer(const lh_bottleneck_desc* d, const void* x, const void* 
  * same operands as lh_stem_pool (padded NHWC4 image, the stem's weight pack), on the same direct kernel form: out =
  * [n][conv_h][conv_w][64] raw convolution output (bit-identical to lh_igemm on that pack), stats = fp32
  * [lh_stem_conv_rows(n, conv_h, conv_w)][2][64] per-workgroup sums / sums of squares of the stored values for lh_bn_finalize.
- * 16-bit types. */
+ * lh_stem_conv_rows is the launch's grid as well (persistent over tiles of 16 x 16 outputs), as lh_stem_pool_grid and
+ * lh_bottleneck_infer_grid are for theirs.  16-bit types. */
 int lh_stem_conv_rows(int n, int conv_h, int conv_w);
 int lh_stem_conv(const void* img, int n, int hp, int wp, const void* wpack, void* out, float* stats, int conv_h, int conv_w,
                  int dtype, void* stream);

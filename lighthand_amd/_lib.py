@@ -190,6 +190,8 @@ SIGNATURES = {
     "lh_fuse_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "lh_fuse_bwd": (_I, [C.POINTER(FuseBwdDesc), _I, _I, _I, _I, _P, _I, _P]),
     "lh_fuse_bwd_plan": (_I, [C.POINTER(FuseBwdDesc), _I, _I, _I, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I]),
+    "lh_stem_pool_grid": (_I, [_I, _I, _I]),
+    "lh_bottleneck_infer_grid": (_I, [C.POINTER(BottleneckDesc)]),
     "lh_stem_pool": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "lh_bottleneck_infer": (_I, [C.POINTER(BottleneckDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "lh_stem_conv_rows": (_I, [_I, _I, _I]),

@@ -9,6 +9,15 @@
 const unsigned char* lh_ring_zero_page();      // igemm_ring.hip: 16 zero bytes / 1 KiB nobody reads, per device
 unsigned char* lh_ring_dump_page();
 
+// workgroups lh_bottleneck_infer launches: persistent over 16 x 16 tiles, one 8-wave workgroup per CU.  (An 8 x 16 / 4-wave form with
+// two workgroups per CU was equal to 3 % slower -- the launch moves 4.4 GB through the fabric either way: x with its halo, x AGAIN as
+// the residual, the output -- and was removed in round 6.)
+extern "C" int lh_bottleneck_infer_grid(const lh_bottleneck_desc* d) {
+    if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
+    const long nt = (long)d->n * ceil_div(d->h, 16) * ceil_div(d->w, 16);
+    return (int)(nt < 256 ? nt : 256);
+}
+
 extern "C" int lh_bottleneck_infer(const lh_bottleneck_desc* d, const void* x, const void* w1, const void* w2, const void* w3,
                                    const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
                                    const void* residual, void* out, int dtype, void* stream) {
@@ -32,9 +41,7 @@ extern "C" int lh_bottleneck_infer(const lh_bottleneck_desc* d, const void* x, c
     a.x = (const unsigned char*)x; a.w1 = (const unsigned char*)w1; a.w2 = (const unsigned char*)w2; a.w3 = (const unsigned char*)w3;
     a.s1 = s1; a.b1 = b1; a.s2 = s2; a.b2 = b2; a.s3 = s3; a.b3 = b3;
     a.n = d->n; a.h = d->h; a.w = d->w; a.cin = d->cin; a.kpad1 = (d->cin + 63) / 64 * 64;
-    // 16 x 16 tiles, one 8-wave workgroup per CU.  (An 8 x 16 / 4-wave form with two workgroups per CU was equal to 3 % slower -- the launch moves
-    // 4.4 GB through the fabric either way: x with its halo, x AGAIN as the residual, the output -- and was removed in round 6.)
-    a.grid = (int)(nt < 256 ? nt : 256);
+    a.grid = lh_bottleneck_infer_grid(d);
     const int lds = lh_bottleneck_lds_bytes(16, 4);
     hipStream_t s = (hipStream_t)stream;
     const void* fn = dtype == LH_BF16 ? reinterpret_cast<const void*>(&bottleneck_infer_kernel<bf16, 16, 8, 4>)

@@ -26,7 +26,8 @@
 //    instructions per stage kind: surplus ones copy the zero page into a dump kilobyte).
 //  * K order of every convolution = that of the tiled kernels (tap-major, K ascending in 32-element MFMA slices), the
 //    epilogue arithmetic that of igemm_wave_epilogue.h: the block output is BIT-IDENTICAL to the three launches
-//    (tests/test_gpu_ops.py::test_fused_inference_bottleneck_is_bit_identical).
+//    (tests/test_gpu_model.py::test_fused_inference_bottleneck_is_bit_identical on whole models; tests/test_gpu_exact_fused.py through
+//    the C ABI, every ring residue, several tiles per workgroup).
 #pragma once
 #include "igemm_ring_kernel.h"
 #include "igemm_wave_epilogue.h"

@@ -173,6 +173,13 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolArgs p)
     }
 }
 
+// workgroups lh_stem_pool launches for n images of conv_h x conv_w convolution outputs: persistent, two workgroups per CU at most
+extern "C" int lh_stem_pool_grid(int n, int conv_h, int conv_w) {
+    const int ph = (conv_h + 2 - 3) / 2 + 1, pw = (conv_w + 2 - 3) / 2 + 1;
+    const long nt = (long)n * ceil_div(ph, 8) * ceil_div(pw, 8);
+    return (int)(nt < 512 ? nt : 512);
+}
+
 extern "C" int lh_stem_pool(const void* img, int n, int hp, int wp, const void* wpack, const float* bias, const float* scale,
                             const float* shift, void* out, int conv_h, int conv_w, int relu, int dtype, void* stream) {
     LH_REQUIRE(img && wpack && out && n > 0 && conv_h > 0 && conv_w > 0, "lh_stem_pool: bad arguments");
@@ -188,7 +195,7 @@ extern "C" int lh_stem_pool(const void* img, int n, int hp, int wp, const void* 
     const long nt = (long)n * a.ty * a.tx;
     LH_REQUIRE(nt < (1L << 30), "lh_stem_pool: too many tiles");
     a.ntiles = (int)nt;
-    const int grid = (int)(nt < 512 ? nt : 512);                      // persistent: two workgroups per CU
+    const int grid = lh_stem_pool_grid(n, conv_h, conv_w);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LH_BF16) hipLaunchKernelGGL((stem_pool_kernel<bf16>), dim3(grid), dim3(256), SP_LDS, s, a);
     else hipLaunchKernelGGL((stem_pool_kernel<f16>), dim3(grid), dim3(256), SP_LDS, s, a);

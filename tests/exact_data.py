@@ -7,7 +7,8 @@ The bound is derived, not measured: |any partial sum| <= sum of the magnitudes o
 (check_exact computes exactly that, in fp64, on the reference alone).  The reference is torch.nn.functional in float64 on the CPU: sums of
 integers below 2^53 are exact there in any order too.
 
-The second half of the file ("The BatchNorm grid") does the same for the BatchNorm / fused elementwise / pooling kernels."""
+The second half of the file ("The BatchNorm grid") does the same for the BatchNorm / fused elementwise / pooling kernels, the last
+section for the fused stem and bottleneck kernels."""
 import torch
 import torch.nn.functional as F
 
@@ -699,3 +700,219 @@ def bn_planned_route(lib, desc, n, h, w, c, workspace, dtype_code):
     nrec = lib.lh_fuse_bwd_plan(C.byref(desc), n, h, w, c, workspace, dtype_code, kinds, grids, folds, cap)
     assert 0 < nrec <= cap, (nrec, lib.lh_last_error())
     return [(kinds[i], grids[i], folds[i]) for i in range(nrec)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The fused stem and bottleneck kernels (tests/test_gpu_exact_fused.py): lh_stem_pool, lh_stem_conv (csrc/stem_pool.hip) and
+# lh_bottleneck_infer (csrc/bottleneck_infer_kernel.h), all three persistent.  Same rules as above: integer operands, power-of-two scales,
+# every sum of magnitudes below 2^24 product quanta (fused_stem_check / bneck_check, on the fp64 reference alone).
+#
+# Stem images (n, h, w) -> convolution 7x7 / s2 / p3, pool 3x3 / s2 / p1:
+#   tiny    9 x 7:   conv 5 x 4, pooled 3 x 2 -- less than one tile of either kernel
+#   ragged  70 x 90: conv 35 x 45 (odd both; the last convolution row reads past the image, the last column does not), pooled 18 x 23
+#                    = 3 x 3 pool tiles of 8 x 8, 3 x 3 conv tiles of 16 x 16
+#   multi   66 x 66: conv 33, pooled 17: 3 x 3 tiles per image with a one-pixel last tile, for both kernels; 171 images = 1539 tiles =
+#                    3 x 512 + 3: with the grid of 512 three workgroups take four tiles, the others three, and the prefetch behind the last
+#                    tile is the zero fill (the GPU test asserts this against lh_stem_pool_grid / lh_stem_conv_rows, not against 512)
+FUSED_STEM_IMAGES = {"tiny": (1, 9, 7), "ragged": (2, 70, 90), "multi": (171, 66, 66)}
+# flavour -> precision -> (a for the image, a for the weights, a for the shift).  "exact": sums large enough to need roundings; the shift
+# spans the values with one more bit than the type holds, so that the pooled maxima need roundings too.  "stats": small enough that the
+# sums of SQUARES of the stored convolution outputs of one lh_stem_conv workgroup (up to four tiles of 256 pixels) stay below 2^24 --
+# which no data that needs roundings can do (EPILOGUE_RANGES): the rounded values are then the sums themselves.
+FUSED_STEM_RANGES = {"exact": {"bf16": (8, 4, 512), "fp16": (32, 8, 4096)}, "stats": {"bf16": (4, 2, 64), "fp16": (4, 2, 64)}}
+# "exact" ranges widened where a small case leaves condition (c) of tests/test_exact_host.py unmet: (image, precision) -> (a image, a weights,
+# a shift).  From that test's failures; never narrower.
+FUSED_STEM_WIDER = {("tiny", "bf16"): (32, 8, 512), ("tiny", "fp16"): (128, 16, 4096)}
+FUSED_STEM_DEAD, FUSED_STEM_NEG = 5, 9       # a channel whose shift leaves nothing above zero; a channel with negative scale (others: drawn)
+
+
+def fused_stem_ranges(image, precision, flavour):
+    r = FUSED_STEM_RANGES[flavour][precision]
+    return FUSED_STEM_WIDER.get((image, precision), r) if flavour == "exact" else r
+
+
+def fused_stem_sizes(image):
+    """(n, h, w, hp, wp, ch, cw, ph, pw): image, its padded NHWC4 form (engine.Plan._c_stem: hp = h + 6, wp = w + 8), convolution, pool."""
+    n, h, w = FUSED_STEM_IMAGES[image]
+    ch, cw = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
+    return n, h, w, h + 6, w + 8, ch, cw, (ch - 1) // 2 + 1, (cw - 1) // 2 + 1
+
+
+def fused_stem_data(image, precision, flavour="exact"):
+    """x [n][3][h][w], w [64][3][7][7], bias, shift: integers; scale from +-{0.5, 1, 2}.  Channel FUSED_STEM_DEAD has a shift below minus
+    the largest value the affine can reach (every output of it is zero), channel FUSED_STEM_NEG a negative scale."""
+    n, h, w = FUSED_STEM_IMAGES[image]
+    ax, aw, ash = fused_stem_ranges(image, precision, flavour)
+    g = torch.Generator().manual_seed(2000 + 7 * h + w)
+    half = torch.tensor([0.5, 1.0, 2.0])
+    d = dict(x=ints((n, 3, h, w), ax, g), w=ints((64, 3, 7, 7), aw, g), bias=ints((64,), 16, g), shift=ints((64,), ash, g),
+             scale=half[torch.randint(0, 3, (64,), generator=g)] * (2.0 * torch.randint(0, 2, (64,), generator=g) - 1.0))
+    d["scale"][FUSED_STEM_NEG] = -d["scale"][FUSED_STEM_NEG].abs()
+    d["shift"][FUSED_STEM_DEAD] = -(2.0 * (147 * ax * aw + 16) + 1.0)
+    return d
+
+
+def fused_stem_layout(x, w):
+    """The operands as the kernels read them (engine.Plan._c_stem): the zero-padded NHWC4 image [n][h + 6][w + 8][4] with pixel (y, x) at
+    (y + 3, x + 3), and the weight staging [64][7 kernel rows][8 pixels][4 channels] whose rows are the K runs of the pack (pixel 7 and
+    channel 3 are zero)."""
+    n, _, h, wd = x.shape
+    img = torch.zeros(n, h + 6, wd + 8, 4, dtype=x.dtype)
+    img[:, 3:3 + h, 3:3 + wd, :3] = x.permute(0, 2, 3, 1)
+    stage = torch.zeros(w.shape[0], 7, 8, 4, dtype=w.dtype)
+    stage[:, :, :7, :3] = w.permute(0, 2, 3, 1)
+    return img, stage
+
+
+def fused_stem_tap_conv(img, stage, ch, cw):
+    """The stem convolution as the direct kernels form it, in fp64: acc[n][a][b][co] = sum over kernel rows r and the 32 elements j of
+    the row's K run of img[n][2 a + r][2 b + j / 4][j % 4] * stage[co][r][j]."""
+    img, stage = img.double(), stage.double()
+    acc = torch.zeros(img.shape[0], ch, cw, stage.shape[0], dtype=torch.float64)
+    for r in range(7):
+        for px in range(8):
+            acc += img[:, r:r + 2 * ch - 1:2, px:px + 2 * cw - 1:2] @ stage[:, r, px].t()
+    return acc
+
+
+def fused_stem_reference(d, precision):
+    """fp64 reference, NHWC.  acc: the exact convolution; mag: the same of |x|, |w|; act: relu(acc * scale + (bias * scale + shift)) before
+    its rounding; conv16 / act16: the ONE round-to-nearest-even of acc / act (what lh_stem_conv stores / what lh_stem_pool keeps in LDS);
+    pooled: F.max_pool2d(3, 2, 1) over act16; s1, s2: per-channel sums / sums of squares of conv16.  Zeros are +0."""
+    dt = DTYPES[precision]
+    acc = F.conv2d(d["x"].double(), d["w"].double(), None, 2, 3).permute(0, 2, 3, 1).contiguous()
+    mag = F.conv2d(d["x"].double().abs(), d["w"].double().abs(), None, 2, 3).permute(0, 2, 3, 1)
+    sc = d["scale"].double()
+    act = torch.relu(acc * sc + (d["bias"].double() * sc + d["shift"].double())) + 0.0
+    conv16, act16 = expected_16(acc + 0.0, dt), expected_16(act, dt)
+    pooled = F.max_pool2d(act16.double().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).contiguous()
+    c = conv16.double().reshape(-1, 64)
+    return dict(acc=acc, mag=mag, act=act, conv16=conv16, act16=act16, pooled=expected_16(pooled, dt), s1=c.sum(0), s2=(c * c).sum(0))
+
+
+def fused_stem_check(d, r):
+    """(a) for the stem: the convolution's sum of magnitudes below 2^24, and the affine acc * scale + (bias * scale + shift) in its quantum
+    0.5 (|scale| <= 2).  Returns the larger, in quanta."""
+    for k in ("x", "w", "bias", "shift"):
+        assert torch.equal(d[k], d[k].round()), k
+    assert set(d["scale"].abs().tolist()) <= {0.5, 1.0, 2.0}
+    mag = float(r["mag"].max())
+    worst = max(mag, 2.0 * (2.0 * (mag + float(d["bias"].abs().max())) + float(d["shift"].abs().max())))
+    assert worst < LIMIT, f"stem: sum of magnitudes {worst:.0f} >= 2^24"
+    return worst
+
+
+def pooled_source(r):
+    """The exact (unrounded) activation behind every pooled value: the window's largest exact value -- rounding is monotonic, so it rounds
+    to the window's largest stored value.  What rounding_counts is asked about the pooled map."""
+    return F.max_pool2d(r["act"].permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+
+
+def stem_conv_row_of_pixel(n, ch, cw, rows):
+    """Statistics row of every convolution output [n][ch][cw], as stem_conv_kernel's tile loop assigns it (csrc/stem_pool.hip: tiles of
+    16 x 16 outputs numbered image-major, then tile row, then tile column; workgroup b takes tiles b, b + grid, ...; one row per workgroup)."""
+    ty, tx = (ch + 15) // 16, (cw + 15) // 16
+    tile = (torch.arange(n).view(n, 1, 1) * ty + torch.arange(ch).view(1, ch, 1) // 16) * tx + torch.arange(cw).view(1, 1, cw) // 16
+    return tile % rows
+
+
+# The bottleneck: cin -> stages per tile cin / 32 + 5 = 7, 8, 10, 13: ring residues 3, 0, 2, 1; 96 and 160 are no multiple of 64 (kpad1 != cin)
+BNECK_CIN = (64, 96, 160, 256)
+#   tiny    5 x 7:   every pixel is a border pixel, the whole halo lies outside the image
+#   ragged  17 x 33: 2 x 3 tiles whose last row and column of tiles are one pixel deep
+#   multi   17 x 17: 4 tiles per image, 130 images = 520 tiles = 2 x 256 + 8: with the grid of 256 eight workgroups take three tiles
+BNECK_SHAPES = {"tiny": (1, 5, 7), "ragged": (2, 17, 33), "multi": (130, 17, 17)}
+# precision -> a for x, w1, w2, w3; largest |k| of the shifts b = k * quantum of layers 1, 2, 3; a for a separate residual; log2 of the
+# scales: layer l draws |s| from 2^-(e_l + {0, 1}).  The shifts of layers 1 and 2 reach past the values the type holds exactly, so that
+# the intermediates need roundings whatever cin; e_l keeps the magnitudes level (and every fp16 value normal and finite).
+# The bit budget that sets the ranges: a stored activation that needs a rounding has more than 8 / 11 significant bits in ITS channel's
+# quantum, the next accumulator counts in the FINEST channel's quantum (one more bit: two exponents per layer), and sums 576 or 64 such
+# terms times |w| -- in fp16 2^12 * 576 * mean|w2| is about 2^22, and conv3 behind it only fits with w3 from {-1, 0, 1} and the last
+# sum with a residual of at most 128.  Three exponents per layer, w3 = 2 or a residual of 2047 pass 2^24 (bneck_check says where).
+BNECK_RANGES = {"bf16": dict(x=8, w1=4, w2=2, w3=2, k=(512, 8192, 65536), res=128, e=(1, 4, 4)),
+                "fp16": dict(x=32, w1=8, w2=2, w3=1, k=(4096, 131072, 524288), res=128, e=(3, 6, 2))}
+BNECK_WIDER = {}        # (cin, shape, precision) -> dict of the entries of BNECK_RANGES that are widened; never narrower
+BNECK_POSITIVE = 8      # channels 0 .. 7 of b1 and b2 are strictly positive: relu(shift) in the halo instead of conv2's zero padding must show
+
+
+def bneck_ranges(cin, shape, precision):
+    return {**BNECK_RANGES[precision], **BNECK_WIDER.get((cin, shape, precision), {})}
+
+
+def _pow2_scale(c, e, gen):
+    return 2.0 ** -(e + torch.randint(0, 2, (c,), generator=gen).double()) * (2.0 * torch.randint(0, 2, (c,), generator=gen).double() - 1.0)
+
+
+def bneck_data(cin, shape, precision):
+    """Operands of one bottleneck case, fp64 holding values fp32 and (x, w, res) the 16-bit type hold exactly: x [n][h][w][cin], w1 [64][cin],
+    w2 [64][64][3][3], w3 [256][64], res [n][h][w][256] integers; s_l = +- a power of two per channel; b_l = k * q_l |s_l| with integer k and
+    q_l the quantum of layer l's accumulator (q: the three of them)."""
+    n, h, w = BNECK_SHAPES[shape]
+    r = bneck_ranges(cin, shape, precision)
+    g = torch.Generator().manual_seed(3000 + cin + 7 * h + w)
+    d = dict(x=ints((n, h, w, cin), r["x"], g).double(), w1=ints((64, cin), r["w1"], g).double(), w2=ints((64, 64, 3, 3), r["w2"], g).double(),
+             w3=ints((256, 64), r["w3"], g).double(), res=ints((n, h, w, 256), r["res"], g).double())
+    q, qs = 1.0, []
+    for l, c in ((1, 64), (2, 64), (3, 256)):
+        s = _pow2_scale(c, r["e"][l - 1], g)
+        k = ints((c,), r["k"][l - 1], g).double()
+        if l < 3:
+            k[:BNECK_POSITIVE] = k[:BNECK_POSITIVE].abs() + 1.0
+        d[f"s{l}"], d[f"k{l}"], d[f"b{l}"] = s, k, k * q * s.abs()
+        qs.append(q)
+        q = q * float(s.abs().min())            # the quantum of the stored activation = that of the next accumulator (integer weights)
+    d["q"] = qs
+    return d
+
+
+def bneck_reference(d, precision, residual=None):
+    """fp64 reference with every storage point of bottleneck_infer_kernel.h (residual: default d["res"]; pass d["x"] for an identity block):
+      a1 = round16(relu(acc1 * s1 + b1))                     conv1 epilogue, lines 323-326 (rounded, then ReLU: the same value)
+      a2 = round16(relu(acc2 * s2 + b2)), acc2 from a1 with ZERO padding outside the image (line 327: `if (!inside) pk.u = 0`), lines 405-408
+      y3 = round16(acc3 * s3 + b3)                           bneck_epilogue_half, lines 63-66 (igemm_wave_epilogue.h:45-48)
+      out = round16(relu(y3 + residual))                     lines 83-84 (igemm_wave_epilogue.h:122-128)
+    pre1 / pre2 / pre3 / pre_out: the exact values in front of those four roundings (raw1 / raw2: without the ReLU, which the kernel applies
+    behind the rounding); mag1 / mag2 / mag3: the layers' sums of magnitudes
+    |input| * |w| + |k|, in the accumulator's quanta.  Zeros are +0."""
+    dt = DTYPES[precision]
+
+    def r16(t):
+        return (t + 0.0).float().to(dt).double()
+    res = d["res"] if residual is None else residual
+    q1, q2, q3 = d["q"]
+    acc1 = d["x"] @ d["w1"].t()
+    pre1 = torch.relu(acc1 * d["s1"] + d["b1"])
+    a1 = r16(pre1)
+    conv2 = lambda a, w: F.conv2d(a.permute(0, 3, 1, 2), w, None, 1, 1).permute(0, 2, 3, 1)
+    acc2 = conv2(a1, d["w2"])
+    pre2 = torch.relu(acc2 * d["s2"] + d["b2"])
+    a2 = r16(pre2)
+    acc3 = a2 @ d["w3"].t()
+    pre3 = acc3 * d["s3"] + d["b3"]
+    y3 = r16(pre3)
+    pre_out = torch.relu(y3 + res)
+    out = r16(pre_out)
+    mag1 = (d["x"].abs() @ d["w1"].abs().t() + d["k1"].abs()) / q1
+    mag2 = conv2(a1.abs(), d["w2"].abs()) / q2 + d["k2"].abs()
+    mag3 = (a2.abs() @ d["w3"].abs().t()) / q3 + d["k3"].abs()
+    return dict(acc1=acc1, acc2=acc2, acc3=acc3, raw1=acc1 * d["s1"] + d["b1"], raw2=acc2 * d["s2"] + d["b2"], pre1=pre1, a1=a1, pre2=pre2, a2=a2, pre3=pre3, y3=y3, pre_out=pre_out, out=out,
+                mag1=mag1, mag2=mag2, mag3=mag3, res=res)
+
+
+def bneck_check(d, r):
+    """(a) per layer: every operand a multiple of its quantum and the layer's sum of magnitudes below 2^24 quanta, so acc * s + b is exact
+    in fp32 (s a power of two, b = k quanta * |s|); the last sum y3 + residual in the quantum of y3 as well.  Returns the three layer
+    maxima and that of the last sum, in quanta."""
+    q1, q2, q3 = d["q"]
+    for t, q, what in ((d["x"], 1.0, "x"), (d["w1"], 1.0, "w1"), (d["w2"], 1.0, "w2"), (d["w3"], 1.0, "w3"), (r["res"], 1.0, "residual"),
+                       (r["a1"], q2, "a1"), (r["a2"], q3, "a2")):
+        assert bool((t / q == torch.round(t / q)).all()), f"{what} is no multiple of its quantum {q}"
+    for l in (1, 2, 3):
+        s = d[f"s{l}"].abs()
+        assert bool((torch.log2(s) == torch.round(torch.log2(s))).all()) and torch.equal(d[f"b{l}"], d[f"k{l}"] * d["q"][l - 1] * s)
+    q4 = q3 * d["s3"].abs()                                      # per channel: y3 and the integer residual are multiples of it
+    assert float(q4.max()) <= 1.0 and bool((r["y3"] / q4 == torch.round(r["y3"] / q4)).all())
+    last = float(((r["y3"].abs() + r["res"].abs()) / q4).max())
+    worst = [float(r["mag1"].max()), float(r["mag2"].max()), float(r["mag3"].max()), last]
+    assert max(worst) < LIMIT, f"bottleneck: sums of magnitudes {worst} (>= 2^24 somewhere)"
+    return worst

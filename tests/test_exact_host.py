@@ -2,7 +2,8 @@
 (a) every sum of magnitudes, in units of the product quantum, is below 2^24 -- so an fp32 accumulator is exact in any order;
 (b) no expected fp16 value overflows;
 (c) out and dx together hold at least 10 exact ties and at least 100 values that need rounding -- so a wrong rounding mode cannot pass.
-Plus: the hand-written tap loop that serves as the epilogue test's host side agrees with F.conv2d / F.conv_transpose2d in fp64."""
+Plus: the hand-written tap loop that serves as the epilogue test's host side agrees with F.conv2d / F.conv_transpose2d in fp64.
+The last section does the same for the fused stem and bottleneck kernels of tests/test_gpu_exact_fused.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -330,3 +331,173 @@ def test_bn_route_table_is_what_the_planners_return(monkeypatch):
             assert kind.value == kf[want] and grid.value == (-(-chunks // 256) if want == "GEN" else max(1, -(-chunks // 1024))), (name, precision)
             seen_f.add(kind.value)
     assert seen_f == set(range(3))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The fused stem and bottleneck kernels of tests/test_gpu_exact_fused.py: (a) - (c) for every case and precision it runs, the statistics
+# rows of lh_stem_conv on the kernel's own tile-to-workgroup partition, the multi-tile conditions against the library's grid queries
+# (host arithmetic: no GPU), and the hand-written references against F.conv2d.
+def _held_exactly(t, dt):
+    return torch.equal(t.float().to(dt).double(), t.double())
+
+
+def _no_fp16_trouble(tensors, what):
+    """(b): finite, and no nonzero value below the smallest normal fp16 (2^-14): the comparison never rests on subnormal handling."""
+    for k, t in tensors.items():
+        a = t.double().abs()
+        assert float(a.max()) <= E.FP16_MAX and bool(torch.isfinite(t.float().to(torch.float16)).all()), (what, k, float(a.max()))
+        assert not bool(((a > 0) & (a < 2.0 ** -14)).any()), (what, k, "a subnormal fp16 value")
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("image", list(E.FUSED_STEM_IMAGES))
+def test_fused_stem_cases_meet_the_preconditions(image, precision):
+    """lh_stem_pool and lh_stem_conv, "exact" flavour: integer operands the type holds, (a) through fused_stem_check, (b) on the raw
+    convolution and the activation, (c) on the raw convolution (what lh_stem_conv stores) and on the pooled map (asked of the exact value
+    behind each pooled maximum); one channel is dead, one has a negative scale, no two images are equal, and the sums row of every
+    lh_stem_conv workgroup stays below 2^24 (its squares row does not: that is the "stats" flavour's)."""
+    dt = E.DTYPES[precision]
+    d = E.fused_stem_data(image, precision)
+    got, base = E.fused_stem_ranges(image, precision, "exact"), E.FUSED_STEM_RANGES["exact"][precision]
+    assert all(g >= b for g, b in zip(got, base))                                       # widened, never narrowed
+    assert _held_exactly(d["x"], dt) and _held_exactly(d["w"], dt)
+    n, h, w, hp, wp, ch, cw, ph, pw = E.fused_stem_sizes(image)
+    assert len(torch.unique(d["x"].reshape(n, -1), dim=0)) == n
+    r = E.fused_stem_reference(d, precision)
+    assert r["acc"].shape == (n, ch, cw, 64) and r["pooled"].shape == (n, ph, pw, 64)
+    worst = E.fused_stem_check(d, r)                                                    # (a)
+    peak = max(float(r["acc"].abs().max()), float(r["act"].max()))
+    if precision == "fp16":
+        _no_fp16_trouble(dict(acc=r["acc"], act=r["act"]), image)                       # (b)
+    assert float(r["pooled"][..., E.FUSED_STEM_DEAD].abs().max()) == 0.0 and float(r["act"][..., E.FUSED_STEM_DEAD].max()) == 0.0
+    assert float(d["scale"][E.FUSED_STEM_NEG]) < 0 and float(r["pooled"][..., E.FUSED_STEM_NEG].max()) > 0
+    (rc, tc), (rp, tp) = E.rounding_counts(r["acc"], dt), E.rounding_counts(E.pooled_source(r), dt)
+    assert torch.equal(E.expected_16(E.pooled_source(r), dt), r["pooled"])              # rounding is monotonic: pooled_source is what it says
+    rows = _library().lh_stem_conv_rows(n, ch, cw)
+    rid = E.stem_conv_row_of_pixel(n, ch, cw, rows).reshape(-1)
+    sums = torch.zeros(rows, 64, dtype=torch.float64).index_add_(0, rid, r["conv16"].double().abs().reshape(-1, 64))
+    print(image, precision, f"largest sum of magnitudes {worst:.0f}, peak {peak:.0f}; convolution: need rounding {rc}, ties {tc}; pooled map: need "
+          f"rounding {rp}, ties {tp}; largest statistics row, sum of magnitudes {float(sums.max()):.0f}")
+    assert rc >= 100 and tc >= 10 and rp >= 100 and tp >= 10                            # (c)
+    assert float(sums.max()) < E.LIMIT
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("image", list(E.FUSED_STEM_IMAGES))
+def test_stem_conv_statistics_rows_are_exact(image, precision):
+    """"stats" flavour: workgroup b of stem_conv_kernel sums the stored values and their squares over the valid pixels of tiles b, b + grid,
+    ... (exact_data.stem_conv_row_of_pixel restates the tile loop); every row's sum of squares -- all terms non-negative integers -- stays
+    below 2^24, so each row is exact in fp32 in any order and the fp64 total of the rows equals the fp64 sums of the stored values."""
+    dt = E.DTYPES[precision]
+    d = E.fused_stem_data(image, precision, "stats")
+    r = E.fused_stem_reference(d, precision)
+    E.fused_stem_check(d, r)
+    n, h, w, hp, wp, ch, cw, ph, pw = E.fused_stem_sizes(image)
+    rows = _library().lh_stem_conv_rows(n, ch, cw)
+    rid = E.stem_conv_row_of_pixel(n, ch, cw, rows).reshape(-1)
+    assert rid.numel() == n * ch * cw and int(rid.max()) == rows - 1 and len(torch.unique(rid)) == rows
+    v = r["conv16"].double().reshape(-1, 64)
+    assert torch.equal(v, r["acc"].reshape(-1, 64))                                     # no value of this flavour needs a rounding
+    s1 = torch.zeros(rows, 64, dtype=torch.float64).index_add_(0, rid, v)
+    s1m = torch.zeros(rows, 64, dtype=torch.float64).index_add_(0, rid, v.abs())
+    s2 = torch.zeros(rows, 64, dtype=torch.float64).index_add_(0, rid, v * v)
+    print(image, precision, f"{rows} rows; largest row: sum of magnitudes {float(s1m.max()):.0f}, sum of squares {float(s2.max()):.0f}")
+    assert float(s1m.max()) < E.LIMIT and float(s2.max()) < E.LIMIT
+    assert torch.equal(s1.float().double(), s1) and torch.equal(s2.float().double(), s2)
+    assert torch.equal(s1.sum(0), r["s1"]) and torch.equal(s2.sum(0), r["s2"])
+
+
+def test_stem_tap_loop_equals_conv2d():
+    """The stem convolution restated on the kernels' operands -- padded NHWC4 image, weight rows of 8 pixels x 4 channels
+    (exact_data.fused_stem_layout, fused_stem_tap_conv) -- against F.conv2d(stride 2, padding 3) in fp64, on the odd-sized cases."""
+    for image in ("tiny", "ragged"):
+        d = E.fused_stem_data(image, "fp16")
+        n, h, w, hp, wp, ch, cw, ph, pw = E.fused_stem_sizes(image)
+        img, stage = E.fused_stem_layout(d["x"], d["w"])
+        assert img.shape == (n, hp, wp, 4) and hp >= 2 * (ch - 1) + 7 and wp >= 2 * (cw - 1) + 8
+        want = F.conv2d(d["x"].double(), d["w"].double(), None, 2, 3).permute(0, 2, 3, 1)
+        assert torch.equal(E.fused_stem_tap_conv(img, stage, ch, cw), want)
+        assert torch.equal(E.fused_stem_reference(d, "fp16")["acc"], want)
+
+
+_BNECK_RUNS = [(cin, shape, res) for cin in E.BNECK_CIN for shape in E.BNECK_SHAPES for res in (("separate", "x") if cin == 256 else ("separate",))]
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("cin,shape,res", _BNECK_RUNS)
+def test_bottleneck_cases_meet_the_preconditions(cin, shape, res, precision):
+    """lh_bottleneck_infer: (a) for each of the three layers and for the last sum (bneck_check), (b) on every value any of the four
+    roundings meets, ReLU or not, (c) on the block output, and at least 100 real roundings in front of each intermediate; several
+    channels of b1 and b2 are strictly positive and alive."""
+    dt = E.DTYPES[precision]
+    d = E.bneck_data(cin, shape, precision)
+    rng, base = E.bneck_ranges(cin, shape, precision), E.BNECK_RANGES[precision]
+    assert all(rng[k] >= base[k] for k in ("x", "w1", "w2", "w3", "res")) and all(a >= b for a, b in zip(rng["k"], base["k"]))   # never narrowed
+    for k in ("x", "w1", "w2", "w3", "res"):
+        assert _held_exactly(d[k], dt) and torch.equal(d[k], d[k].round()), k
+    for l in (1, 2, 3):
+        assert torch.equal(d[f"s{l}"].float().double(), d[f"s{l}"]) and torch.equal(d[f"b{l}"].float().double(), d[f"b{l}"])
+    assert float(d["b1"][:E.BNECK_POSITIVE].min()) > 0 and float(d["b2"][:E.BNECK_POSITIVE].min()) > 0
+    r = E.bneck_reference(d, precision, d["x"] if res == "x" else None)
+    worst = E.bneck_check(d, r)                                                         # (a)
+    # a positive shift that matters: relu(b1) would be stored in the halo by a kernel that forgot conv2's zero padding
+    assert float(E.expected_16(torch.relu(d["b1"][:E.BNECK_POSITIVE]), dt).min()) > 0 and float(r["a2"][..., :E.BNECK_POSITIVE].max()) > 0
+    peak = max(float(r[k].abs().max()) for k in ("raw1", "raw2", "pre3", "pre_out"))
+    if precision == "fp16":
+        _no_fp16_trouble({k: r[k] for k in ("raw1", "raw2", "pre3", "pre_out", "a1", "a2", "y3", "out")}, (cin, shape))     # (b)
+    counts = {k: E.rounding_counts(r[k], dt) for k in ("pre1", "pre2", "pre3", "pre_out")}
+    print(cin, shape, res, precision, "largest sums of magnitudes (conv1, conv2, conv3, y3 + residual): " + ", ".join(f"{m:.0f}" for m in worst)
+          + f"; peak {peak:.0f}; (need rounding, ties) of a1, a2, y3, out: {list(counts.values())}")
+    assert counts["pre_out"][0] >= 100 and counts["pre_out"][1] >= 10                   # (c)
+    assert all(counts[k][0] >= 100 for k in ("pre1", "pre2", "pre3"))
+
+
+def test_bottleneck_reference_equals_three_conv2d_calls():
+    """exact_data.bneck_reference (matrix products on NHWC for the 1x1 layers) against three F.conv2d calls on NCHW with the same roundings."""
+    for cin, precision in ((96, "bf16"), (256, "fp16")):
+        dt = E.DTYPES[precision]
+        d = E.bneck_data(cin, "ragged", precision)
+        r = E.bneck_reference(d, precision)
+        r16 = lambda t: t.float().to(dt).double()
+        aff = lambda t, l: t * d[f"s{l}"].view(1, -1, 1, 1) + d[f"b{l}"].view(1, -1, 1, 1)
+        x = d["x"].permute(0, 3, 1, 2)
+        a1 = r16(torch.relu(aff(F.conv2d(x, d["w1"].view(64, cin, 1, 1)), 1)))
+        a2 = r16(torch.relu(aff(F.conv2d(a1, d["w2"], None, 1, 1), 2)))
+        y3 = r16(aff(F.conv2d(a2, d["w3"].view(256, 64, 1, 1)), 3))
+        out = r16(torch.relu(y3 + d["res"].permute(0, 3, 1, 2)))
+        assert torch.equal(out.permute(0, 2, 3, 1), r["out"]) and torch.equal(a2.permute(0, 2, 3, 1), r["a2"])
+
+
+def _library():
+    from lighthand_amd import _lib
+    return _lib.load()
+
+
+def test_multi_tile_cases_walk_the_persistent_loops():
+    """The grid queries (host arithmetic) on the shapes alone: lh_stem_pool_grid, lh_stem_conv_rows and lh_bottleneck_infer_grid answer
+    min(tiles, cap) -- one workgroup per tile on the small cases --, and on the multi-tile cases every workgroup takes at least two tiles,
+    some take one more, and the tile count is no multiple of the grid (the prefetch behind a workgroup's last tile is the zero fill)."""
+    import ctypes as C
+    from lighthand_amd import _lib
+    lib = _lib.load()
+    up = lambda a, b: -(-a // b)
+    for image in E.FUSED_STEM_IMAGES:
+        n, h, w, hp, wp, ch, cw, ph, pw = E.fused_stem_sizes(image)
+        for grid, tiles in ((lib.lh_stem_pool_grid(n, ch, cw), n * up(ph, 8) * up(pw, 8)), (lib.lh_stem_conv_rows(n, ch, cw), n * up(ch, 16) * up(cw, 16))):
+            assert 0 < grid <= tiles
+            if image == "multi":
+                assert tiles > 2 * grid and tiles % grid != 0 and up(tiles, grid) >= 3, (tiles, grid)
+            else:
+                assert grid == tiles
+    assert E.fused_stem_sizes("tiny")[5:] == (5, 4, 3, 2) and E.fused_stem_sizes("ragged")[5:] == (35, 45, 18, 23) and E.fused_stem_sizes("multi")[5:] == (33, 33, 17, 17)
+    for shape, (n, h, w) in E.BNECK_SHAPES.items():
+        for cin in E.BNECK_CIN:
+            bd = _lib.BottleneckDesc(n, h, w, cin, 64, 256)
+            grid, tiles = lib.lh_bottleneck_infer_grid(C.byref(bd)), n * up(h, 16) * up(w, 16)
+            assert 0 < grid <= tiles
+            if shape == "multi":
+                assert tiles > 2 * grid and tiles % grid != 0 and up(tiles, grid) >= 3, (tiles, grid)
+            else:
+                assert grid == tiles
+    assert lib.lh_bottleneck_infer_grid(C.byref(_lib.BottleneckDesc(0, 17, 17, 64, 64, 256))) == 0 and lib.lh_bottleneck_infer_grid(None) == 0
+    assert sorted((cin // 32 + 5) % 4 for cin in E.BNECK_CIN) == [0, 1, 2, 3]           # every phase of the four-slot ring at a tile boundary
