@@ -224,6 +224,37 @@ int lh_keypoints_to_rois(const float* preds_dev, const float* maxvals_dev, const
  * multiplies |dxhat|, units of x per second). */
 int lh_one_euro(const float* x_dev, const int* src_frame_dev, const int* lost_dev, const float* dt_dev, int b, int j, float min_cutoff,
                 float beta, float d_cutoff, float* xhat_dev, float* dxhat_dev, int* init_dev, float* out_dev, void* stream);
+/* Track management of the tracked step (opt-in; runtime.ManagedInferStep(frames=..., track=True, manage_tracks=...)), one launch behind
+ * lh_keypoints_to_boxes / lh_keypoints_to_rois and in front of lh_one_euro; it edits next_boxes_dev fp32 [b][4], next_rot_dev fp32
+ * [b][2] (may be NULL: upright steps) and lost_dev int32 [b] in place and keeps lost_count_dev int32 [b] (state: frames a slot has been
+ * lost).  Slot i belongs to frame f = frame_index[i] when 0 <= f < n_frames; any other slot is never touched, and frames are
+ * independent.  The detection list has k entries: det_boxes_dev fp32 [k][4] = x0 y0 x1 y1 (frame pixel indices), det_frame_dev int32
+ * [k], det_score_dev fp32 [k]; an entry is valid when its frame is in range, its coordinates are finite, x1 > x0, y1 > y0 and its
+ * score is finite and >= det_min_score.  All arithmetic is fp32 in the order written, without division or sqrtf; min / max are
+ * "a < b ? a : b" / "a > b ? a : b".
+ *  1. kb[i] = the bounds lh_keypoints_to_boxes computes from preds_dev fp32 [b][j][2] / maxvals_dev fp32 [b][j]: min / max of the
+ *     joints with maxval >= track_min_score in ascending order, each side widened about its centre to track_min_side (axis-aligned in
+ *     the frame under oriented ROIs too); score[i] = the sum of those maxvals in ascending order.  A slot is live when lost[i] == 0.
+ *  2. over(a, b, t): iw = min(ax1, bx1) - max(ax0, bx0), ih likewise; false unless iw > 0 && ih > 0; else
+ *     iw*ih > t * min((ax1-ax0)*(ay1-ay0), (bx1-bx0)*(by1-by0)) -- intersection over the smaller area.
+ *  3. The live slots of a frame are walked in descending score (ties: lower index); a slot is kept unless over(kb[i], kb[k],
+ *     dup_overlap) for a slot k kept before it (the first such k in that order).  A suppressed slot: dup_of[i] = k, lost[i] = 1,
+ *     next_boxes[i] = 0 0 0 0, lost_count[i] = 0.  dup_of = -1 for every other slot of a frame.
+ *  4. lost_count = 0 for a kept slot and for one with src_frame < 0; every other slot that is not suppressed counts
+ *     min(lost_count + 1, 1 << 30), and with max_lost > 0 a count >= max_lost empties it: next_boxes = 0 0 0 0, lost_count = 0.
+ *  5. The frame's free slots are those not kept, in ascending index.  Its valid detections are walked in descending score (ties:
+ *     lower index): det_state[d] = -2 if over(det, kb[i], match_overlap) for a kept slot i, else -3 if it overlaps (same test) a
+ *     detection accepted before it, else -4 if no free slot is left, else the first free slot i: seeded[i] = d, next_boxes[i] = the
+ *     detection's box, next_rot[i] = (1, 0), lost_count[i] = 0 (lost[i] stays as it is).  det_state = -1 for every other entry,
+ *     seeded = -1 for every other slot of a frame.
+ * One workgroup of 64 threads per frame (a mode of the fp32 frame-crop kernel with a launch of its own and dynamic LDS sized by b and k);
+ * records staged in LDS, ranks by counting, no atomics: a replay is bit-reproducible.
+ * 1 <= b <= 1024, 1 <= k <= 1024, j > 0; thresholds finite, and all but track_min_score >= 0; max_lost >= 0. */
+int lh_tracks_manage(const float* preds_dev, const float* maxvals_dev, const int* src_frame_dev, const int* frame_index_dev, int b, int j,
+                     int n_frames, const float* det_boxes_dev, const int* det_frame_dev, const float* det_score_dev, int k,
+                     float track_min_score, float track_min_side, float dup_overlap, float match_overlap, float det_min_score, int max_lost,
+                     float* next_boxes_dev, float* next_rot_dev, int* lost_dev, int* lost_count_dev, int* dup_of_dev, int* seeded_dev,
+                     int* det_state_dev, void* stream);
 /* Training on hand ROIs cropped from full frames (opt-in; runtime.TrainStep(frames=..., roi_aug=...)).
  * lh_roi_perturb: the caller's ROI (boxes_dev fp32 [b][4], rot_dev fp32 [b][2] or NULL = (1, 0), mirror_dev int32 [b] or NULL = 0) and
  * this step's draw aug_dev fp32 [b][6] = (c, s, k, tx, ty, flip) -> the ROI that lh_roi_affine reads (boxes_out, rot_out, mirror_out).

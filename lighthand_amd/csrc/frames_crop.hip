@@ -197,6 +197,10 @@ extern "C" int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, voi
 }
 
 // ------------------------------------------------------------------------------------------------ training on frames: the two modes
+void lh_frames_crop_launch_f32(const CropArgs& a, int grid, int block, size_t lds, void* stream) {
+    hipLaunchKernelGGL((frames_crop_kernel<float>), dim3(grid), dim3(block), lds, (hipStream_t)stream, a);
+}
+
 extern "C" int lh_roi_perturb(const float* boxes_dev, const float* rot_dev, const int* mirror_dev, const float* aug_dev, int b,
                               float* boxes_out, float* rot_out, int* mirror_out, void* stream) {
     LH_REQUIRE(boxes_dev && aug_dev && boxes_out && rot_out && mirror_out && b > 0, "lh_roi_perturb: bad arguments");

@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 #include "color_jitter.h"
+#include "tracks_manage_kernel.h"
 
 // ------------------------------------------------------------------------------------------------ frames -> crops
 // Slot blockIdx.y reads frame src_frame[slot] of a buffer every slot shares: several boxes per frame, frames of any size.  The slot's
@@ -43,8 +44,12 @@ struct CropArgs {
     int gen;
     const long long* table;                                       // [n_frames] device addresses (0 = empty), or null: src + f * frame_stride
     int dsc[4];                                                   // LH_FRAMES_420 / 420W: c_pitch, cb_offset, cr_offset, c_step (with pitch, siting)
+    TracksArgs tm;                                                // op = LH_CROP_TRACKS_MANAGE (lh_tracks_manage, tracks_manage_kernel.h): all it reads
 };
-enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3 };
+// frames_crop.hip: a launch of the fp32 instantiation with `grid` workgroups of `block` threads and `lds` bytes of dynamic LDS, for an
+// entry in another file (tracks_manage.hip); the caller runs LH_LAUNCH_CHECK.
+void lh_frames_crop_launch_f32(const CropArgs& a, int grid, int block, size_t lds, void* stream);
+enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3, LH_CROP_TRACKS_MANAGE = 4 };
 enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2, LH_JIT_STORE = 3 };      // STORE: no jitter, the store is jit.dtype's
 
 // What a jittered launch carries into the pixel loops: the slot's factors and order, then the grey mean (LH_JIT_APPLY) or the number
@@ -430,6 +435,11 @@ __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the modes (CropArgs)
         if (p.op == LH_CROP_ROI_PERTURB || p.op == LH_CROP_POINTS_INV) {
             crop_aux_modes(p);
+            return;
+        }
+        if (p.op == LH_CROP_TRACKS_MANAGE) {                      // grid (n_frames), 64 threads, dynamic LDS: lh_tracks_manage's launch alone
+            extern __shared__ __attribute__((aligned(16))) unsigned char tm_lds[];
+            tracks_manage_frame(p.tm, tm_lds);
             return;
         }
     }

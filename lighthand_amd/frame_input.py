@@ -138,6 +138,42 @@ def _check_tracking(model, fi, track, track_min_score, track_min_joints, track_m
     return float(min_cutoff), float(beta), float(d_cutoff)
 
 
+MANAGE_TRACKS_MAX = 1024           # slots, and detections, of one lh_tracks_manage launch (its static LDS arrays)
+
+
+def _check_manage_tracks(fi, track, manage_tracks, batch):
+    """ManagedInferStep / ManagedInferPipeline(manage_tracks=) behind _check_tracking: refuse what cannot run, before any device work.  False / None:
+    None (the step as it was).  True or a dict of ``max_detections`` (1..1024, default: the batch), ``dup_overlap`` (0.5),
+    ``match_overlap`` (0.5), ``det_min_score`` (0.0), ``max_lost`` (0: nothing expires) -> the dict with every key, as ints / floats."""
+    if manage_tracks is None or manage_tracks is False:
+        return None
+    if manage_tracks is not True and not isinstance(manage_tracks, dict):
+        raise ValueError(f"manage_tracks must be False, True or a dict of options, not {manage_tracks!r}")
+    if not track or fi.frames is None:
+        raise ValueError("manage_tracks= manages the slots of a tracked step: pass frames=(n_frames, hs, ws), track=True")
+    given = {} if manage_tracks is True else dict(manage_tracks)
+    unknown = sorted(set(given) - {"max_detections"} - set(topdown.MANAGE_TRACKS_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"manage_tracks: unknown keys {unknown!r}; it takes max_detections, " + ", ".join(topdown.MANAGE_TRACKS_DEFAULTS))
+    if not isinstance(batch, numbers.Integral) or not 1 <= batch <= MANAGE_TRACKS_MAX:
+        raise ValueError(f"manage_tracks serves a batch of 1..{MANAGE_TRACKS_MAX} slots, not {batch!r}")
+    out = dict(topdown.MANAGE_TRACKS_DEFAULTS, max_detections=batch)
+    out.update(given)
+    for key in ("max_detections", "max_lost"):
+        v = out[key]
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"manage_tracks: {key} must be an integer >= 0, not {v!r}")
+        out[key] = int(v)
+    if not 1 <= out["max_detections"] <= MANAGE_TRACKS_MAX:
+        raise ValueError(f"manage_tracks: max_detections must be within 1..{MANAGE_TRACKS_MAX}, not {out['max_detections']!r}")
+    for key in ("dup_overlap", "match_overlap", "det_min_score"):
+        v = out[key]
+        if not _is_number(v) or v < 0:
+            raise ValueError(f"manage_tracks: {key} must be a finite number >= 0, not {v!r}")
+        out[key] = float(v)
+    return out
+
+
 def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_jitter=None, targets_from_joints=True, roi_aug=None,
                         coord_loss_weight=0.0, use_target_weight=False, crop_jitter=None, **frame_options):
     """TrainStep(frames=, roi_aug=, crop_jitter=) against the step's other options: refuse what cannot run, before any device work (no

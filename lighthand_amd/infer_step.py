@@ -3,7 +3,7 @@ import torch
 
 from . import _lib, heatmap
 from ._lib import LightHandError, check
-from .frame_input import FrameInput, _check_beta, _check_tracking, _FrameStep, _ptr
+from .frame_input import FrameInput, _check_beta, _check_manage_tracks, _check_tracking, _FrameStep, _ptr
 
 
 class InferStep(_FrameStep):
@@ -75,12 +75,14 @@ class InferStep(_FrameStep):
     surfaces are cropped where they lie, with no copy.  ``bind_surfaces(tensors, start=0)`` / ``unbind_surfaces(indices=None)`` fill
     and clear it, ``step(surfaces=seq, ...)`` binds and replays; the captured graph stays the same.  An unbound frame is empty: its
     slots crop exactly black (``valid`` keeps meaning ``src_frame >= 0``: whether a surface is bound is the caller's matter).  A
-    surface may be overwritten or freed only after the step's stream has passed the replay that reads it."""
+    surface may be overwritten or freed only after the step's stream has passed the replay that reads it.
+    Track management -- duplicate tracks, expiry, a detector's boxes -- is ManagedInferStep's, below."""
 
     _serial = 0
     _frame_inputs = "frames / boxes / frame_index"
     _frames_take = "frames / boxes / frame_index, not images"
     _rot_also, _rot_first = "", False
+    _manage_tracks_option, _detections = False, None               # ManagedInferStep(manage_tracks=) / its call's detections=
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
@@ -93,6 +95,7 @@ class InferStep(_FrameStep):
                               yuv=yuv, chroma_siting=chroma_siting, frame_layout=frame_layout, surfaces=surfaces)
         smooth = _check_tracking(model, fi, track=track, track_min_score=track_min_score, track_min_joints=track_min_joints,
                                  track_min_side=track_min_side, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth)
+        self.manage_tracks = _check_manage_tracks(fi, track, self._manage_tracks_option, batch)        # ManagedInferStep's
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
         self.soft_argmax_beta = float(soft_argmax_beta)
@@ -107,6 +110,7 @@ class InferStep(_FrameStep):
         # input_u8=(hs, ws): raw uint8 HWC frames; ToTensor / Resize / Normalize run fused on the device (dataset.py:128-159)
         self.images = self.plan.use_uint8_input(*input_u8) if input_u8 else self.plan.img_nchw
         self.crop_preds = self.next_boxes = self.lost = self.next_rot = self.dt = self.smooth_preds = None
+        self.det_boxes = self.det_frame = self.det_score = self.lost_count = self.dup_of = self.seeded = self.det_state = None
         self.track, self.smooth = bool(track) and fi.frames is not None, smooth
         self.track_min_score, self.track_min_joints, self.track_min_side = float(track_min_score), int(track_min_joints), float(track_min_side)
         self._use_frame_input(fi)
@@ -119,6 +123,15 @@ class InferStep(_FrameStep):
                 self.lost = torch.ones(batch, dtype=torch.int32, device=dev)
                 if self.oriented:
                     self.next_rot = self.rot.clone()
+                if self.manage_tracks:
+                    k = self.manage_tracks["max_detections"]
+                    self._n_frames = fi.frames[0]
+                    self.det_boxes = torch.zeros(k, 4, dtype=torch.float32, device=dev)
+                    self.det_frame = torch.full((k,), -1, dtype=torch.int32, device=dev)
+                    self.det_score = torch.zeros(k, dtype=torch.float32, device=dev)
+                    self.lost_count = torch.zeros(batch, dtype=torch.int32, device=dev)       # state: replays in a row a slot has been lost
+                    self.dup_of, self.seeded = (torch.full((batch,), -1, dtype=torch.int32, device=dev) for _ in range(2))
+                    self.det_state = torch.full((k,), -1, dtype=torch.int32, device=dev)
             if smooth:
                 self.dt = torch.full((batch,), 1.0 / 30.0, dtype=torch.float32, device=dev)
                 self.smooth_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
@@ -175,6 +188,14 @@ class InferStep(_FrameStep):
                                                      out.shape[0], out.shape[1], self.track_min_score, self.track_min_joints,
                                                      self.track_min_side, self.next_boxes.data_ptr(), self.lost.data_ptr(), s),
                       "lh_keypoints_to_boxes")
+            if self.manage_tracks:
+                mt = self.manage_tracks
+                check(self.lib.lh_tracks_manage(self.preds.data_ptr(), self.maxvals.data_ptr(), p.src_frame.data_ptr(), self.frame_index.data_ptr(),
+                                                out.shape[0], out.shape[1], self._n_frames, self.det_boxes.data_ptr(), self.det_frame.data_ptr(),
+                                                self.det_score.data_ptr(), mt["max_detections"], self.track_min_score, self.track_min_side,
+                                                mt["dup_overlap"], mt["match_overlap"], mt["det_min_score"], mt["max_lost"],
+                                                self.next_boxes.data_ptr(), _ptr(self.next_rot), self.lost.data_ptr(), self.lost_count.data_ptr(),
+                                                self.dup_of.data_ptr(), self.seeded.data_ptr(), self.det_state.data_ptr(), s), "lh_tracks_manage")
             if self.smooth:
                 check(self.lib.lh_one_euro(self.preds.data_ptr(), p.src_frame.data_ptr(), _ptr(self.lost), self.dt.data_ptr(), out.shape[0],
                                            out.shape[1], self.smooth[0], self.smooth[1], self.smooth[2], self._xhat.data_ptr(),
@@ -201,6 +222,36 @@ class InferStep(_FrameStep):
         else:
             self._seen[torch.as_tensor(slots, device=self._seen.device)] = 0
 
+    def reset_tracks(self, slots=None):
+        """Zero ``lost_count`` of ``slots`` (indices or a mask; None: all), on the device: their expiry starts counting again.
+        LightHandError on a step built without ``manage_tracks=``, as advance()'s."""
+        if not self.manage_tracks:
+            raise LightHandError("reset_tracks() needs ManagedInferStep(frames=..., track=True, manage_tracks=True)")
+        if slots is None:
+            self.lost_count.zero_()
+        else:
+            self.lost_count[torch.as_tensor(slots, device=self.lost_count.device)] = 0
+
+    def _copy_detections(self, detections):
+        """The detection list of this call: ``detections`` = (boxes [n][4], frame [n], score [n]), n <= max_detections, tensors or
+        array-likes; the entries behind them, or all of them without ``detections``, are empty (frame -1)."""
+        n = 0
+        if detections is not None:
+            if not isinstance(detections, (tuple, list)) or len(detections) != 3:
+                raise ValueError("detections must be (boxes [n][4], frame [n], score [n])")
+            dev = self.det_boxes.device
+            boxes = torch.as_tensor(detections[0], dtype=torch.float32).reshape(-1, 4)
+            frame, score = torch.as_tensor(detections[1], dtype=torch.int32).reshape(-1), torch.as_tensor(detections[2], dtype=torch.float32).reshape(-1)
+            n = boxes.shape[0]
+            if frame.shape[0] != n or score.shape[0] != n or n > self.det_boxes.shape[0]:
+                raise ValueError(f"detections: boxes [n][4], frame [n] and score [n] with n <= max_detections = {self.det_boxes.shape[0]}, got "
+                                 f"{tuple(boxes.shape)} / {tuple(frame.shape)} / {tuple(score.shape)}")
+            if n:
+                self.det_boxes[:n].copy_(boxes.to(dev, non_blocking=True), non_blocking=True)
+                self.det_frame[:n].copy_(frame.to(dev, non_blocking=True), non_blocking=True)
+                self.det_score[:n].copy_(score.to(dev, non_blocking=True), non_blocking=True)
+        self.det_frame[n:].fill_(-1)
+
     def refresh_weights(self):
         self.plan.refresh_packs(torch.cuda.current_stream().cuda_stream)
         self._packed = True
@@ -214,12 +265,16 @@ class InferStep(_FrameStep):
         self._copy_frame_inputs(frames, boxes, frame_index, rot, mirror)
         if dt is not None:
             self.dt.copy_(dt, non_blocking=True) if torch.is_tensor(dt) else self.dt.fill_(float(dt))
+        if self.manage_tracks:
+            self._copy_detections(self._detections)
+            self._detections = None
         if not self._packed:
             self.refresh_weights()
         if not self.use_graph:
             self._enqueue()
             return self.preds
         if self.graph is None:
+            lost_count = self.lost_count.clone() if self.manage_tracks else None
             warm = torch.cuda.Stream()
             warm.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(warm):
@@ -228,6 +283,8 @@ class InferStep(_FrameStep):
             torch.cuda.synchronize()
             if self.smooth:
                 self._seen.zero_()                                  # the warm-up run is not a frame: the first replay starts the filter
+            if self.manage_tracks:
+                self.lost_count.copy_(lost_count)                   # nor does it count towards a slot's expiry
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._enqueue()
@@ -249,11 +306,14 @@ class InferPipeline:
     ``frame_format`` / ``yuv`` / ``chroma_siting`` / ``frame_layout``: as InferStep's; every slot owns its NV12 buffer.
     ``surfaces``: as InferStep's; every slot owns its surface table, and ``submit(surfaces=seq, ...)`` binds on the slot that runs
     the ticket (the slot keeps the references until it is bound again, ``depth`` submits later).
+    Track management: ManagedInferPipeline, below.
 
         pipe = InferPipeline(model, 64, 256, 256, depth=2)
         t0 = pipe.submit(images0); t1 = pipe.submit(images1)
         preds0, maxvals0 = pipe.result(t0)          # valid until `depth` more batches have been submitted
     """
+
+    _step_class, _step_extra = InferStep, {}                        # ManagedInferPipeline's slots are ManagedInferSteps
 
     def __init__(self, model, batch, height, width, depth=2, input_u8=None, flip_test=False, shift_heatmap=True, post_process=False,
                  blur_kernel=11, soft_argmax_beta=100.0, frames=None, box_padding=1.25, track=False, track_min_score=0.1,
@@ -263,7 +323,7 @@ class InferPipeline:
         options = {k: v for k, v in locals().items() if k not in ("self", "model", "batch", "height", "width", "depth")}
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.steps = [InferStep(model, batch, height, width, bn_train=False, slot=i, **options) for i in range(depth)]
+        self.steps = [self._step_class(model, batch, height, width, bn_train=False, slot=i, **options, **self._step_extra) for i in range(depth)]
         self.streams = [torch.cuda.Stream() for _ in range(depth)]
         self.events = [None] * depth
         self.count = 0
@@ -288,10 +348,13 @@ class InferPipeline:
                 # after submit() gets the same block back for the next batch while this copy is still queued
                 t.record_stream(st)
         with torch.cuda.stream(st):
-            self.steps[i](images, frames, boxes, frame_index, rot, mirror, dt, surfaces)
+            self._call_step(self.steps[i], images, frames, boxes, frame_index, rot, mirror, dt, surfaces)
             self.events[i] = st.record_event()
         self.count += 1
         return self.count - 1
+
+    def _call_step(self, step, *inputs):
+        step(*inputs)
 
     def result(self, ticket):
         if ticket < self.count - len(self.steps) or ticket >= self.count:
@@ -302,7 +365,7 @@ class InferPipeline:
 
     def map(self, batches):
         """Yields (preds, maxvals) clones for every batch of the iterable, in order, keeping `depth` batches in flight.  A batch is
-        an image tensor, or a dict of submit()'s keyword arguments (frames / boxes / frame_index / rot / mirror / dt)."""
+        an image tensor, or a dict of submit()'s keyword arguments (frames / boxes / frame_index / rot / mirror / dt; ManagedInferPipeline: also detections)."""
         pending = []
         for images in batches:
             pending.append(self.submit(**images) if isinstance(images, dict) else self.submit(images))
@@ -312,3 +375,61 @@ class InferPipeline:
         for t in pending:
             p, m = self.result(t)
             yield p.clone(), m.clone()
+
+
+class ManagedInferStep(InferStep):
+    """InferStep(frames=..., track=True) that manages its tracks on the device: every argument of InferStep, and
+    ``manage_tracks=True`` (the default here) or a dict, on top of ``frames=..., track=True`` (``False``: InferStep as it is): lh_tracks_manage runs
+    behind lh_keypoints_to_boxes / lh_keypoints_to_rois and in front of lh_one_euro and edits ``next_boxes`` / ``next_rot`` / ``lost`` in
+    place, per frame (the slots with that ``frame_index``), so ``advance()`` hands on managed tracks with no host arithmetic.  Of the
+    live slots whose keypoint bounds overlap by more than ``dup_overlap`` of the smaller box, the one with the larger sum of confident
+    maxvals stays and the others are emptied (``dup_of`` names the winner; a zero box, ``lost`` = 1); a slot lost for ``max_lost``
+    replays in a row is emptied too (``lost_count`` counts them; 0: never).  The step owns a detection list of ``max_detections``
+    entries, ``det_boxes`` fp32 [K][4] / ``det_frame`` int32 [K] / ``det_score`` fp32 [K], filled through ``detections=(boxes, frame,
+    score)`` (n <= K rows; the rest is padded with frame -1): a detection of at least ``det_min_score`` that no kept slot and no
+    better detection covers by more than ``match_overlap`` takes the lowest slot of its frame that was not kept -- ``next_boxes`` is its
+    box, ``next_rot`` (1, 0), ``seeded`` names it, ``det_state`` says what became of every entry (the slot, -1 invalid, -2 tracked, -3
+    repeated, -4 no room) -- and ``lost`` stays 1 for that frame, so the filter starts fresh on the next.  A call without
+    ``detections=`` runs with an empty list: a list never seeds twice.  ``reset_tracks(slots=None)`` zeroes ``lost_count``.  The
+    defaults (0.5 / 0.5 / 0.0 / 0, MediaPipe's similarity threshold for the overlaps) are a design choice, not measured.  ``mirror`` and
+    ``frame_index`` stay the caller's; topdown.manage_tracks_host states the rule.
+    The two keywords live on this class, so InferStep's own signatures stay as they are."""
+
+    def __init__(self, *args, manage_tracks=True, **kwargs):
+        self._manage_tracks_option = manage_tracks
+        super().__init__(*args, **kwargs)
+
+    def __call__(self, *args, detections=None, **kwargs):
+        if detections is not None and not self.manage_tracks:
+            raise ValueError("detections are the input of ManagedInferStep(frames=..., track=True, manage_tracks=True)")
+        self._detections = detections
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            self._detections = None
+
+
+class ManagedInferPipeline(InferPipeline):
+    """InferPipeline whose slots are ManagedInferSteps: every argument of InferPipeline and ``manage_tracks`` as ManagedInferStep's, for
+    every slot.  Every slot owns its detection list and its ``lost_count``; ``submit(detections=...)`` fills the list of the slot that
+    runs the ticket (``steps[i].dup_of`` / ``seeded`` / ``det_state`` / ``reset_tracks()``)."""
+
+    _step_class = ManagedInferStep
+
+    def __init__(self, *args, manage_tracks=True, **kwargs):
+        self._step_extra = dict(manage_tracks=manage_tracks)
+        self._detections = None
+        super().__init__(*args, **kwargs)
+
+    def submit(self, *args, detections=None, **kwargs):
+        self._detections = detections
+        try:
+            return super().submit(*args, **kwargs)
+        finally:
+            self._detections = None
+
+    def _call_step(self, step, *inputs):
+        for t in self._detections if isinstance(self._detections, (tuple, list)) else ():
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(torch.cuda.current_stream())       # the slot's copy of the list runs on its stream: as submit()'s inputs
+        step(*inputs, detections=self._detections)

@@ -6,7 +6,7 @@ captured graph plus one device-to-device copy per frame, no host arithmetic in b
     track_frames.py --synthetic N --frame_size HSxWS [--hands 2] [--flip_test] [--dark_decode]
                     [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME] [--antialias [N]]
                     [--frame_format nv12|nv21|yuv420p|p010 [--yuv_matrix bt601|bt709] [--yuv_range limited|full]
-                     [--chroma_siting left|center]] [--surfaces]
+                     [--chroma_siting left|center]] [--surfaces] [--detect_every N [--max_lost M]]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -26,6 +26,11 @@ the step what a video decoder does: the synthetic frames are encoded to NV12 on 
 ``--frame_format nv21 | yuv420p | p010`` encode with topdown.rgb_to_yuv420_host in the tight layout of that format.  ``--surfaces``
 allocates one device tensor per synthetic frame, as a decoder on the same GPU leaves its surfaces, and binds the frame's tensor in
 front of every replay in place of the copy into ``step.frames`` (InferStep(surfaces=True), ``step(surfaces=[tensor])``).
+``--detect_every N`` manages the tracks on the device (runtime.ManagedInferStep(manage_tracks=dict(max_lost=M))): the detector is the scene's own
+ground truth, the bounds of each hand's joints jittered by a few pixels with the tool's seed, handed over as ``detections=`` on every
+N-th frame; hand 0 leaves the scene for the middle fifth of the sequence (its region is painted over with the background) and is
+detected once more on the frame it re-enters.  The line then also counts the slots that were seeded by a detection, suppressed as
+duplicates and expired after ``--max_lost`` lost frames in a row (default 0: never).
 With none of these the sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
@@ -57,13 +62,15 @@ def build_parser():
     ap.add_argument("--yuv_range", default="limited", choices=["limited", "full"], help="quantisation range of NV12 frames")
     ap.add_argument("--chroma_siting", default="left", choices=["left", "center"], help="horizontal position of NV12's chroma samples")
     ap.add_argument("--surfaces", action="store_true", help="one device tensor per frame, bound in place (no copy into a frame buffer)")
+    ap.add_argument("--detect_every", default=0, type=int, metavar="N", help="manage the tracks on the device; ground-truth detections every N-th frame")
+    ap.add_argument("--max_lost", default=0, type=int, metavar="M", help="with --detect_every: a slot lost M frames in a row is emptied (0: never)")
     return ap
 
 
 def main(argv=None):
     import torch
 
-    from lighthand_amd.runtime import InferStep
+    from lighthand_amd.runtime import InferStep, ManagedInferStep
     from lighthand_amd.modeling.simplebaseline.config import default_config
     from lighthand_amd.modeling.simplebaseline.pose_resnet import get_pose_net
     ap = build_parser()
@@ -76,8 +83,21 @@ def main(argv=None):
         ap.error("--mirror needs --oriented")
     if args.antialias is not None and not 1 <= args.antialias <= 8:
         ap.error("--antialias takes 1..8")
+    if args.detect_every < 0 or args.max_lost < 0 or (args.max_lost and not args.detect_every):
+        ap.error("--detect_every N >= 1 turns track management on; --max_lost M >= 0 needs it")
     hs, ws = args.frame_size
-    frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed, spin=args.spin)
+    if args.detect_every:
+        import numpy as np
+        frames, boxes, joints = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed, spin=args.spin, return_joints=True)
+        rng = np.random.RandomState(args.seed + 1)
+        truth = np.concatenate([joints.min(2), joints.max(2)], 2)                 # [n][hands][4]
+        truth = (truth + rng.uniform(-3, 3, size=truth.shape)).astype(np.float32)
+        away = range(2 * args.synthetic // 5, 3 * args.synthetic // 5)          # hand 0 is out of the scene on these frames
+        for t in away:
+            x0, y0, x1, y1 = np.rint(truth[t, 0] + (-8, -8, 8, 8)).astype(int).clip(0, [ws, hs, ws, hs])
+            frames[t, y0:y1, x0:x1] = rng.randint(0, 32, size=(y1 - y0, x1 - x0, 3))
+    else:
+        frames, boxes = synthetic_sequence(args.synthetic, hs, ws, args.hands, args.seed, spin=args.spin)
     torch.manual_seed(args.seed)
     model = get_pose_net(default_config(args.depth), is_train=True).cuda().set_precision(args.precision)
     model.eval()
@@ -115,7 +135,9 @@ def main(argv=None):
     del probe
     if args.one_euro:
         options["smooth"] = tuple(args.one_euro)
-    step = InferStep(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
+    if args.detect_every:
+        options["manage_tracks"] = dict(max_lost=args.max_lost)
+    step = (ManagedInferStep if args.detect_every else InferStep)(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
     step.boxes.copy_(torch.from_numpy(boxes))
     lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
     moved = torch.zeros((), dtype=torch.float64, device=step.lost.device)
@@ -125,10 +147,22 @@ def main(argv=None):
         step.rot.copy_(torch.tensor([1.0, 0.0]).expand(args.hands, 2))
     if args.one_euro:
         step.reset_filter()
+    if args.detect_every:
+        step.reset_tracks()
+        counts = torch.zeros(3, dtype=torch.int64, device=step.lost.device)      # seeded, suppressed, expired
+        on_frame_0, given = torch.zeros(args.hands, dtype=torch.int32), 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(args.synthetic):
-        step(**feed(t))
+        if args.detect_every:
+            hands = [h for h in range(args.hands) if (t % args.detect_every == 0 and not (h == 0 and t in away)) or (h == 0 and t and t == away.stop)]
+            dets = (torch.from_numpy(truth[t, hands]), on_frame_0[:len(hands)], torch.ones(len(hands))) if hands else None
+            given += len(hands)
+            step(detections=dets, **feed(t))
+            emptied = (step.next_boxes == 0).all(1) & step.valid & (step.dup_of < 0) & (step.seeded < 0)
+            counts += torch.stack([(step.seeded >= 0).sum(), (step.dup_of >= 0).sum(), emptied.sum()])
+        else:
+            step(**feed(t))
         lost += step.lost
         if args.one_euro:
             moved += (step.smooth_preds - step.preds).norm(dim=-1).mean().double()
@@ -153,6 +187,10 @@ def main(argv=None):
         result.update(frame_format=args.frame_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range, chroma_siting=args.chroma_siting)
     if args.surfaces:
         result["surfaces"] = True
+    if args.detect_every:
+        seeded, suppressed, expired = counts.tolist()
+        result.update(detect_every=args.detect_every, max_lost=args.max_lost, detections=given, slots_seeded=seeded, slots_suppressed=suppressed,
+                      slots_expired=expired)
     print(json.dumps(result))
     return result
 

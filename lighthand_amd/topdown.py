@@ -385,6 +385,99 @@ def boxes_from_keypoints_host(preds, maxvals, boxes, src_frame, min_score=0.1, m
     return out, lost.astype(np.int32)
 
 
+def _over_host(a, b, t):
+    """lh_tracks_manage's overlap test on two boxes of fp32 scalars: intersection over the smaller area > t, by comparisons and products."""
+    ix1, ix0 = (a[2] if a[2] < b[2] else b[2]), (a[0] if a[0] > b[0] else b[0])
+    iy1, iy0 = (a[3] if a[3] < b[3] else b[3]), (a[1] if a[1] > b[1] else b[1])
+    iw, ih = ix1 - ix0, iy1 - iy0
+    if not (iw > 0 and ih > 0):
+        return False
+    aa, ab = (a[2] - a[0]) * (a[3] - a[1]), (b[2] - b[0]) * (b[3] - b[1])
+    return bool(iw * ih > t * (aa if aa < ab else ab))
+
+
+MANAGE_TRACKS_DEFAULTS = dict(dup_overlap=0.5, match_overlap=0.5, det_min_score=0.0, max_lost=0)
+
+
+def manage_tracks_host(preds, maxvals, src_frame, frame_index, n_frames, next_boxes, next_rot, lost, lost_count, det_boxes, det_frame, det_score,
+                       min_score=0.1, min_side=16.0, dup_overlap=0.5, match_overlap=0.5, det_min_score=0.0, max_lost=0, dup_of=None,
+                       seeded=None):
+    """lh_tracks_manage in numpy, fp32 in the kernel's order: preds [b][j][2] (frame coordinates), maxvals [b][j] or [b][j][1], src_frame /
+    frame_index / lost / lost_count [b], next_boxes [b][4], next_rot [b][2] or None, the detection list det_boxes [k][4], det_frame [k],
+    det_score [k] -> (next_boxes, next_rot, lost, lost_count, dup_of, seeded, det_state), new arrays: the inputs are not modified.
+    ``dup_of`` / ``seeded`` [b] are what the outputs of those names hold before the call (None: -1), which a slot of no frame keeps.
+    Per frame f (the slots with frame_index == f, 0 <= f < n_frames):
+    kb = the bounds lh_keypoints_to_boxes takes of the joints with maxval >= min_score, score = the sum of those maxvals; the live slots
+    (lost == 0) are walked in descending score, ties to the lower index, and one is kept unless it overlaps (``_over_host`` at
+    dup_overlap) a slot kept before it -- then dup_of names the first such slot, lost = 1, its next box is 0 0 0 0 and lost_count 0.
+    lost_count is 0 for a kept slot and for an empty one (src_frame < 0) and counts up (to 1 << 30) for every other slot; with max_lost > 0
+    a count >= max_lost empties the slot (next box 0 0 0 0, count 0).  The valid detections (finite box with x1 > x0, y1 > y0, finite
+    score >= det_min_score) are walked in descending score, ties to the lower index: det_state = -2 when one overlaps (match_overlap) a
+    kept slot, else -3 when it overlaps a detection accepted before it, else -4 when every slot that was not kept is taken, else the
+    lowest such slot i: seeded[i] = d, its next box is the detection's, next_rot (1, 0), lost_count 0, lost as it was.  -1 for every
+    other entry of the list."""
+    preds = np.asarray(preds, np.float32)
+    b, j = preds.shape[:2]
+    mv = np.asarray(maxvals, np.float32).reshape(b, j)
+    src, fidx = np.asarray(src_frame, np.int32).reshape(b), np.asarray(frame_index, np.int32).reshape(b)
+    nbox = np.array(next_boxes, np.float32).reshape(b, 4)
+    nrot = None if next_rot is None else np.array(next_rot, np.float32).reshape(b, 2)
+    lost, count = np.array(lost, np.int32).reshape(b), np.array(lost_count, np.int32).reshape(b)
+    dbox = np.asarray(det_boxes, np.float32).reshape(-1, 4)
+    k = dbox.shape[0]
+    dfr, dsc = np.asarray(det_frame, np.int32).reshape(k), np.asarray(det_score, np.float32).reshape(k)
+    dup_of = np.full(b, -1, np.int32) if dup_of is None else np.array(dup_of, np.int32).reshape(b)
+    seeded = np.full(b, -1, np.int32) if seeded is None else np.array(seeded, np.int32).reshape(b)
+    det_state = np.full(k, -1, np.int32)
+    kb, _ = boxes_from_keypoints_host(preds, mv, np.zeros((b, 4), np.float32), np.zeros(b, np.int32), min_score, 0, min_side)
+    score = np.zeros(b, np.float32)
+    for q in range(j):
+        score = np.where(mv[:, q] >= F(min_score), score + mv[:, q], score).astype(np.float32)
+    dup_t, match_t = F(dup_overlap), F(match_overlap)
+    with np.errstate(all="ignore"):
+        valid = ((dfr >= 0) & (dfr < n_frames) & np.isfinite(dbox).all(1) & (dbox[:, 2] > dbox[:, 0]) & (dbox[:, 3] > dbox[:, 1])
+                 & np.isfinite(dsc) & (dsc >= F(det_min_score)))
+        for f in range(int(n_frames)):
+            members = [int(i) for i in np.nonzero(fidx == f)[0]]
+            kept, suppressed = [], set()
+            for i in sorted((i for i in members if lost[i] == 0), key=lambda i: (-score[i], i)):
+                hit = next((q for q in kept if _over_host(kb[i], kb[q], dup_t)), None)
+                if hit is None:
+                    kept.append(i)
+                else:
+                    suppressed.add(i)
+                    dup_of[i], lost[i], nbox[i], count[i] = hit, 1, 0, 0
+            for i in members:
+                seeded[i] = -1
+                if i in kept:
+                    dup_of[i], count[i] = -1, 0
+                elif i in suppressed:
+                    pass
+                elif src[i] < 0:
+                    dup_of[i], count[i] = -1, 0
+                else:
+                    dup_of[i] = -1
+                    count[i] = count[i] + 1 if count[i] < (1 << 30) else (1 << 30)
+                    if max_lost > 0 and count[i] >= max_lost:
+                        nbox[i], count[i] = 0, 0
+            free = [i for i in members if i not in kept]
+            accepted = []
+            for d in sorted((int(d) for d in np.nonzero(valid & (dfr == f))[0]), key=lambda d: (-dsc[d], d)):
+                if any(_over_host(dbox[d], kb[i], match_t) for i in kept):
+                    det_state[d] = -2
+                elif any(_over_host(dbox[d], dbox[e], match_t) for e in accepted):
+                    det_state[d] = -3
+                elif len(accepted) >= len(free):
+                    det_state[d] = -4
+                else:
+                    i = free[len(accepted)]
+                    accepted.append(d)
+                    det_state[d], seeded[i], nbox[i], count[i] = i, d, dbox[d], 0
+                    if nrot is not None:
+                        nrot[i] = (1, 0)
+    return nbox, nrot, lost, count, dup_of, seeded, det_state
+
+
 def rot_from_angle(radians):
     """The orientation (cos, sin) of a crop turned by ``radians`` in the image plane (x to the right, y down: a positive angle turns
     the crop's +x axis towards the frame's +y).  The kernels take the direction, never the angle."""
@@ -883,3 +976,33 @@ def one_euro(x, dt, state, src_frame, lost=None, min_cutoff=1.0, beta=0.007, d_c
                                            b, j, float(min_cutoff), float(beta), float(d_cutoff), xhat.data_ptr(), dxhat.data_ptr(),
                                            init.data_ptr(), out.data_ptr(), _stream()), "lh_one_euro")
     return out
+
+
+def manage_tracks(preds, maxvals, src_frame, frame_index, n_frames, next_boxes, next_rot, lost, lost_count, det_boxes, det_frame, det_score,
+                  dup_of, seeded, det_state, min_score=0.1, min_side=16.0, dup_overlap=0.5, match_overlap=0.5, det_min_score=0.0, max_lost=0):
+    """One lh_tracks_manage launch on the current stream, on contiguous device tensors: preds fp32 [b][j][2], maxvals fp32 [b][j] or
+    [b][j][1], src_frame / frame_index int32 [b], the detection list det_boxes fp32 [k][4], det_frame int32 [k], det_score fp32 [k];
+    next_boxes fp32 [b][4], next_rot fp32 [b][2] or None, lost / lost_count int32 [b] are UPDATED IN PLACE, dup_of / seeded int32 [b] and
+    det_state int32 [k] are written (a slot of no frame keeps what they held).  The rule: manage_tracks_host."""
+    import torch
+    from . import _lib
+    b, j = preds.shape[:2]
+    k = det_boxes.shape[0]
+    f32 = [(preds, (b, j, 2)), (next_boxes, (b, 4)), (det_boxes, (k, 4)), (det_score, (k,))] + ([(next_rot, (b, 2))] if next_rot is not None else [])
+    i32 = [(t, (b,)) for t in (src_frame, frame_index, lost, lost_count, dup_of, seeded)] + [(det_frame, (k,)), (det_state, (k,))]
+    good = (preds.is_cuda and maxvals.dtype == torch.float32 and maxvals.is_contiguous() and maxvals.numel() == b * j and maxvals.device == preds.device
+            and all(t.dtype == torch.float32 and tuple(t.shape) == shape for t, shape in f32)
+            and all(t.dtype == torch.int32 and tuple(t.shape) == shape for t, shape in i32)
+            and all(t.is_contiguous() and t.device == preds.device for t, _ in f32 + i32))
+    if not good:
+        raise _lib.LightHandError("manage_tracks: contiguous tensors on one device -- fp32 preds [b, j, 2], maxvals [b, j], next_boxes [b, 4], "
+                                  "next_rot [b, 2] or None, det_boxes [k, 4], det_score [k]; int32 src_frame, frame_index, lost, lost_count, "
+                                  "dup_of, seeded [b], det_frame, det_state [k]")
+    with torch.cuda.device(preds.device):
+        _lib.check(_lib.load().lh_tracks_manage(preds.data_ptr(), maxvals.data_ptr(), src_frame.data_ptr(), frame_index.data_ptr(), b, j,
+                                                int(n_frames), det_boxes.data_ptr(), det_frame.data_ptr(), det_score.data_ptr(), k,
+                                                float(min_score), float(min_side), float(dup_overlap), float(match_overlap),
+                                                float(det_min_score), int(max_lost), next_boxes.data_ptr(),
+                                                None if next_rot is None else next_rot.data_ptr(), lost.data_ptr(), lost_count.data_ptr(),
+                                                dup_of.data_ptr(), seeded.data_ptr(), det_state.data_ptr(), _stream()), "lh_tracks_manage")
+    return next_boxes, next_rot, lost, lost_count, dup_of, seeded, det_state

@@ -14,7 +14,9 @@ against the frames and the frames+antialias legs, same boxes.  Four legs price w
 leg: "nv12 copy" pays a device-to-device copy of all 32 frames into ``step.frames`` in front of every replay (what a pipeline whose
 decoder sits on the same GPU pays with a frame buffer), "nv12 surfaces" binds the 32 frames where they lie in front of every replay
 (InferStep(surfaces=True): 32 addresses instead of 99.5 MB), "yuv420p surfaces" and "p010 surfaces" do the same for the planar and the
-10-bit format (lh_frames_crop_surfaces_to_nhwc4 in the crop's place in all three).  Device events around `steps` replays, after a
+10-bit format (lh_frames_crop_surfaces_to_nhwc4 in the crop's place in all three).  One leg prices track management against the
+oriented + track leg of the same run: ManagedInferStep(oriented + track) adds the lh_tracks_manage launch and hands over a full detection
+list (64 boxes, two per frame, seeded) in front of every replay, three small copies and a fill.  Device events around `steps` replays, after a
 warm-up; median over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
@@ -26,7 +28,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from lighthand_amd.runtime import InferStep  # noqa: E402
+from lighthand_amd.runtime import InferStep, ManagedInferStep  # noqa: E402
 
 
 def timed(step, n, feed=None):
@@ -97,6 +99,14 @@ def main():
         feeds[tag] = dict(surfaces=src)
     for tag, feed in feeds.items():
         forms[tag](boxes=boxes, frame_index=index, **feed)
+    # a detector's output per replay (drawn after every draw above): as many boxes as slots, two per frame, any score
+    det_c = np.stack([rng.uniform(200, ws - 200, size=batch), rng.uniform(200, hs - 200, size=batch)], 1)
+    det_h = rng.uniform(75, 250, size=(batch, 1))
+    dets = (torch.from_numpy(np.concatenate([det_c - det_h, det_c + det_h], 1).astype(np.float32)).cuda(), index.clone(),
+            torch.from_numpy(rng.uniform(0, 1, size=batch).astype(np.float32)).cuda())
+    forms["oriented+track+manage"] = ManagedInferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True)
+    feeds["oriented+track+manage"] = dict(detections=dets)
+    forms["oriented+track+manage"](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror, detections=dets)
     for tag, step in forms.items():
         timed(step, 10, feeds.get(tag))                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
@@ -106,6 +116,10 @@ def main():
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
     for tag, v in ms.items():
+        if tag == "oriented+track+manage":
+            print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['oriented+track']:+.3f} vs oriented+track; rounds: "
+                  f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
+            continue
         if tag in feeds:
             print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['nv12']:+.3f} vs nv12; rounds: {', '.join(f'{x:.3f}' for x in v)})",
                   flush=True)
