@@ -255,6 +255,37 @@ int lh_tracks_manage(const float* preds_dev, const float* maxvals_dev, const int
                      float track_min_score, float track_min_side, float dup_overlap, float match_overlap, float det_min_score, int max_lost,
                      float* next_boxes_dev, float* next_rot_dev, int* lost_dev, int* lost_count_dev, int* dup_of_dev, int* seeded_dev,
                      int* det_state_dev, void* stream);
+/* Motion-aware tracking (opt-in; runtime.ManagedInferStep(frames=..., track=True, motion=..., smooth=..., smooth_gate=...)).  All
+ * arithmetic is fp32 in the order written, with + - * /, fabsf, fminf / fmaxf and comparisons only.
+ * lh_rois_predict: ROI velocity prediction and coasting, one launch behind lh_keypoints_to_boxes / lh_keypoints_to_rois and
+ * lh_tracks_manage and in front of the filter.  It edits next_boxes_dev fp32 [b][4] in place -- a translation, so it serves upright
+ * and oriented ROIs alike -- and keeps the state centre_dev fp32 [b][2], vel_dev fp32 [b][2] (frame px / s), seen_dev int32 [b],
+ * coasted_dev int32 [b].  lost_dev, src_frame_dev int32 [b], seeded_dev int32 [b] (lh_tracks_manage's; may be NULL) and dt_dev fp32
+ * [b] (seconds since the slot's previous frame) are read.  Slot i, (x0, y0, x1, y1) its incoming box, okdt = dt > 0 && isfinite(dt):
+ *  1. reset -- src_frame < 0, or seeded[i] >= 0, or !(x1-x0 > 0 && y1-y0 > 0): seen = 0, vel = 0, coasted = 0; the box stays.
+ *  2. lost != 0: if seen && okdt && coasted < coast: s = vel * dt per axis clamped to +-lim (step 3's), added to the box and to centre,
+ *     ++coasted; otherwise seen = 0, vel = 0.
+ *  3. found: c = ((x0+x1)*0.5, (y0+y1)*0.5).  If !seen || !okdt: centre = c, vel = 0, seen = 1, coasted = 0, no shift.  Otherwise
+ *     vm = (c - centre) / dt, r = (6.2831855f * cutoff) * dt, a = r / (r + 1.f), vel = a * vm + (1.f - a) * vel (lh_one_euro's
+ *     derivative low-pass); centre = c, coasted = 0; a vel that is not finite becomes 0 and nothing moves; else
+ *     lim = max_shift * fmaxf(x1-x0, y1-y0), s = fminf(fmaxf((lead * vel) * dt, -lim), lim) per axis, added to x0, x1 / y0, y1.
+ * One thread per slot, no atomics.  cutoff (Hz) > 0, lead >= 0, max_shift >= 0, all finite; coast >= 0; b > 0.
+ * lh_one_euro_gated: lh_one_euro with a confidence gate per joint and, with by_size != 0, beta multiplying a speed in hand sizes per
+ * second; in lh_one_euro's place, never beside it.  x_dev, xhat_dev, dxhat_dev, out_dev as lh_one_euro's; maxvals_dev fp32 [b][j];
+ * next_boxes_dev fp32 [b][4] (read with by_size only; may be NULL without); state seen_j_dev int32 [b][j] (in the place of init) and
+ * gap_dev fp32 [b][j], the seconds a joint has gone without an update.  An away slot (src_frame < 0, or lost_dev non-NULL and set)
+ * passes x through and zeroes its seen_j and gap.  Otherwise per joint: gated out (!(maxval >= gate_min_score)): out = seen_j ? xhat :
+ * x, the state stays, gap += dt when dt > 0 and finite.  Gated in: T = gap + dt; if !seen_j or T is not > 0 and finite: xhat = x,
+ * dxhat = 0, out = x; else lh_one_euro's update with T for dt and fc = min_cutoff + beta * speed, speed = fabsf(dxhat'), or with
+ * by_size fabsf(dxhat') / fmaxf(fmaxf(x1-x0, y1-y0), 1.f); then seen_j = 1, gap = 0.  With gate_min_score = -3.0e38f, by_size = 0 and
+ * finite maxvals, out / xhat / dxhat are lh_one_euro's bit for bit over any sequence of frames (T = 0 + dt).  One workgroup of 64
+ * threads per slot, one thread per coordinate (strided); a joint's seen_j and gap are written by one thread behind a barrier. */
+int lh_rois_predict(float* next_boxes_dev, const int* lost_dev, const int* src_frame_dev, const int* seeded_dev, const float* dt_dev, int b,
+                    float cutoff, float lead, float max_shift, int coast, float* centre_dev, float* vel_dev, int* seen_dev, int* coasted_dev,
+                    void* stream);
+int lh_one_euro_gated(const float* x_dev, const float* maxvals_dev, const float* next_boxes_dev, const int* src_frame_dev, const int* lost_dev,
+                      const float* dt_dev, int b, int j, float min_cutoff, float beta, float d_cutoff, float gate_min_score, int by_size,
+                      float* xhat_dev, float* dxhat_dev, int* seen_j_dev, float* gap_dev, float* out_dev, void* stream);
 /* Training on hand ROIs cropped from full frames (opt-in; runtime.TrainStep(frames=..., roi_aug=...)).
  * lh_roi_perturb: the caller's ROI (boxes_dev fp32 [b][4], rot_dev fp32 [b][2] or NULL = (1, 0), mirror_dev int32 [b] or NULL = 0) and
  * this step's draw aug_dev fp32 [b][6] = (c, s, k, tx, ty, flip) -> the ROI that lh_roi_affine reads (boxes_out, rot_out, mirror_out).

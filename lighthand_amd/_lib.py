@@ -148,6 +148,8 @@ SIGNATURES = {
     "lh_keypoints_to_rois": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P]),
     "lh_one_euro": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "lh_tracks_manage": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lh_rois_predict": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "lh_one_euro_gated": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P]),
     "lh_roi_perturb": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lh_affine_points_inv": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "lh_nhwc_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "color_jitter.h"
 #include "tracks_manage_kernel.h"
+#include "motion_kernel.h"
 
 // ------------------------------------------------------------------------------------------------ frames -> crops
 // Slot blockIdx.y reads frame src_frame[slot] of a buffer every slot shares: several boxes per frame, frames of any size.  The slot's
@@ -45,11 +46,14 @@ struct CropArgs {
     const long long* table;                                       // [n_frames] device addresses (0 = empty), or null: src + f * frame_stride
     int dsc[4];                                                   // LH_FRAMES_420 / 420W: c_pitch, cb_offset, cr_offset, c_step (with pitch, siting)
     TracksArgs tm;                                                // op = LH_CROP_TRACKS_MANAGE (lh_tracks_manage, tracks_manage_kernel.h): all it reads
+    PredictArgs pr;                                               // op = LH_CROP_ROIS_PREDICT (lh_rois_predict, motion_kernel.h): all it reads
+    GatedArgs og;                                                 // op = LH_CROP_ONE_EURO_GATED (lh_one_euro_gated, motion_kernel.h): all it reads
 };
 // frames_crop.hip: a launch of the fp32 instantiation with `grid` workgroups of `block` threads and `lds` bytes of dynamic LDS, for an
-// entry in another file (tracks_manage.hip); the caller runs LH_LAUNCH_CHECK.
+// entry in another file (tracks_manage.hip, motion.hip); the caller runs LH_LAUNCH_CHECK.
 void lh_frames_crop_launch_f32(const CropArgs& a, int grid, int block, size_t lds, void* stream);
-enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3, LH_CROP_TRACKS_MANAGE = 4 };
+enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3, LH_CROP_TRACKS_MANAGE = 4, LH_CROP_ROIS_PREDICT = 5,
+       LH_CROP_ONE_EURO_GATED = 6 };
 enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2, LH_JIT_STORE = 3 };      // STORE: no jitter, the store is jit.dtype's
 
 // What a jittered launch carries into the pixel loops: the slot's factors and order, then the grey mean (LH_JIT_APPLY) or the number
@@ -433,8 +437,12 @@ __device__ __forceinline__ void crop_aux_modes(const CropArgs& p) {
 template <typename T>
 __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the modes (CropArgs)
-        if (p.op == LH_CROP_ROI_PERTURB || p.op == LH_CROP_POINTS_INV) {
-            crop_aux_modes(p);
+        // one branch for the four thread-per-item modes: with a test of their own in front of the crop the two of motion_kernel.h took this
+        // instantiation from 71 to 85 vector registers (7 waves a SIMD to 6); behind this one it allocates what it did
+        if (p.op == LH_CROP_ROI_PERTURB || p.op == LH_CROP_POINTS_INV || p.op >= LH_CROP_ROIS_PREDICT) {
+            if (p.op == LH_CROP_ROIS_PREDICT) rois_predict_slot(p.pr);               // grid (b / 64), 64 threads: lh_rois_predict's launch alone
+            else if (p.op == LH_CROP_ONE_EURO_GATED) one_euro_gated_slot(p.og);      // grid (b), 64 threads: lh_one_euro_gated's launch alone
+            else crop_aux_modes(p);
             return;
         }
         if (p.op == LH_CROP_TRACKS_MANAGE) {                      // grid (n_frames), 64 threads, dynamic LDS: lh_tracks_manage's launch alone

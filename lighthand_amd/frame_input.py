@@ -174,6 +174,54 @@ def _check_manage_tracks(fi, track, manage_tracks, batch):
     return out
 
 
+def _check_motion(fi, track, motion):
+    """ManagedInferStep / ManagedInferPipeline(motion=) behind _check_tracking: refuse what cannot run, before any device work.  None /
+    False: None (the step as it was).  True or a dict of ``cutoff`` (Hz, > 0; 10.0), ``lead`` (>= 0; 1.0), ``max_shift`` (>= 0, in box
+    sides; 0.5) and ``coast`` (an integer >= 0; 0) -> the dict with every key, as floats / int."""
+    if motion is None or motion is False:
+        return None
+    if motion is not True and not isinstance(motion, dict):
+        raise ValueError(f"motion must be None, True or a dict of options, not {motion!r}")
+    if not track or fi.frames is None:
+        raise ValueError("motion= predicts the next ROI of a tracked step: pass frames=(n_frames, hs, ws), track=True")
+    given = {} if motion is True else dict(motion)
+    unknown = sorted(set(given) - set(topdown.MOTION_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"motion: unknown keys {unknown!r}; it takes " + ", ".join(topdown.MOTION_DEFAULTS))
+    out = dict(topdown.MOTION_DEFAULTS)
+    out.update(given)
+    if not _is_number(out["cutoff"]) or not 0 < out["cutoff"] <= 3.0e38:
+        raise ValueError(f"motion: cutoff must be a finite number > 0 (Hz), not {out['cutoff']!r}")
+    for key in ("lead", "max_shift"):
+        if not _is_number(out[key]) or not 0 <= out[key] <= 3.0e38:
+            raise ValueError(f"motion: {key} must be a finite number >= 0, not {out[key]!r}")
+    if not isinstance(out["coast"], numbers.Integral) or isinstance(out["coast"], bool) or not 0 <= out["coast"] < 2 ** 31:
+        raise ValueError(f"motion: coast must be an integer >= 0, not {out['coast']!r}")
+    return dict(cutoff=float(out["cutoff"]), lead=float(out["lead"]), max_shift=float(out["max_shift"]), coast=int(out["coast"]))
+
+
+def _check_smooth_gate(smooth, smooth_gate, track_min_score):
+    """ManagedInferStep / ManagedInferPipeline(smooth_gate=) behind _check_tracking (``smooth`` is what it returned): refuse what cannot
+    run, before any device work.  None / False: None (lh_one_euro as it was).  True or a dict of ``min_score`` (finite; default: the
+    step's ``track_min_score``) and ``by_size`` (a bool; True) -> the dict with both keys."""
+    if smooth_gate is None or smooth_gate is False:
+        return None
+    if smooth_gate is not True and not isinstance(smooth_gate, dict):
+        raise ValueError(f"smooth_gate must be None, True or a dict of options, not {smooth_gate!r}")
+    if smooth is None:
+        raise ValueError("smooth_gate= gates the One-Euro filter: pass frames=(n_frames, hs, ws), smooth=(min_cutoff, beta)")
+    given = {} if smooth_gate is True else dict(smooth_gate)
+    unknown = sorted(set(given) - {"min_score", "by_size"}, key=str)
+    if unknown:
+        raise ValueError(f"smooth_gate: unknown keys {unknown!r}; it takes min_score, by_size")
+    min_score, by_size = given.get("min_score", track_min_score), given.get("by_size", True)
+    if not _is_number(min_score) or abs(min_score) > 3.0e38:
+        raise ValueError(f"smooth_gate: min_score must be a finite number, not {min_score!r}")
+    if not isinstance(by_size, bool):
+        raise ValueError(f"smooth_gate: by_size must be False or True, not {by_size!r}")
+    return dict(min_score=float(min_score), by_size=by_size)
+
+
 def _check_train_frames(model, frames, input_u8=None, geometric_aug=None, color_jitter=None, targets_from_joints=True, roi_aug=None,
                         coord_loss_weight=0.0, use_target_weight=False, crop_jitter=None, **frame_options):
     """TrainStep(frames=, roi_aug=, crop_jitter=) against the step's other options: refuse what cannot run, before any device work (no

@@ -3,7 +3,7 @@ import torch
 
 from . import _lib, heatmap
 from ._lib import LightHandError, check
-from .frame_input import FrameInput, _check_beta, _check_manage_tracks, _check_tracking, _FrameStep, _ptr
+from .frame_input import FrameInput, _check_beta, _check_manage_tracks, _check_motion, _check_smooth_gate, _check_tracking, _FrameStep, _ptr
 
 
 class InferStep(_FrameStep):
@@ -76,13 +76,15 @@ class InferStep(_FrameStep):
     and clear it, ``step(surfaces=seq, ...)`` binds and replays; the captured graph stays the same.  An unbound frame is empty: its
     slots crop exactly black (``valid`` keeps meaning ``src_frame >= 0``: whether a surface is bound is the caller's matter).  A
     surface may be overwritten or freed only after the step's stream has passed the replay that reads it.
-    Track management -- duplicate tracks, expiry, a detector's boxes -- is ManagedInferStep's, below."""
+    Track management -- duplicate tracks, expiry, a detector's boxes -- is ManagedInferStep's, below, and so are motion prediction
+    (``motion=``) and the gated filter (``smooth_gate=``)."""
 
     _serial = 0
     _frame_inputs = "frames / boxes / frame_index"
     _frames_take = "frames / boxes / frame_index, not images"
     _rot_also, _rot_first = "", False
     _manage_tracks_option, _detections = False, None               # ManagedInferStep(manage_tracks=) / its call's detections=
+    _motion_option, _smooth_gate_option = None, None               # ManagedInferStep(motion=, smooth_gate=)
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
@@ -96,6 +98,8 @@ class InferStep(_FrameStep):
         smooth = _check_tracking(model, fi, track=track, track_min_score=track_min_score, track_min_joints=track_min_joints,
                                  track_min_side=track_min_side, track_axis=track_axis, track_min_axis=track_min_axis, smooth=smooth)
         self.manage_tracks = _check_manage_tracks(fi, track, self._manage_tracks_option, batch)        # ManagedInferStep's
+        self.motion = _check_motion(fi, track, self._motion_option)                                    # ManagedInferStep's, as well
+        self.smooth_gate = _check_smooth_gate(smooth, self._smooth_gate_option, track_min_score)
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
         self.soft_argmax_beta = float(soft_argmax_beta)
@@ -111,6 +115,7 @@ class InferStep(_FrameStep):
         self.images = self.plan.use_uint8_input(*input_u8) if input_u8 else self.plan.img_nchw
         self.crop_preds = self.next_boxes = self.lost = self.next_rot = self.dt = self.smooth_preds = None
         self.det_boxes = self.det_frame = self.det_score = self.lost_count = self.dup_of = self.seeded = self.det_state = None
+        self.velocity = self.coasted = None
         self.track, self.smooth = bool(track) and fi.frames is not None, smooth
         self.track_min_score, self.track_min_joints, self.track_min_side = float(track_min_score), int(track_min_joints), float(track_min_side)
         self._use_frame_input(fi)
@@ -132,12 +137,21 @@ class InferStep(_FrameStep):
                     self.lost_count = torch.zeros(batch, dtype=torch.int32, device=dev)       # state: replays in a row a slot has been lost
                     self.dup_of, self.seeded = (torch.full((batch,), -1, dtype=torch.int32, device=dev) for _ in range(2))
                     self.det_state = torch.full((k,), -1, dtype=torch.int32, device=dev)
-            if smooth:
+            if smooth or self.motion:
                 self.dt = torch.full((batch,), 1.0 / 30.0, dtype=torch.float32, device=dev)
+            if self.motion:
+                # the predictor's state: the centre of the last box the hand was found in, its low-passed velocity (frame px / s),
+                # whether the slot has seen a frame, and the replays in a row it has coasted
+                self._centre, self.velocity = (torch.zeros(batch, 2, dtype=torch.float32, device=dev) for _ in range(2))
+                self._motion_seen, self.coasted = (torch.zeros(batch, dtype=torch.int32, device=dev) for _ in range(2))
+            if smooth:
                 self.smooth_preds = torch.zeros(batch, out.shape[1], 2, dtype=torch.float32, device=dev)
                 # the filter's state: the last filtered keypoints, their filtered derivative, and whether the slot has seen a frame
                 self._xhat, self._dxhat = torch.zeros_like(self.smooth_preds), torch.zeros_like(self.smooth_preds)
                 self._seen = torch.zeros(batch, dtype=torch.int32, device=dev)
+                if self.smooth_gate:                                # per joint in _seen's place, and the seconds a joint has gone without an update
+                    self._seen_j = torch.zeros(batch, out.shape[1], dtype=torch.int32, device=dev)
+                    self._gap = torch.zeros(batch, out.shape[1], dtype=torch.float32, device=dev)
         self.flip_test, self.shift_heatmap, self.post_process, self.blur_kernel = flip_test, shift_heatmap, post_process, int(blur_kernel)
         # flip test: the plain pass's maps are copied here, and the merge writes over them in place
         self.heatmaps = torch.zeros_like(out) if flip_test else out
@@ -196,7 +210,20 @@ class InferStep(_FrameStep):
                                                 mt["dup_overlap"], mt["match_overlap"], mt["det_min_score"], mt["max_lost"],
                                                 self.next_boxes.data_ptr(), _ptr(self.next_rot), self.lost.data_ptr(), self.lost_count.data_ptr(),
                                                 self.dup_of.data_ptr(), self.seeded.data_ptr(), self.det_state.data_ptr(), s), "lh_tracks_manage")
-            if self.smooth:
+            if self.motion:
+                mo = self.motion
+                check(self.lib.lh_rois_predict(self.next_boxes.data_ptr(), self.lost.data_ptr(), p.src_frame.data_ptr(), _ptr(self.seeded),
+                                               self.dt.data_ptr(), out.shape[0], mo["cutoff"], mo["lead"], mo["max_shift"], mo["coast"],
+                                               self._centre.data_ptr(), self.velocity.data_ptr(), self._motion_seen.data_ptr(),
+                                               self.coasted.data_ptr(), s), "lh_rois_predict")
+            if self.smooth_gate:                                    # in lh_one_euro's place, never beside it
+                sizes = self.next_boxes if self.track else self.boxes
+                check(self.lib.lh_one_euro_gated(self.preds.data_ptr(), self.maxvals.data_ptr(), sizes.data_ptr(), p.src_frame.data_ptr(),
+                                                 _ptr(self.lost), self.dt.data_ptr(), out.shape[0], out.shape[1], self.smooth[0], self.smooth[1],
+                                                 self.smooth[2], self.smooth_gate["min_score"], int(self.smooth_gate["by_size"]),
+                                                 self._xhat.data_ptr(), self._dxhat.data_ptr(), self._seen_j.data_ptr(), self._gap.data_ptr(),
+                                                 self.smooth_preds.data_ptr(), s), "lh_one_euro_gated")
+            elif self.smooth:
                 check(self.lib.lh_one_euro(self.preds.data_ptr(), p.src_frame.data_ptr(), _ptr(self.lost), self.dt.data_ptr(), out.shape[0],
                                            out.shape[1], self.smooth[0], self.smooth[1], self.smooth[2], self._xhat.data_ptr(),
                                            self._dxhat.data_ptr(), self._seen.data_ptr(), self.smooth_preds.data_ptr(), s), "lh_one_euro")
@@ -217,10 +244,22 @@ class InferStep(_FrameStep):
         through unfiltered and starts the filter again.  LightHandError on a step built without ``smooth=``, as advance()'s."""
         if not self.smooth:
             raise LightHandError("reset_filter() needs InferStep(frames=..., smooth=(min_cutoff, beta))")
-        if slots is None:
-            self._seen.zero_()
-        else:
-            self._seen[torch.as_tensor(slots, device=self._seen.device)] = 0
+        for state in (self._seen,) + ((self._seen_j, self._gap) if self.smooth_gate else ()):
+            if slots is None:
+                state.zero_()
+            else:
+                state[torch.as_tensor(slots, device=state.device)] = 0
+
+    def reset_motion(self, slots=None):
+        """Forget the motion state of ``slots`` (indices or a mask; None: all), on the device: ``velocity`` and ``coasted`` go to zero and
+        their next frame starts the predictor again, with no shift.  LightHandError on a step built without ``motion=``, as advance()'s."""
+        if not self.motion:
+            raise LightHandError("reset_motion() needs ManagedInferStep(frames=..., track=True, motion=True)")
+        for state in (self._motion_seen, self.velocity, self.coasted, self._centre):
+            if slots is None:
+                state.zero_()
+            else:
+                state[torch.as_tensor(slots, device=state.device)] = 0
 
     def reset_tracks(self, slots=None):
         """Zero ``lost_count`` of ``slots`` (indices or a mask; None: all), on the device: their expiry starts counting again.
@@ -258,7 +297,7 @@ class InferStep(_FrameStep):
 
     def __call__(self, images=None, frames=None, boxes=None, frame_index=None, rot=None, mirror=None, dt=None, surfaces=None):
         self._check_call(images is not None, frames, boxes, frame_index, rot, mirror, surfaces)
-        if dt is not None and not self.smooth:
+        if dt is not None and not (self.smooth or self.motion):
             raise ValueError("dt is the input of InferStep(frames=..., smooth=(min_cutoff, beta))")
         if images is not None:
             self.images.copy_(images, non_blocking=True)
@@ -283,8 +322,13 @@ class InferStep(_FrameStep):
             torch.cuda.synchronize()
             if self.smooth:
                 self._seen.zero_()                                  # the warm-up run is not a frame: the first replay starts the filter
+                if self.smooth_gate:
+                    self._seen_j.zero_()
+                    self._gap.zero_()
             if self.manage_tracks:
                 self.lost_count.copy_(lost_count)                   # nor does it count towards a slot's expiry
+            if self.motion:
+                self.reset_motion()                                 # nor is it a frame the predictor has seen
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._enqueue()
@@ -393,10 +437,27 @@ class ManagedInferStep(InferStep):
     ``detections=`` runs with an empty list: a list never seeds twice.  ``reset_tracks(slots=None)`` zeroes ``lost_count``.  The
     defaults (0.5 / 0.5 / 0.0 / 0, MediaPipe's similarity threshold for the overlaps) are a design choice, not measured.  ``mirror`` and
     ``frame_index`` stay the caller's; topdown.manage_tracks_host states the rule.
-    The two keywords live on this class, so InferStep's own signatures stay as they are."""
+    Motion-aware tracking, opt-in and with or without ``manage_tracks`` (both None: the launches above, nothing else):
+    ``motion=True`` or a dict, on top of ``frames=..., track=True``: lh_rois_predict runs behind the launches above and in front of the
+    filter and moves ``next_boxes`` to where the hand will be -- the box's centre is differenced against the last one over ``dt``,
+    low-passed at ``cutoff`` Hz (the One-Euro derivative filter) into ``velocity`` (fp32 [batch][2], frame px / s), and the box is
+    shifted by ``lead`` x velocity x dt, at most ``max_shift`` of its larger side per axis; a lost slot moves on along its last
+    velocity for up to ``coast`` replays in a row (``coasted`` counts them) before the track is forgotten.  An empty slot, one that
+    track management emptied or a detection just seeded, and a ``dt`` that is not finite and > 0 start the predictor fresh;
+    ``reset_motion(slots=None)`` does the same by hand.  ``next_rot``, ``lost`` and ``advance()`` are untouched, a translation serves
+    upright and oriented ROIs alike, and coasting moves the box but invents no keypoints.  ``step.dt`` and ``dt=`` exist with
+    ``motion`` as with ``smooth``.  topdown.rois_predict_host states the rule.
+    ``smooth_gate=True`` or a dict, on top of ``smooth=``: lh_one_euro_gated runs in lh_one_euro's place.  A joint whose maxval is
+    below ``min_score`` (default: ``track_min_score``) holds its filtered position instead of dragging the filter after a guess, and
+    its next confident frame is filtered over the whole time it was away; with ``by_size`` (default True) ``beta`` multiplies a
+    speed in hand sizes per second (the larger side of ``next_boxes``, or of ``boxes`` without ``track``, at least 1 px), so one
+    ``beta`` serves near and far hands.  With ``min_score=-3.0e38, by_size=False`` it is lh_one_euro bit for bit.
+    topdown.one_euro_gated_host states the rule.  The defaults of both (10 Hz / 1.0 / 0.5 / 0; ``track_min_score`` / True) are design
+    choices, not measured.
+    The keywords live on this class, so InferStep's own signatures stay as they are."""
 
-    def __init__(self, *args, manage_tracks=True, **kwargs):
-        self._manage_tracks_option = manage_tracks
+    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, **kwargs):
+        self._manage_tracks_option, self._motion_option, self._smooth_gate_option = manage_tracks, motion, smooth_gate
         super().__init__(*args, **kwargs)
 
     def __call__(self, *args, detections=None, **kwargs):
@@ -412,12 +473,14 @@ class ManagedInferStep(InferStep):
 class ManagedInferPipeline(InferPipeline):
     """InferPipeline whose slots are ManagedInferSteps: every argument of InferPipeline and ``manage_tracks`` as ManagedInferStep's, for
     every slot.  Every slot owns its detection list and its ``lost_count``; ``submit(detections=...)`` fills the list of the slot that
-    runs the ticket (``steps[i].dup_of`` / ``seeded`` / ``det_state`` / ``reset_tracks()``)."""
+    runs the ticket (``steps[i].dup_of`` / ``seeded`` / ``det_state`` / ``reset_tracks()``).  ``motion`` / ``smooth_gate``: as
+    ManagedInferStep's, for every slot; every slot owns its motion state and its filter state (``steps[i].velocity`` / ``coasted`` /
+    ``reset_motion()``)."""
 
     _step_class = ManagedInferStep
 
-    def __init__(self, *args, manage_tracks=True, **kwargs):
-        self._step_extra = dict(manage_tracks=manage_tracks)
+    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, **kwargs):
+        self._step_extra = dict(manage_tracks=manage_tracks, motion=motion, smooth_gate=smooth_gate)
         self._detections = None
         super().__init__(*args, **kwargs)
 

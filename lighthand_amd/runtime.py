@@ -12,6 +12,7 @@ This module is the import surface; the code lives by role in ``draws`` (the host
 options and what the two steps share), ``train_step`` and ``infer_step``.
 """
 from .draws import sample_affine, sample_color_jitter, sample_roi_aug  # noqa: F401
-from .frame_input import FrameInput, _antialias_taps, _check_manage_tracks, _check_train_frames  # noqa: F401
+from .frame_input import (FrameInput, _antialias_taps, _check_manage_tracks, _check_motion, _check_smooth_gate,  # noqa: F401
+                          _check_train_frames)
 from .infer_step import InferPipeline, InferStep, ManagedInferPipeline, ManagedInferStep  # noqa: F401
 from .train_step import TrainStep  # noqa: F401

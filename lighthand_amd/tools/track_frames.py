@@ -7,6 +7,7 @@ captured graph plus one device-to-device copy per frame, no host arithmetic in b
                     [--oriented] [--mirror] [--one_euro MIN_CUTOFF BETA] [--spin DEG_PER_FRAME] [--antialias [N]]
                     [--frame_format nv12|nv21|yuv420p|p010 [--yuv_matrix bt601|bt709] [--yuv_range limited|full]
                      [--chroma_siting left|center]] [--surfaces] [--detect_every N [--max_lost M]]
+                    [--motion [--motion_cutoff HZ] [--motion_lead F] [--coast N]] [--smooth_gate [--gate_min_score S] [--no_size_norm]]
 
 ``--synthetic N`` renders a seeded sequence of N frames: per hand a cluster of 21 bright discs drifting over a dim noise background
 (camera footage is not shipped; a real loop copies each captured frame into ``step.frames`` and its detector's boxes into
@@ -31,6 +32,11 @@ ground truth, the bounds of each hand's joints jittered by a few pixels with the
 N-th frame; hand 0 leaves the scene for the middle fifth of the sequence (its region is painted over with the background) and is
 detected once more on the frame it re-enters.  The line then also counts the slots that were seeded by a detection, suppressed as
 duplicates and expired after ``--max_lost`` lost frames in a row (default 0: never).
+``--motion`` predicts each next ROI from the box's low-passed velocity (runtime.ManagedInferStep(motion=dict(cutoff=HZ, lead=F, coast=N)):
+``--motion_cutoff`` Hz, default 10; ``--motion_lead`` frames of lead, default 1; ``--coast N`` replays a lost slot keeps moving, default 0);
+the line then also gives the mean speed of the found slots in frame px / s and the number of coasted slots.  ``--smooth_gate``, on top of
+``--one_euro``, gates the filter per joint at ``--gate_min_score`` (default: the tracking threshold) and measures speed in hand sizes
+unless ``--no_size_norm`` (ManagedInferStep(smooth_gate=dict(min_score=S, by_size=...))).
 With none of these the sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
@@ -64,6 +70,13 @@ def build_parser():
     ap.add_argument("--surfaces", action="store_true", help="one device tensor per frame, bound in place (no copy into a frame buffer)")
     ap.add_argument("--detect_every", default=0, type=int, metavar="N", help="manage the tracks on the device; ground-truth detections every N-th frame")
     ap.add_argument("--max_lost", default=0, type=int, metavar="M", help="with --detect_every: a slot lost M frames in a row is emptied (0: never)")
+    ap.add_argument("--motion", action="store_true", help="predict the next ROI from the box's velocity")
+    ap.add_argument("--motion_cutoff", default=10.0, type=float, metavar="HZ", help="with --motion: cut-off of the velocity's low-pass")
+    ap.add_argument("--motion_lead", default=1.0, type=float, metavar="F", help="with --motion: frames of lead")
+    ap.add_argument("--coast", default=0, type=int, metavar="N", help="with --motion: replays in a row a lost slot keeps moving")
+    ap.add_argument("--smooth_gate", action="store_true", help="with --one_euro: gate the filter per joint by confidence")
+    ap.add_argument("--gate_min_score", default=None, type=float, metavar="S", help="with --smooth_gate: the gate (default: the tracking threshold)")
+    ap.add_argument("--no_size_norm", action="store_true", help="with --smooth_gate: keep the filter's speed in frame pixels per second")
     return ap
 
 
@@ -85,6 +98,12 @@ def main(argv=None):
         ap.error("--antialias takes 1..8")
     if args.detect_every < 0 or args.max_lost < 0 or (args.max_lost and not args.detect_every):
         ap.error("--detect_every N >= 1 turns track management on; --max_lost M >= 0 needs it")
+    if not args.motion and (args.motion_cutoff, args.motion_lead, args.coast) != (10.0, 1.0, 0):
+        ap.error("--motion_cutoff / --motion_lead / --coast need --motion")
+    if args.smooth_gate and not args.one_euro:
+        ap.error("--smooth_gate needs --one_euro")
+    if not args.smooth_gate and (args.gate_min_score is not None or args.no_size_norm):
+        ap.error("--gate_min_score / --no_size_norm need --smooth_gate")
     hs, ws = args.frame_size
     if args.detect_every:
         import numpy as np
@@ -137,7 +156,14 @@ def main(argv=None):
         options["smooth"] = tuple(args.one_euro)
     if args.detect_every:
         options["manage_tracks"] = dict(max_lost=args.max_lost)
-    step = (ManagedInferStep if args.detect_every else InferStep)(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
+    managed = bool(args.detect_every or args.motion or args.smooth_gate)
+    if managed and not args.detect_every:
+        options["manage_tracks"] = False
+    if args.motion:
+        options["motion"] = dict(cutoff=args.motion_cutoff, lead=args.motion_lead, coast=args.coast)
+    if args.smooth_gate:
+        options["smooth_gate"] = dict(min_score=score if args.gate_min_score is None else args.gate_min_score, by_size=not args.no_size_norm)
+    step = (ManagedInferStep if managed else InferStep)(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
     step.boxes.copy_(torch.from_numpy(boxes))
     lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
     moved = torch.zeros((), dtype=torch.float64, device=step.lost.device)
@@ -151,6 +177,10 @@ def main(argv=None):
         step.reset_tracks()
         counts = torch.zeros(3, dtype=torch.int64, device=step.lost.device)      # seeded, suppressed, expired
         on_frame_0, given = torch.zeros(args.hands, dtype=torch.int32), 0
+    if args.motion:
+        step.reset_motion()
+        speed = torch.zeros(2, dtype=torch.float64, device=step.lost.device)      # sum of the found slots' speeds, their number
+        coasted = torch.zeros((), dtype=torch.int64, device=step.lost.device)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(args.synthetic):
@@ -164,6 +194,10 @@ def main(argv=None):
         else:
             step(**feed(t))
         lost += step.lost
+        if args.motion:
+            found = step.lost == 0
+            speed += torch.stack([(step.velocity.norm(dim=-1) * found).sum().double(), found.sum().double()])
+            coasted += (step.coasted > 0).sum()
         if args.one_euro:
             moved += (step.smooth_preds - step.preds).norm(dim=-1).mean().double()
         step.advance()
@@ -191,6 +225,11 @@ def main(argv=None):
         seeded, suppressed, expired = counts.tolist()
         result.update(detect_every=args.detect_every, max_lost=args.max_lost, detections=given, slots_seeded=seeded, slots_suppressed=suppressed,
                       slots_expired=expired)
+    if args.motion:
+        result.update(motion=dict(cutoff=args.motion_cutoff, lead=args.motion_lead, coast=args.coast),
+                      mean_speed_px_s=float(speed[0] / speed[1].clamp(min=1)), slots_coasted=int(coasted))
+    if args.smooth_gate:
+        result["smooth_gate"] = step.smooth_gate
     print(json.dumps(result))
     return result
 

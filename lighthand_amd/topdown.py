@@ -31,7 +31,11 @@ Normalize, csrc/color_jitter.h's four ops (``color_jitter_host``), Normalize -- 
 Decoder surfaces in place and the other 4:2:0 flavours (lh_frames_crop_surfaces_to_nhwc4, InferStep / TrainStep(frames=...,
 surfaces=True, frame_format="nv21" | "yuv420p" | "p010")): ``check_surface`` / ``surface_table`` are the host checks and the table of
 addresses, ``frames_crop(..., surfaces=[...])`` the launch, ``frames_crop_yuv420_host`` its rule in numpy -- the NV12 rule behind
-another texel fetch (frame_formats.py: the plane descriptor ``Yuv420Layout`` and what builds and checks one)."""
+another texel fetch (frame_formats.py: the plane descriptor ``Yuv420Layout`` and what builds and checks one).
+
+Motion-aware tracking (lh_rois_predict / lh_one_euro_gated, runtime.ManagedInferStep(motion=..., smooth_gate=...)): ``rois_predict``
+shifts the next ROIs along their low-passed velocity and coasts lost ones, ``one_euro_gated`` is the One-Euro filter gated per joint
+by confidence with its speed in hand sizes; ``rois_predict_host`` / ``one_euro_gated_host`` restate them in numpy, fp32 or fp64."""
 import numpy as np
 
 from .frame_formats import (FRAME_FORMATS, Yuv420Layout, check_frame_format, check_nv12_layout, check_yuv420_layout,  # noqa: F401
@@ -656,6 +660,108 @@ def one_euro_host64(x, dt, state=None, src_frame=None, lost=None, min_cutoff=1.0
     return one_euro_host(x, dt, state, src_frame, lost, min_cutoff, beta, d_cutoff, dtype=np.float64)
 
 
+GATE_OPEN = -3.0e38                  # gate_min_score that every finite maxval passes: lh_one_euro_gated is then lh_one_euro
+
+
+def one_euro_gated_host(x, maxvals, dt, state=None, src_frame=None, lost=None, next_boxes=None, min_cutoff=1.0, beta=0.007, d_cutoff=1.0,
+                        gate_min_score=GATE_OPEN, by_size=False, dtype=np.float32):
+    """One frame of the gated One-Euro filter, lh_one_euro_gated in numpy (``dtype=np.float64``: the same recurrence in fp64): x
+    [b][j][2], maxvals [b][j] or [b][j][1], dt [b] (or a scalar), state = (xhat, dxhat [b][j][2], seen_j int32 [b][j], gap [b][j]) of
+    the previous frame (None: nothing seen yet), src_frame / lost [b] (None: every slot is live), next_boxes [b][4] (read with
+    ``by_size``) -> (out [b][j][2], new state).  A joint with ``!(maxval >= gate_min_score)`` holds its filtered position and counts
+    the seconds in ``gap``; on its return the update runs over T = gap + dt.  The inputs are not modified."""
+    T = np.dtype(dtype).type
+    x = np.asarray(x, dtype)
+    b, j = x.shape[:2]
+    mv = np.asarray(maxvals, dtype).reshape(b, j)
+    dt = np.broadcast_to(np.asarray(dt, dtype), (b,)).reshape(b, 1)
+    if state is None:
+        state = (np.zeros_like(x), np.zeros_like(x), np.zeros((b, j), np.int32), np.zeros((b, j), dtype))
+    xhat, dxhat = np.asarray(state[0], dtype), np.asarray(state[1], dtype)
+    seen, gap = np.asarray(state[2], np.int32).reshape(b, j) != 0, np.asarray(state[3], dtype).reshape(b, j)
+    away = np.zeros(b, bool)
+    if src_frame is not None:
+        away |= np.asarray(src_frame).reshape(b) < 0
+    if lost is not None:
+        away |= np.asarray(lost).reshape(b) != 0
+    away = away.reshape(b, 1)
+    size = T(1)
+    if by_size:
+        box = np.asarray(next_boxes, dtype).reshape(b, 4)
+        size = np.fmax(np.fmax(box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]), T(1)).reshape(b, 1, 1)
+    with np.errstate(all="ignore"):
+        gin = mv >= T(gate_min_score)
+        span = gap + dt
+        fresh = ~seen | ~(span > 0) | ~np.isfinite(span)
+        s3 = span[:, :, None]
+        rd = (T(TWO_PI) * T(d_cutoff)) * s3
+        ad = rd / (rd + T(1))
+        dx = (x - xhat) / s3
+        dxh = ad * dx + (T(1) - ad) * dxhat
+        speed = np.abs(dxh) / size if by_size else np.abs(dxh)
+        fc = T(min_cutoff) + T(beta) * speed
+        r = (T(TWO_PI) * fc) * s3
+        al = r / (r + T(1))
+        nx = al * x + (T(1) - al) * xhat
+        okdt = (dt > 0) & np.isfinite(dt)
+        grown = np.where(okdt, gap + dt, gap)
+    upd, start, hold = (~away & gin & ~fresh)[:, :, None], (~away & gin & fresh)[:, :, None], (~away & ~gin & seen)[:, :, None]
+    new_xhat = np.where(upd, nx, np.where(start, x, xhat)).astype(dtype)
+    new_dxhat = np.where(upd, dxh, np.where(start, T(0), dxhat)).astype(dtype)
+    out = np.where(upd, nx, np.where(hold, xhat, x)).astype(dtype)
+    new_seen = np.where(away, 0, np.where(gin, 1, seen)).astype(np.int32)
+    new_gap = np.where(away | gin, T(0), grown).astype(dtype)
+    return out, (new_xhat, new_dxhat, new_seen, new_gap)
+
+
+MOTION_DEFAULTS = dict(cutoff=10.0, lead=1.0, max_shift=0.5, coast=0)
+
+
+def rois_predict_host(next_boxes, lost, src_frame, seeded, dt, state=None, cutoff=10.0, lead=1.0, max_shift=0.5, coast=0, dtype=np.float32):
+    """ROI velocity prediction and coasting, lh_rois_predict in numpy (``dtype=np.float64``: the same rule in fp64): next_boxes [b][4]
+    as lh_keypoints_to_boxes / lh_keypoints_to_rois (and lh_tracks_manage) left them, lost / src_frame [b], seeded [b] or None, dt [b]
+    (or a scalar), state = (centre [b][2], vel [b][2], seen int32 [b], coasted int32 [b]) of the previous frame (None: nothing seen
+    yet) -> (the shifted boxes [b][4], new state).  The rule, clause by clause, is in include/lighthand_hip.h.  The inputs are not
+    modified."""
+    T = np.dtype(dtype).type
+    box = np.asarray(next_boxes, dtype).reshape(-1, 4)
+    b = box.shape[0]
+    lost = np.asarray(lost).reshape(b) != 0
+    dt = np.broadcast_to(np.asarray(dt, dtype), (b,)).reshape(b, 1)
+    if state is None:
+        state = (np.zeros((b, 2), dtype), np.zeros((b, 2), dtype), np.zeros(b, np.int32), np.zeros(b, np.int32))
+    centre, vel = np.asarray(state[0], dtype).reshape(b, 2), np.asarray(state[1], dtype).reshape(b, 2)
+    seen, coasted = np.asarray(state[2], np.int32).reshape(b) != 0, np.asarray(state[3], np.int32).reshape(b)
+    bw, bh = box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]
+    reset = (np.asarray(src_frame).reshape(b) < 0) | ~((bw > 0) & (bh > 0))
+    if seeded is not None:
+        reset |= np.asarray(seeded).reshape(b) >= 0
+    with np.errstate(all="ignore"):
+        okdt = ((dt > 0) & np.isfinite(dt)).reshape(b)
+        lim = (T(max_shift) * np.fmax(bw, bh)).reshape(b, 1)
+        coasting = ~reset & lost & seen & okdt & (coasted < int(coast))
+        forget = ~reset & lost & ~coasting
+        found = ~reset & ~lost
+        fresh = found & (~seen | ~okdt)
+        c = np.stack([(box[:, 0] + box[:, 2]) * T(0.5), (box[:, 1] + box[:, 3]) * T(0.5)], 1)
+        vm = (c - centre) / dt
+        r = (T(TWO_PI) * T(cutoff)) * dt
+        al = r / (r + T(1))
+        nv = al * vm + (T(1) - al) * vel
+        bad = found & ~fresh & ~np.isfinite(nv).all(1)
+        good = found & ~fresh & ~bad
+        s_coast = np.fmin(np.fmax(vel * dt, -lim), lim)
+        s_lead = np.fmin(np.fmax((T(lead) * nv) * dt, -lim), lim)
+        s = np.where(coasting[:, None], s_coast, s_lead)
+        moved = (coasting | good)[:, None]
+        out = np.where(np.tile(moved, (1, 4)), box + np.tile(s, (1, 2)), box).astype(dtype)
+        new_centre = np.where(coasting[:, None], centre + s_coast, np.where(found[:, None], c, centre)).astype(dtype)
+    new_vel = np.where((reset | forget | fresh | bad)[:, None], T(0), np.where(good[:, None], nv, vel)).astype(dtype)
+    new_seen = np.where(reset | forget, 0, np.where(found, 1, seen)).astype(np.int32)
+    new_coasted = np.where(reset | found, 0, np.where(coasting, coasted + 1, coasted)).astype(np.int32)
+    return out, (new_centre, new_vel, new_seen, new_coasted)
+
+
 def _stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
@@ -1006,3 +1112,58 @@ def manage_tracks(preds, maxvals, src_frame, frame_index, n_frames, next_boxes, 
                                                 None if next_rot is None else next_rot.data_ptr(), lost.data_ptr(), lost_count.data_ptr(),
                                                 dup_of.data_ptr(), seeded.data_ptr(), det_state.data_ptr(), _stream()), "lh_tracks_manage")
     return next_boxes, next_rot, lost, lost_count, dup_of, seeded, det_state
+
+
+def rois_predict(next_boxes, lost, src_frame, seeded, dt, state, cutoff=10.0, lead=1.0, max_shift=0.5, coast=0):
+    """One lh_rois_predict launch on the current stream, on contiguous device tensors: next_boxes fp32 [b][4] and state = (centre fp32
+    [b][2], vel fp32 [b][2], seen int32 [b], coasted int32 [b]) are UPDATED IN PLACE (fresh state: zeros); lost / src_frame int32 [b],
+    seeded int32 [b] or None and dt fp32 [b] are read.  The rule: rois_predict_host."""
+    import torch
+    from . import _lib
+    centre, vel, seen, coasted = state
+    b = next_boxes.shape[0]
+    f32 = [(next_boxes, (b, 4)), (centre, (b, 2)), (vel, (b, 2)), (dt, (b,))]
+    i32 = [(t, (b,)) for t in (lost, src_frame, seen, coasted) + ((seeded,) if seeded is not None else ())]
+    good = (next_boxes.is_cuda and all(torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == shape for t, shape in f32)
+            and all(torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == shape for t, shape in i32)
+            and all(t.is_contiguous() and t.device == next_boxes.device for t, _ in f32 + i32))
+    if not good:
+        raise _lib.LightHandError("rois_predict: contiguous tensors on one device -- fp32 next_boxes [b, 4], centre, vel [b, 2], dt [b]; int32 lost, "
+                                  "src_frame, seen, coasted [b], seeded [b] or None")
+    with torch.cuda.device(next_boxes.device):
+        _lib.check(_lib.load().lh_rois_predict(next_boxes.data_ptr(), lost.data_ptr(), src_frame.data_ptr(),
+                                               None if seeded is None else seeded.data_ptr(), dt.data_ptr(), b, float(cutoff), float(lead),
+                                               float(max_shift), int(coast), centre.data_ptr(), vel.data_ptr(), seen.data_ptr(),
+                                               coasted.data_ptr(), _stream()), "lh_rois_predict")
+    return next_boxes
+
+
+def one_euro_gated(x, maxvals, dt, state, src_frame, lost=None, next_boxes=None, min_cutoff=1.0, beta=0.007, d_cutoff=1.0,
+                   gate_min_score=GATE_OPEN, by_size=False, out=None):
+    """One frame of the gated One-Euro filter on device tensors: x fp32 [b][j][2], maxvals fp32 [b][j] or [b][j][1], dt fp32 [b], state =
+    (xhat, dxhat fp32 [b][j][2], seen_j int32 [b][j], gap fp32 [b][j]) UPDATED IN PLACE (fresh state: zeros), src_frame int32 [b], lost
+    int32 [b] or None, next_boxes fp32 [b][4] (needed with ``by_size``) -> out fp32 [b][j][2] (one lh_one_euro_gated launch on the current
+    stream).  The rule: one_euro_gated_host."""
+    import torch
+    from . import _lib
+    xhat, dxhat, seen_j, gap = state
+    b, j = x.shape[:2]
+    f32 = [(x, (b, j, 2)), (xhat, (b, j, 2)), (dxhat, (b, j, 2)), (gap, (b, j)), (dt, (b,))] + ([(next_boxes, (b, 4))] if next_boxes is not None else [])
+    i32 = [(seen_j, (b, j)), (src_frame, (b,))] + ([(lost, (b,))] if lost is not None else [])
+    good = (x.is_cuda and torch.is_tensor(maxvals) and maxvals.dtype == torch.float32 and maxvals.is_contiguous() and maxvals.numel() == b * j
+            and maxvals.device == x.device and (next_boxes is not None or not by_size)
+            and all(torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == shape for t, shape in f32)
+            and all(torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == shape for t, shape in i32)
+            and all(t.is_contiguous() and t.device == x.device for t, _ in f32 + i32))
+    if not good:
+        raise _lib.LightHandError("one_euro_gated: contiguous tensors on one device -- fp32 x, xhat, dxhat [b, j, 2], maxvals, gap [b, j], dt [b], "
+                                  "next_boxes [b, 4] (needed with by_size); int32 seen_j [b, j], src_frame [b], lost [b] or None")
+    if out is None:
+        out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().lh_one_euro_gated(x.data_ptr(), maxvals.data_ptr(), None if next_boxes is None else next_boxes.data_ptr(),
+                                                 src_frame.data_ptr(), None if lost is None else lost.data_ptr(), dt.data_ptr(), b, j,
+                                                 float(min_cutoff), float(beta), float(d_cutoff), float(gate_min_score), int(bool(by_size)),
+                                                 xhat.data_ptr(), dxhat.data_ptr(), seen_j.data_ptr(), gap.data_ptr(), out.data_ptr(), _stream()),
+                   "lh_one_euro_gated")
+    return out

@@ -16,7 +16,10 @@ decoder sits on the same GPU pays with a frame buffer), "nv12 surfaces" binds th
 (InferStep(surfaces=True): 32 addresses instead of 99.5 MB), "yuv420p surfaces" and "p010 surfaces" do the same for the planar and the
 10-bit format (lh_frames_crop_surfaces_to_nhwc4 in the crop's place in all three).  One leg prices track management against the
 oriented + track leg of the same run: ManagedInferStep(oriented + track) adds the lh_tracks_manage launch and hands over a full detection
-list (64 boxes, two per frame, seeded) in front of every replay, three small copies and a fill.  Device events around `steps` replays, after a
+list (64 boxes, two per frame, seeded) in front of every replay, three small copies and a fill.  Two legs price motion-aware tracking,
+ManagedInferStep(manage_tracks=False, ...): "oriented+track+motion" adds the lh_rois_predict launch (motion=True) and is reported against
+the oriented + track leg, "oriented+track+motion+gate" adds smooth= and smooth_gate=True on top (lh_one_euro_gated in lh_one_euro's place)
+and is reported against that and against the oriented + track + smooth leg.  Device events around `steps` replays, after a
 warm-up; median over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
@@ -107,6 +110,11 @@ def main():
     forms["oriented+track+manage"] = ManagedInferStep(model, batch, size, size, frames=(n_frames, hs, ws), track=True, oriented=True)
     feeds["oriented+track+manage"] = dict(detections=dets)
     forms["oriented+track+manage"](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror, detections=dets)
+    motion = dict(frames=(n_frames, hs, ws), track=True, oriented=True, manage_tracks=False, motion=True)
+    forms["oriented+track+motion"] = ManagedInferStep(model, batch, size, size, **motion)
+    forms["oriented+track+motion+gate"] = ManagedInferStep(model, batch, size, size, smooth=(1.0, 0.007), smooth_gate=True, **motion)
+    for tag in ("oriented+track+motion", "oriented+track+motion+gate"):
+        forms[tag](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
     for tag, step in forms.items():
         timed(step, 10, feeds.get(tag))                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
@@ -119,6 +127,10 @@ def main():
         if tag == "oriented+track+manage":
             print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['oriented+track']:+.3f} vs oriented+track; rounds: "
                   f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
+            continue
+        if tag.startswith("oriented+track+motion"):
+            print(f"  {tag:26s} {med[tag]:7.3f} ms/step median ({med[tag] - med['oriented+track']:+.3f} vs oriented+track, "
+                  f"{med[tag] - med['oriented+track+smooth']:+.3f} vs oriented+track+smooth; rounds: {', '.join(f'{x:.3f}' for x in v)})", flush=True)
             continue
         if tag in feeds:
             print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['nv12']:+.3f} vs nv12; rounds: {', '.join(f'{x:.3f}' for x in v)})",
