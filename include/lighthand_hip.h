@@ -286,6 +286,43 @@ int lh_rois_predict(float* next_boxes_dev, const int* lost_dev, const int* src_f
 int lh_one_euro_gated(const float* x_dev, const float* maxvals_dev, const float* next_boxes_dev, const int* src_frame_dev, const int* lost_dev,
                       const float* dt_dev, int b, int j, float min_cutoff, float beta, float d_cutoff, float gate_min_score, int by_size,
                       float* xhat_dev, float* dxhat_dev, int* seen_j_dev, float* gap_dev, float* out_dev, void* stream);
+/* Skeleton overlay (opt-in; runtime.ManagedInferStep(frames=..., overlay=...)): the tracked hands drawn into the frames IN PLACE, on
+ * the pixels around each hand only.  The frames are EITHER frames with frame_stride OR surface_table_dev, and layout says where their
+ * texels are, all three as lh_frames_crop_surfaces_to_nhwc4's (chroma_siting and csc12 are checked and not used: the kernel converts
+ * no colour and ignores chroma siting).  Per slot: preds_dev fp32 [b][j][2] (frame coordinates, pixel centres on the integers),
+ * maxvals_dev fp32 [b][j], src_frame_dev int32 [b], lost_dev int32 [b] (may be NULL), mat_dev fp32 [b][6] the slot's crop matrix of a
+ * crop_h x crop_w crop (may be NULL: no outline), boxes_dev fp32 [b][4] (may be NULL with by_size == 0).  parents_dev int32 [j] (-1 or
+ * outside 0..j-1: no bone), group_dev int32 [j] (the palette row of joint i and of the bone that ends in i), palette_dev fp32
+ * [n_groups + 2][3] in the frames' own plane space (R G B on 0..255; Y Cb Cr on the 8-bit scale, for p010 on the 10-bit scale); its
+ * last two rows colour the outline of a live and of a lost slot.  All arithmetic is fp32 in the order written.
+ *  s = by_size != 0 ? (bw > bh ? bw : bh) of the slot's box : 0, r_line = line_radius + by_size*s, r_joint = joint_radius + by_size*s.
+ *  The primitives of a slot, in this order: with mat_dev and draw_roi the four edges c0c1, c1c2, c2c3, c3c0 of the crop's quad, c =
+ *  (-.5, -.5), (w-.5, -.5), (w-.5, h-.5), (-.5, h-.5) through the matrix as the crop takes a pixel (fx = (m0*u + m1*v) + m2), radius
+ *  r_line, row n_groups, or n_groups + 1 for a lost slot (lost != 0), which draws nothing else; the bones i = 0..j-1 with a parent,
+ *  from joint parents[i] to joint i, when both maxvals are >= min_score, radius r_line, row group[i]; the joints i = 0..j-1 with
+ *  maxval >= min_score as segments of length 0, radius r_joint, row group[i].  A primitive with a coordinate or radius that is not
+ *  finite, or a row outside the palette, is skipped.  A slot with src_frame outside 0..n_frames-1, or on an unbound surface (table
+ *  entry 0, tested before an address is formed), draws nothing.
+ *  Coverage of the pixel (px, py) by the segment a -> b of radius r: d = (b - a), l2 = dx*dx + dy*dy, q = p - a, e = q; if l2 > 0:
+ *  t = (qx*dx + qy*dy) * (1.f / l2) clamped to 0..1 by comparison, e = q - t*d; k = (r + 0.5f) - sqrtf(ex*ex + ey*ey) clamped to
+ *  0..1 by comparison (a bone of length 0 is the disc of its end point).
+ *  A pixel starts from its texel as a float; for every primitive of every slot of its frame, slot after slot in index order, with
+ *  al = opacity * k > 0: c = c + al * (colour - c) per component; it ends as floorf(c + 0.5f) clamped to the texel range, and a
+ *  pixel no primitive covers is NOT WRITTEN.  4:2:0 frames: luma is such a plane; the chroma pair of a 2 x 2 luma block takes
+ *  al = (opacity * ((k00 + k01) + (k10 + k11))) * 0.25f and the palette's Cb / Cr.  p010 blends u16 >> 6 on the 10-bit scale
+ *  (0..1023) and stores code << 6; a texel that is not written keeps its low six bits.
+ * b * 8 workgroups of 256 threads, each walking its slot's draw bounds (the primitives' bounds grown by r + 1, clipped to the frame)
+ * in a grid-stride loop: nothing runs over whole frames, nothing is read or written outside a frame.  A pixel is owned by the lowest
+ * drawing slot of its frame whose bounds contain it, and the owner composites every slot whose bounds contain it: one writer per
+ * texel, no atomics, a replay is bit-reproducible.  (A mode of the fp32 frame-crop kernel with a launch of its own and dynamic LDS
+ * sized by b.)  LH_ERR_ARG: a NULL pointer beside those named; b outside 1..1024; j, n_groups, n_frames, crop_h or crop_w < 1;
+ * a radius or by_size that is negative or not finite, min_score not finite, opacity outside 0..1; the frame source and layout as
+ * lh_frames_crop_surfaces_to_nhwc4's; palette_dev equal to preds_dev or maxvals_dev. */
+int lh_draw_hands(unsigned char* frames, long frame_stride, const long long* surface_table_dev, const lh_frames_layout* layout, int n_frames,
+                  int hs, int ws, const float* preds_dev, const float* maxvals_dev, const int* src_frame_dev, const int* lost_dev,
+                  const float* mat_dev, const float* boxes_dev, int b, int j, int crop_h, int crop_w, const int* parents_dev,
+                  const int* group_dev, const float* palette_dev, int n_groups, float min_score, float line_radius, float joint_radius,
+                  float by_size, float opacity, int draw_roi, void* stream);
 /* Training on hand ROIs cropped from full frames (opt-in; runtime.TrainStep(frames=..., roi_aug=...)).
  * lh_roi_perturb: the caller's ROI (boxes_dev fp32 [b][4], rot_dev fp32 [b][2] or NULL = (1, 0), mirror_dev int32 [b] or NULL = 0) and
  * this step's draw aug_dev fp32 [b][6] = (c, s, k, tx, ty, flip) -> the ROI that lh_roi_affine reads (boxes_out, rot_out, mirror_out).

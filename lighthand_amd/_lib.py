@@ -150,6 +150,8 @@ SIGNATURES = {
     "lh_tracks_manage": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lh_rois_predict": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "lh_one_euro_gated": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "lh_draw_hands": (_I, [_P, _L, _P, C.POINTER(FramesLayout), _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F,
+                           _I, _P]),
     "lh_roi_perturb": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lh_affine_points_inv": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "lh_nhwc_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

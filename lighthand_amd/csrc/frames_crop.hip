@@ -132,26 +132,13 @@ extern "C" int lh_frames_crop_jitter_to_nhwc4(const unsigned char* frames, void*
                                max_taps, true, factors_dev, order_dev, workspace, dtype, stream}, frames, csc12 ? &yuv : nullptr);
 }
 
-// ------------------------------------------------------------------------------------------------ decoder surfaces, 4:2:0 flavours
-// The entry of the surface table and the plane descriptor (the rules: frames_crop_kernel.h, above crop_texel and above the kernel's
-// table load).  Every launch is the fp32 instantiation's, which stores in ``dtype``.  All of the layout is checked here, in front of
-// any launch: the kernel trusts it.
-extern "C" int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, void* out, long frame_stride, const long long* surface_table_dev,
-                                                const lh_frames_layout* layout, int b, int n_frames, int hs, int ws, int h, int w,
-                                                int pad, int wp, const float* mean3, const float* std3, const float* mat_dev,
-                                                const int* src_frame_dev, int max_taps, const float* factors_dev, const int* order_dev,
-                                                void* workspace, int dtype, void* stream) {
-    const char* who = "lh_frames_crop_surfaces_to_nhwc4";
-    const CropCall c = {who, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev, src_frame_dev, max_taps,
-                        factors_dev || order_dev || workspace, factors_dev, order_dev, workspace, dtype, stream};
-    LH_REQUIRE(frames || surface_table_dev, "%s: no frame source (frames and surface_table_dev are both null)", who);
-    LH_REQUIRE(!(frames && surface_table_dev), "%s: two frame sources (pass frames or surface_table_dev, not both)", who);
-    if (const int rc = crop_check(c, layout != nullptr, true, "crop")) return rc;
-    LH_REQUIRE(!surface_table_dev || ((uintptr_t)surface_table_dev & 7) == 0, "%s: surface_table_dev must be 8-byte aligned", who);
+// Where the frames of a plane descriptor are: every check of ``layout`` for hs x ws frames (and of the buffer ``frames`` /
+// ``frame_stride``, null: a surface table), and the fields of CropArgs the kernel finds a sample through -- format, pitch, siting, dsc,
+// k, o, frame_stride.  Shared with lh_draw_hands (draw_hands.hip), which writes through the same descriptor.
+int lh_frames_layout_args(const char* who, const lh_frames_layout* layout, int hs, int ws, const unsigned char* frames, long frame_stride,
+                          CropArgs& a) {
     const int f = layout->format;
     LH_REQUIRE(f >= LH_FRAMES_FMT_RGB && f <= LH_FRAMES_FMT_P010, "%s: unknown format code %d", who, f);
-    CropArgs a = crop_args(c);
-    a.src = frames; a.table = surface_table_dev; a.gen = 1;
     long need;                                                    // the highest byte a sample can touch, plus one
     if (f == LH_FRAMES_FMT_RGB) {
         need = (long)hs * ws * 3;
@@ -193,6 +180,28 @@ extern "C" int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, voi
     LH_REQUIRE(need < (1L << 31), "%s: a frame of %ld bytes does not fit 32-bit byte indices", who, need);
     LH_REQUIRE(!frames || frame_stride >= need, "%s: frame_stride %ld is below the %ld bytes a frame's samples span", who, frame_stride, need);
     a.frame_stride = frames ? frame_stride : 0;
+    return LH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ decoder surfaces, 4:2:0 flavours
+// The entry of the surface table and the plane descriptor (the rules: frames_crop_kernel.h, above crop_texel and above the kernel's
+// table load).  Every launch is the fp32 instantiation's, which stores in ``dtype``.  All of the layout is checked here, in front of
+// any launch: the kernel trusts it.
+extern "C" int lh_frames_crop_surfaces_to_nhwc4(const unsigned char* frames, void* out, long frame_stride, const long long* surface_table_dev,
+                                                const lh_frames_layout* layout, int b, int n_frames, int hs, int ws, int h, int w,
+                                                int pad, int wp, const float* mean3, const float* std3, const float* mat_dev,
+                                                const int* src_frame_dev, int max_taps, const float* factors_dev, const int* order_dev,
+                                                void* workspace, int dtype, void* stream) {
+    const char* who = "lh_frames_crop_surfaces_to_nhwc4";
+    const CropCall c = {who, out, b, n_frames, hs, ws, h, w, pad, wp, mean3, std3, mat_dev, src_frame_dev, max_taps,
+                        factors_dev || order_dev || workspace, factors_dev, order_dev, workspace, dtype, stream};
+    LH_REQUIRE(frames || surface_table_dev, "%s: no frame source (frames and surface_table_dev are both null)", who);
+    LH_REQUIRE(!(frames && surface_table_dev), "%s: two frame sources (pass frames or surface_table_dev, not both)", who);
+    if (const int rc = crop_check(c, layout != nullptr, true, "crop")) return rc;
+    LH_REQUIRE(!surface_table_dev || ((uintptr_t)surface_table_dev & 7) == 0, "%s: surface_table_dev must be 8-byte aligned", who);
+    CropArgs a = crop_args(c);
+    a.src = frames; a.table = surface_table_dev; a.gen = 1;
+    if (const int rc = lh_frames_layout_args(who, layout, hs, ws, frames, frame_stride, a)) return rc;
     return crop_enqueue(c, a, "frames_crop_surfaces_to_nhwc4 grey-mean launch", "frames_crop_surfaces_to_nhwc4 launch");
 }
 

@@ -15,6 +15,7 @@
 // image_u8_kernel.  A gather over bytes: neighbouring lanes read neighbouring source pixels (a box maps rows to rows), the four taps
 // of a pixel share cache lines with its neighbours', and the frame's reuse across the boxes that read it is the L2's.
 enum { LH_FRAMES_RGB = 0, LH_FRAMES_NV12 = 1, LH_FRAMES_420 = 2, LH_FRAMES_420W = 3 };
+#include "draw_hands_kernel.h"                                    // (behind the format codes: it draws through them)
 
 struct CropArgs {
     const unsigned char* src;
@@ -48,12 +49,16 @@ struct CropArgs {
     TracksArgs tm;                                                // op = LH_CROP_TRACKS_MANAGE (lh_tracks_manage, tracks_manage_kernel.h): all it reads
     PredictArgs pr;                                               // op = LH_CROP_ROIS_PREDICT (lh_rois_predict, motion_kernel.h): all it reads
     GatedArgs og;                                                 // op = LH_CROP_ONE_EURO_GATED (lh_one_euro_gated, motion_kernel.h): all it reads
+    DrawArgs dr;                                                  // op = LH_CROP_DRAW_HANDS (lh_draw_hands, draw_hands_kernel.h): beside the fields it names
 };
 // frames_crop.hip: a launch of the fp32 instantiation with `grid` workgroups of `block` threads and `lds` bytes of dynamic LDS, for an
-// entry in another file (tracks_manage.hip, motion.hip); the caller runs LH_LAUNCH_CHECK.
+// entry in another file (tracks_manage.hip, motion.hip, draw_hands.hip); the caller runs LH_LAUNCH_CHECK.
 void lh_frames_crop_launch_f32(const CropArgs& a, int grid, int block, size_t lds, void* stream);
+// frames_crop.hip: the checks of a plane descriptor and the fields of ``a`` a kernel finds its samples through (lh_draw_hands shares them)
+int lh_frames_layout_args(const char* who, const lh_frames_layout* layout, int hs, int ws, const unsigned char* frames, long frame_stride,
+                          CropArgs& a);
 enum { LH_CROP = 0, LH_CROP_ROI_PERTURB = 1, LH_CROP_POINTS_INV = 2, LH_CROP_GREY_MEAN = 3, LH_CROP_TRACKS_MANAGE = 4, LH_CROP_ROIS_PREDICT = 5,
-       LH_CROP_ONE_EURO_GATED = 6 };
+       LH_CROP_ONE_EURO_GATED = 6, LH_CROP_DRAW_HANDS = 7 };
 enum { LH_JIT_NONE = 0, LH_JIT_APPLY = 1, LH_JIT_MEAN = 2, LH_JIT_STORE = 3 };      // STORE: no jitter, the store is jit.dtype's
 
 // What a jittered launch carries into the pixel loops: the slot's factors and order, then the grey mean (LH_JIT_APPLY) or the number
@@ -437,11 +442,15 @@ __device__ __forceinline__ void crop_aux_modes(const CropArgs& p) {
 template <typename T>
 __global__ __launch_bounds__(256) void frames_crop_kernel(const CropArgs p) {
     if constexpr (sizeof(T) == 4) {                               // the fp32 instantiation alone carries the modes (CropArgs)
-        // one branch for the four thread-per-item modes: with a test of their own in front of the crop the two of motion_kernel.h took this
+        // one branch for the four thread-per-item modes and the overlay: with a test of their own in front of the crop the two of motion_kernel.h took this
         // instantiation from 71 to 85 vector registers (7 waves a SIMD to 6); behind this one it allocates what it did
         if (p.op == LH_CROP_ROI_PERTURB || p.op == LH_CROP_POINTS_INV || p.op >= LH_CROP_ROIS_PREDICT) {
             if (p.op == LH_CROP_ROIS_PREDICT) rois_predict_slot(p.pr);               // grid (b / 64), 64 threads: lh_rois_predict's launch alone
             else if (p.op == LH_CROP_ONE_EURO_GATED) one_euro_gated_slot(p.og);      // grid (b), 64 threads: lh_one_euro_gated's launch alone
+            else if (p.op == LH_CROP_DRAW_HANDS) {                                   // grid (b * DRAW_WGS), 256 threads, dynamic LDS: lh_draw_hands' launch alone
+                extern __shared__ __attribute__((aligned(16))) unsigned char tm_lds[];
+                draw_hands_slot(p, tm_lds);
+            }
             else crop_aux_modes(p);
             return;
         }

@@ -330,33 +330,40 @@ class _FrameStep:
         dimension is always k surfaces, one per row: ONE surface shaped [rows][pitch] goes in as ``[surface]`` (or flattened)."""
         if not self.surfaces:
             raise ValueError("surfaces are the input of a step built with frames=(n_frames, hs, ws), surfaces=True")
-        table = self.plan.surface_table
+        self._bind_table(self.plan.surface_table, self._surface_refs, self.plan.frame_layout, surfaces, start, "bind_surfaces")
+
+    @staticmethod
+    def _bind_table(table, refs, layout, surfaces, start, who):
+        """bind_surfaces on one table of addresses and its list of references (InferStep's overlay table is the other one)."""
         rows = torch.is_tensor(surfaces) and surfaces.dim() > 1
         seq = list(surfaces.unbind(0)) if rows else [surfaces] if torch.is_tensor(surfaces) else list(surfaces)
         if isinstance(start, bool) or not isinstance(start, numbers.Integral) or start < 0 or not seq or start + len(seq) > table.shape[0]:
-            raise ValueError(f"bind_surfaces: {len(seq)} surfaces from frame {start!r} on do not fit the step's {table.shape[0]} frames"
+            raise ValueError(f"{who}: {len(seq)} surfaces from frame {start!r} on do not fit the step's {table.shape[0]} frames"
                              + (f" (a tensor {tuple(surfaces.shape)} is bound row by row: pass one surface as [surface])" if rows else ""))
         try:
-            addresses = [topdown.check_surface(t, table.device, self.plan.frame_layout) for t in seq]
+            addresses = [topdown.check_surface(t, table.device, layout) for t in seq]
         except ValueError as e:
             if rows:                                                # name the likely cause: one surface taken for k rows
                 raise ValueError(f"{e} (a tensor {tuple(surfaces.shape)} is bound row by row, {len(seq)} surfaces of "
                                  f"{seq[0].numel()} bytes: pass one surface as [surface])") from None
             raise
         table[start:start + len(seq)].copy_(torch.tensor(addresses, dtype=torch.int64), non_blocking=True)      # from pageable memory
-        self._surface_refs[start:start + len(seq)] = seq
+        refs[start:start + len(seq)] = seq
 
     def unbind_surfaces(self, indices=None):
         """Zero the table entries of ``indices`` (None: all) and drop the references: such a frame is empty, its slots crop black."""
         if not self.surfaces:
             raise ValueError("surfaces are the input of a step built with frames=(n_frames, hs, ws), surfaces=True")
-        table = self.plan.surface_table
+        self._unbind_table(self.plan.surface_table, self._surface_refs, indices, "unbind_surfaces")
+
+    @staticmethod
+    def _unbind_table(table, refs, indices, who):
         if indices is None:
             indices = range(table.shape[0])
         indices = [int(i) for i in indices]
         if any(i < 0 or i >= table.shape[0] for i in indices):
-            raise ValueError(f"unbind_surfaces: indices within 0..{table.shape[0] - 1}, not {indices!r}")
+            raise ValueError(f"{who}: indices within 0..{table.shape[0] - 1}, not {indices!r}")
         if indices:
             table[torch.tensor(indices, dtype=torch.int64).to(table.device)] = 0
         for i in indices:
-            self._surface_refs[i] = None
+            refs[i] = None

@@ -1,7 +1,9 @@
 """InferStep: eval-mode forward + decode as one captured HIP graph; InferPipeline: several of them in flight."""
+import ctypes
+
 import torch
 
-from . import _lib, heatmap
+from . import _lib, heatmap, overlay as _overlay, topdown
 from ._lib import LightHandError, check
 from .frame_input import FrameInput, _check_beta, _check_manage_tracks, _check_motion, _check_smooth_gate, _check_tracking, _FrameStep, _ptr
 
@@ -85,6 +87,7 @@ class InferStep(_FrameStep):
     _rot_also, _rot_first = "", False
     _manage_tracks_option, _detections = False, None               # ManagedInferStep(manage_tracks=) / its call's detections=
     _motion_option, _smooth_gate_option = None, None               # ManagedInferStep(motion=, smooth_gate=)
+    _overlay_option, overlay, overlay_table = None, None, None     # ManagedInferStep(overlay=)
 
     def __init__(self, model, batch, height, width, bn_train=False, use_graph=True, input_u8=None, slot=0,
                  flip_test=False, shift_heatmap=True, post_process=False, plan_options=None, blur_kernel=11, soft_argmax_beta=100.0,
@@ -100,6 +103,8 @@ class InferStep(_FrameStep):
         self.manage_tracks = _check_manage_tracks(fi, track, self._manage_tracks_option, batch)        # ManagedInferStep's
         self.motion = _check_motion(fi, track, self._motion_option)                                    # ManagedInferStep's, as well
         self.smooth_gate = _check_smooth_gate(smooth, self._smooth_gate_option, track_min_score)
+        if self._overlay_option not in (None, False) and fi.frames is None:
+            raise ValueError("overlay= draws the tracked hands into full frames: pass frames=(n_frames, hs, ws)")
         post_process = heatmap.decode_mode(post_process)
         _check_beta(soft_argmax_beta)
         self.soft_argmax_beta = float(soft_argmax_beta)
@@ -159,6 +164,8 @@ class InferStep(_FrameStep):
         self.maxvals = torch.zeros(batch, out.shape[1], 1, dtype=torch.float32, device=dev)
         self.idx = torch.zeros(batch, out.shape[1], dtype=torch.int32, device=dev) if post_process in ("quarter", "dark") else None
         self.scale = float(height // out.shape[2])
+        if self._overlay_option not in (None, False):
+            self._use_overlay(fi, track_min_score)
         self.use_graph = use_graph
         self.graph = None
         self._packed = False
@@ -227,6 +234,51 @@ class InferStep(_FrameStep):
                 check(self.lib.lh_one_euro(self.preds.data_ptr(), p.src_frame.data_ptr(), _ptr(self.lost), self.dt.data_ptr(), out.shape[0],
                                            out.shape[1], self.smooth[0], self.smooth[1], self.smooth[2], self._xhat.data_ptr(),
                                            self._dxhat.data_ptr(), self._seen.data_ptr(), self.smooth_preds.data_ptr(), s), "lh_one_euro")
+            if self.overlay and not self._warming:                  # the last launch of the graph, behind the filter
+                self._enqueue_overlay(s)
+
+    _warming = False                                               # the eager run in front of the capture is not a frame: it draws nothing
+
+    def _use_overlay(self, fi, track_min_score):
+        """ManagedInferStep(overlay=): the resolved options (``self.overlay``), the topology and palette on the device, the frames'
+        layout, and with target="surfaces" the second surface table (``overlay_table``, zeros: every destination unbound)."""
+        dev = self.preds.device
+        o = _overlay.resolve_overlay(self._overlay_option, self.preds.shape[1], track_min_score, fi.frame_format, fi.yuv, self.smooth)
+        self._ov_layout = topdown.frame_layout_of(fi.frame_format, fi.frames[1], fi.frames[2], fi.frame_layout)
+        self._ov_desc = topdown.frames_layout_struct(self._ov_layout, fi.yuv, fi.chroma_siting)
+        self._ov_tables = [torch.from_numpy(o[k]).to(dev) for k in ("parents", "groups", "palette")]
+        self._ov_frames = fi.frames
+        if o["target"] == "surfaces":
+            self.overlay_table = torch.zeros(fi.frames[0], dtype=torch.int64, device=dev)
+            self._overlay_refs = [None] * fi.frames[0]
+        self.overlay = o
+
+    def _enqueue_overlay(self, s):
+        o, p = self.overlay, self.plan
+        n, hs, ws = self._ov_frames
+        table = self.overlay_table if o["target"] == "surfaces" else p.surface_table if self.surfaces else None
+        frames, stride = (None, 0) if table is not None else (self.frames.data_ptr(), self.frames.stride(0))
+        src = self.smooth_preds if o["source"] == "smooth" else self.preds
+        check(self.lib.lh_draw_hands(frames, stride, _ptr(table), ctypes.byref(self._ov_desc), n, hs, ws, src.data_ptr(), self.maxvals.data_ptr(),
+                                     p.src_frame.data_ptr(), _ptr(self.lost), p.crop_mat.data_ptr(), self.boxes.data_ptr(), src.shape[0],
+                                     src.shape[1], p.h, p.w, self._ov_tables[0].data_ptr(), self._ov_tables[1].data_ptr(),
+                                     self._ov_tables[2].data_ptr(), self._ov_tables[2].shape[0] - 2, o["min_score"], o["line_radius"],
+                                     o["joint_radius"], o["by_size"], o["opacity"], int(o["draw_roi"]), s), "lh_draw_hands")
+
+    def bind_overlay_surfaces(self, surfaces, start=0):
+        """Destination ``start + i`` of the overlay <- ``surfaces[i]`` (ManagedInferStep(overlay=dict(target="surfaces"))): bind_surfaces'
+        rules and checks on the second table, same layout as the frames; also on a step that crops a frame buffer.  The kernel never
+        reads the source frames, so the caller decides what a destination holds beforehand (a copy of the frame, as a rule).  A
+        destination may be reused only after the step's stream has passed the replay that draws on it."""
+        if self.overlay_table is None:
+            raise ValueError("overlay surfaces are the destinations of a step built with overlay=dict(target='surfaces')")
+        self._bind_table(self.overlay_table, self._overlay_refs, self._ov_layout, surfaces, start, "bind_overlay_surfaces")
+
+    def unbind_overlay_surfaces(self, indices=None):
+        """Zero the overlay table's entries of ``indices`` (None: all) and drop the references: nothing is drawn for such a frame."""
+        if self.overlay_table is None:
+            raise ValueError("overlay surfaces are the destinations of a step built with overlay=dict(target='surfaces')")
+        self._unbind_table(self.overlay_table, self._overlay_refs, indices, "unbind_overlay_surfaces")
 
     def advance(self):
         """boxes <- next_boxes (and rot <- next_rot with ``oriented=True``), on the device (``track=True``): the next call crops where
@@ -317,7 +369,11 @@ class InferStep(_FrameStep):
             warm = torch.cuda.Stream()
             warm.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(warm):
-                self._enqueue()
+                self._warming = True
+                try:
+                    self._enqueue()
+                finally:
+                    self._warming = False
             torch.cuda.current_stream().wait_stream(warm)
             torch.cuda.synchronize()
             if self.smooth:
@@ -454,10 +510,28 @@ class ManagedInferStep(InferStep):
     ``beta`` serves near and far hands.  With ``min_score=-3.0e38, by_size=False`` it is lh_one_euro bit for bit.
     topdown.one_euro_gated_host states the rule.  The defaults of both (10 Hz / 1.0 / 0.5 / 0; ``track_min_score`` / True) are design
     choices, not measured.
+    Skeleton overlay, opt-in on top of ``frames=`` and with or without ``track`` / ``manage_tracks`` / ``motion`` / ``smooth`` (None: the
+    launches above, nothing else, nothing allocated): ``overlay=True`` or a dict makes lh_draw_hands the LAST launch of the graph,
+    behind the filter: every slot's ROI outline (the crop's quad through ``plan.crop_mat``, so oriented and mirrored ROIs come out
+    turned; a lost slot draws it alone, in the palette's last row), bones and joint discs are drawn into the frames in place, on the
+    pixels around each hand only -- no pass over whole frames, no copy to the host.  The dict: ``min_score`` (default
+    ``track_min_score``) gates joints and bones, ``line_radius`` (1.0) / ``joint_radius`` (2.5) in frame pixels plus ``by_size`` (0.0)
+    times the larger side of the slot's box, ``opacity`` (1.0), ``draw_roi`` (True), ``source`` "raw" (``preds``) or "smooth"
+    (``smooth_preds``; needs ``smooth=``), ``parents`` / ``groups`` (int [j]; default: the 21-joint hand tree, topdown.HAND_PARENTS /
+    HAND_GROUPS) and ``palette`` (fp32 [n_groups + 2][3] in the frames' own plane space, topdown.overlay_palette converts RGB rows;
+    the last two rows colour the outline of a live and of a lost slot).  ``target`` "inplace" draws on what the crop read
+    (``step.frames``, or the bound surfaces under ``surfaces=True``); "surfaces" draws on a second table, ``bind_overlay_surfaces(tensors,
+    start=0)`` / ``unbind_overlay_surfaces()``, for callers whose source frames must stay clean (a decoder's reference frames): the
+    kernel never reads the source, so the caller decides what a destination holds beforehand, and an unbound destination is skipped.
+    In-place drawing changes what a later replay crops if the caller does not bring new frames; a surface may be reused only after
+    the step's stream has passed the replay; chroma siting is ignored (a chroma texel takes the mean coverage of its 2 x 2 luma
+    block).  The eager run in front of the capture draws nothing, so the first call draws once.  ``step.overlay`` keeps the resolved
+    options (None when off); topdown.draw_hands_host states the rule.
     The keywords live on this class, so InferStep's own signatures stay as they are."""
 
-    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, **kwargs):
+    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, overlay=None, **kwargs):
         self._manage_tracks_option, self._motion_option, self._smooth_gate_option = manage_tracks, motion, smooth_gate
+        self._overlay_option = overlay
         super().__init__(*args, **kwargs)
 
     def __call__(self, *args, detections=None, **kwargs):
@@ -475,12 +549,13 @@ class ManagedInferPipeline(InferPipeline):
     every slot.  Every slot owns its detection list and its ``lost_count``; ``submit(detections=...)`` fills the list of the slot that
     runs the ticket (``steps[i].dup_of`` / ``seeded`` / ``det_state`` / ``reset_tracks()``).  ``motion`` / ``smooth_gate``: as
     ManagedInferStep's, for every slot; every slot owns its motion state and its filter state (``steps[i].velocity`` / ``coasted`` /
-    ``reset_motion()``)."""
+    ``reset_motion()``).  ``overlay``: as ManagedInferStep's, for every slot; every slot draws on its own frames (or its own
+    overlay table: ``steps[i].bind_overlay_surfaces``)."""
 
     _step_class = ManagedInferStep
 
-    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, **kwargs):
-        self._step_extra = dict(manage_tracks=manage_tracks, motion=motion, smooth_gate=smooth_gate)
+    def __init__(self, *args, manage_tracks=True, motion=None, smooth_gate=None, overlay=None, **kwargs):
+        self._step_extra = dict(manage_tracks=manage_tracks, motion=motion, smooth_gate=smooth_gate, overlay=overlay)
         self._detections = None
         super().__init__(*args, **kwargs)
 

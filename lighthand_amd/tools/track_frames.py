@@ -37,9 +37,13 @@ duplicates and expired after ``--max_lost`` lost frames in a row (default 0: nev
 the line then also gives the mean speed of the found slots in frame px / s and the number of coasted slots.  ``--smooth_gate``, on top of
 ``--one_euro``, gates the filter per joint at ``--gate_min_score`` (default: the tracking threshold) and measures speed in hand sizes
 unless ``--no_size_norm`` (ManagedInferStep(smooth_gate=dict(min_score=S, by_size=...))).
+``--overlay_out DIR`` draws the tracked hands into the frames on the device (runtime.ManagedInferStep(overlay=...): ROI outline, bones,
+joint discs; ``--overlay_smooth`` draws the filtered keypoints) and writes every ``--overlay_every``-th annotated frame after its replay:
+packed RGB as binary PPM, a 4:2:0 frame as its raw surface bytes beside a one-line sidecar with format, size and pitches.
 With none of these the sequence and the line are what they were; the new keys appear only with the new options."""
 import argparse
 import json
+import os
 import time
 
 from lighthand_amd.tools.synthetic_frames import frame_size_arg as _frame_size, synthetic_sequence  # noqa: F401  (the renderer is shared with tools.train)
@@ -77,7 +81,30 @@ def build_parser():
     ap.add_argument("--smooth_gate", action="store_true", help="with --one_euro: gate the filter per joint by confidence")
     ap.add_argument("--gate_min_score", default=None, type=float, metavar="S", help="with --smooth_gate: the gate (default: the tracking threshold)")
     ap.add_argument("--no_size_norm", action="store_true", help="with --smooth_gate: keep the filter's speed in frame pixels per second")
+    ap.add_argument("--overlay_out", default=None, metavar="DIR", help="draw the tracked hands into the frames on the device and write them here")
+    ap.add_argument("--overlay_every", default=1, type=int, metavar="N", help="with --overlay_out: write every N-th frame")
+    ap.add_argument("--overlay_smooth", action="store_true", help="with --overlay_out and --one_euro: draw the filtered keypoints")
     return ap
+
+
+def write_overlay_frame(directory, t, frame, frame_format, hs, ws, layout=None):
+    """One annotated frame (a uint8 device tensor) -> its file's name: packed RGB as a binary PPM (``frame_%05d.ppm``); a 4:2:0 frame as
+    its raw surface bytes (``frame_%05d.<format>``) beside a one-line sidecar (``.txt``) with format, size and pitches.  The copy to the
+    host is this tool's, after the replay: the step itself never moves a frame."""
+    data = frame.cpu().numpy().reshape(-1)
+    if frame_format == "rgb":
+        name = os.path.join(directory, f"frame_{t:05d}.ppm")
+        with open(name, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (ws, hs))
+            f.write(data[:hs * ws * 3].tobytes())
+        return name
+    name = os.path.join(directory, f"frame_{t:05d}.{frame_format}")
+    with open(name, "wb") as f:
+        f.write(data.tobytes())
+    with open(name + ".txt", "w") as f:
+        pitch = f" pitch={layout.pitch} c_pitch={layout.c_pitch} cb_offset={layout.cb_offset} cr_offset={layout.cr_offset}" if layout is not None else f" pitch={ws}"
+        f.write(f"format={frame_format} width={ws} height={hs}{pitch} bytes={data.size}\n")
+    return name
 
 
 def main(argv=None):
@@ -104,6 +131,10 @@ def main(argv=None):
         ap.error("--smooth_gate needs --one_euro")
     if not args.smooth_gate and (args.gate_min_score is not None or args.no_size_norm):
         ap.error("--gate_min_score / --no_size_norm need --smooth_gate")
+    if args.overlay_out is None and (args.overlay_every != 1 or args.overlay_smooth):
+        ap.error("--overlay_every / --overlay_smooth need --overlay_out")
+    if args.overlay_every < 1 or (args.overlay_smooth and not args.one_euro):
+        ap.error("--overlay_every N >= 1; --overlay_smooth needs --one_euro")
     hs, ws = args.frame_size
     if args.detect_every:
         import numpy as np
@@ -156,19 +187,25 @@ def main(argv=None):
         options["smooth"] = tuple(args.one_euro)
     if args.detect_every:
         options["manage_tracks"] = dict(max_lost=args.max_lost)
-    managed = bool(args.detect_every or args.motion or args.smooth_gate)
+    managed = bool(args.detect_every or args.motion or args.smooth_gate or args.overlay_out)
     if managed and not args.detect_every:
         options["manage_tracks"] = False
     if args.motion:
         options["motion"] = dict(cutoff=args.motion_cutoff, lead=args.motion_lead, coast=args.coast)
     if args.smooth_gate:
         options["smooth_gate"] = dict(min_score=score if args.gate_min_score is None else args.gate_min_score, by_size=not args.no_size_norm)
+    if args.overlay_out:                                           # the ROI outline is on: a follower's lag is visible
+        options["overlay"] = dict(source="smooth" if args.overlay_smooth else "raw")
+        os.makedirs(args.overlay_out, exist_ok=True)
+        written = []
     step = (ManagedInferStep if managed else InferStep)(model, args.hands, args.size, args.size, track=True, track_min_score=score, **options)
     step.boxes.copy_(torch.from_numpy(boxes))
     lost = torch.zeros(args.hands, dtype=torch.int64, device=step.lost.device)
     moved = torch.zeros((), dtype=torch.float64, device=step.lost.device)
     step(mirror=mirror, **feed(0))                                 # capture; the loop below starts from the first frame's boxes again
     step.boxes.copy_(torch.from_numpy(boxes))
+    if args.overlay_out and args.surfaces:
+        surfaces[0].copy_(seq[0].reshape(-1))                      # the capture call drew on it in place
     if args.oriented:
         step.rot.copy_(torch.tensor([1.0, 0.0]).expand(args.hands, 2))
     if args.one_euro:
@@ -194,6 +231,9 @@ def main(argv=None):
         else:
             step(**feed(t))
         lost += step.lost
+        if args.overlay_out and t % args.overlay_every == 0:
+            written.append(write_overlay_frame(args.overlay_out, t, surfaces[t] if args.surfaces else step.frames[0], args.frame_format, hs, ws,
+                                               step.plan.frame_layout))
         if args.motion:
             found = step.lost == 0
             speed += torch.stack([(step.velocity.norm(dim=-1) * found).sum().double(), found.sum().double()])
@@ -230,6 +270,8 @@ def main(argv=None):
                       mean_speed_px_s=float(speed[0] / speed[1].clamp(min=1)), slots_coasted=int(coasted))
     if args.smooth_gate:
         result["smooth_gate"] = step.smooth_gate
+    if args.overlay_out:
+        result.update(overlay_out=args.overlay_out, overlay_files=written, overlay_smooth=args.overlay_smooth)
     print(json.dumps(result))
     return result
 

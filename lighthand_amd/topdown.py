@@ -35,12 +35,20 @@ another texel fetch (frame_formats.py: the plane descriptor ``Yuv420Layout`` and
 
 Motion-aware tracking (lh_rois_predict / lh_one_euro_gated, runtime.ManagedInferStep(motion=..., smooth_gate=...)): ``rois_predict``
 shifts the next ROIs along their low-passed velocity and coasts lost ones, ``one_euro_gated`` is the One-Euro filter gated per joint
-by confidence with its speed in hand sizes; ``rois_predict_host`` / ``one_euro_gated_host`` restate them in numpy, fp32 or fp64."""
+by confidence with its speed in hand sizes; ``rois_predict_host`` / ``one_euro_gated_host`` restate them in numpy, fp32 or fp64.
+
+The skeleton overlay (lh_draw_hands, runtime.ManagedInferStep(frames=..., overlay=...)): ``draw_hands`` draws the tracked hands into the
+frames in place, ``draw_hands_host`` restates it in numpy, ``overlay_palette`` converts an RGB palette into the frames' plane space;
+``HAND_PARENTS`` / ``HAND_GROUPS`` / ``OVERLAY_DEFAULTS`` hold the defaults.  All of it is overlay.py's; every public name there is
+imported here."""
 import numpy as np
 
 from .frame_formats import (FRAME_FORMATS, Yuv420Layout, check_frame_format, check_nv12_layout, check_yuv420_layout,  # noqa: F401
                             chroma_siting_code, csc12, frame_layout_of, frames_layout_struct, nv12_layout, rgb_to_nv12_host,
                             rgb_to_yuv420_host, surface_bytes, yuv420_layout, yuv_matrix)
+
+from .overlay import (HAND_GROUPS, HAND_PALETTE_RGB, HAND_PARENTS, OVERLAY_DEFAULTS, draw_hands, draw_hands_host,  # noqa: F401
+                      overlay_palette, overlay_tables)
 
 F = np.float32
 _frames_layout_struct = frames_layout_struct          # the name tests/test_surfaces_host.py imports

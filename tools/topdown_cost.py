@@ -19,7 +19,10 @@ oriented + track leg of the same run: ManagedInferStep(oriented + track) adds th
 list (64 boxes, two per frame, seeded) in front of every replay, three small copies and a fill.  Two legs price motion-aware tracking,
 ManagedInferStep(manage_tracks=False, ...): "oriented+track+motion" adds the lh_rois_predict launch (motion=True) and is reported against
 the oriented + track leg, "oriented+track+motion+gate" adds smooth= and smooth_gate=True on top (lh_one_euro_gated in lh_one_euro's place)
-and is reported against that and against the oriented + track + smooth leg.  Device events around `steps` replays, after a
+and is reported against that and against the oriented + track + smooth leg.  Two legs price the skeleton overlay,
+ManagedInferStep(manage_tracks=False, oriented + track + smooth, overlay=True): "oriented+track+smooth+overlay" adds the lh_draw_hands launch
+on the RGB frames and is reported against the oriented + track + smooth leg, "nv12 surf o+t+s+overlay" does the same on 32 NV12 surfaces of
+its own, drawn in place, against "nv12 surf o+t+s", the same step without the overlay.  Device events around `steps` replays, after a
 warm-up; median over the rounds.
 usage (GPU box): python tools/topdown_cost.py [steps] [rounds]"""
 import os
@@ -115,6 +118,13 @@ def main():
     forms["oriented+track+motion+gate"] = ManagedInferStep(model, batch, size, size, smooth=(1.0, 0.007), smooth_gate=True, **motion)
     for tag in ("oriented+track+motion", "oriented+track+motion+gate"):
         forms[tag](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
+    smooth = dict(frames=(n_frames, hs, ws), track=True, oriented=True, manage_tracks=False, smooth=(1.0, 0.007))
+    forms["oriented+track+smooth+overlay"] = ManagedInferStep(model, batch, size, size, overlay=True, **smooth)
+    forms["oriented+track+smooth+overlay"](frames=frames, boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
+    for tag, extra in (("nv12 surf o+t+s", {}), ("nv12 surf o+t+s+overlay", dict(overlay=True))):
+        forms[tag] = ManagedInferStep(model, batch, size, size, frame_format="nv12", surfaces=True, **smooth, **extra)
+        forms[tag](surfaces=list(nv12.clone().reshape(n_frames, -1).unbind(0)), boxes=boxes, frame_index=index, rot=rot, mirror=mirror)
+    against = {"oriented+track+smooth+overlay": "oriented+track+smooth", "nv12 surf o+t+s+overlay": "nv12 surf o+t+s", "nv12 surf o+t+s": "nv12 surfaces"}
     for tag, step in forms.items():
         timed(step, 10, feeds.get(tag))                                   # warm-up (capture happened in the first call)
     ms = {tag: [] for tag in forms}
@@ -124,6 +134,10 @@ def main():
     med = {tag: statistics.median(v) for tag, v in ms.items()}
     print(f"r50 bs{batch} {size}^2 bf16 inference, {n_frames} frames of {hs} x {ws}, {batch // n_frames} boxes each:", flush=True)
     for tag, v in ms.items():
+        if tag in against:
+            print(f"  {tag:30s} {med[tag]:7.3f} ms/step median ({med[tag] - med[against[tag]]:+.3f} vs {against[tag]}; rounds: "
+                  f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
+            continue
         if tag == "oriented+track+manage":
             print(f"  {tag:22s} {med[tag]:7.3f} ms/step median ({med[tag] - med['oriented+track']:+.3f} vs oriented+track; rounds: "
                   f"{', '.join(f'{x:.3f}' for x in v)})", flush=True)
