@@ -141,7 +141,9 @@ extern "C" int lh_igemm_multi(const lh_igemm_call* calls, int n, int dtype, void
         for (int i = 0; i < cnt; ++i) {
             if (int rc = prepare(calls[i0 + i], dtype, false, &tmp[i], &plans[i])) return rc;
             const RingCfg& c = plans[i].cfg;
-            LH_REQUIRE(plans[i].kind == LH_CONV_TILED || plans[i].kind == LH_CONV_DIRECT,
+            // (a dense-wave form is a configuration of the LDS-DMA kernel like any other: it passes here, and a call of several such
+            //  members ends where the 256-wide tiles do -- no multi-problem kernel, LH_ERR_UNSUPPORTED; a lone one runs its own kernel)
+            LH_REQUIRE(plans[i].kind == LH_CONV_TILED || plans[i].kind == LH_CONV_DENSE || plans[i].kind == LH_CONV_DIRECT,
                        "lh_igemm_multi: problem does not run on the LDS-DMA ring kernel or the direct 3x3 kernel (its cfg must name a tiled or the direct configuration)");
             if (plans[i].kind == LH_CONV_DIRECT) { ++ndirect; continue; }
             if (cfg0.bm == 0) cfg0 = c;

@@ -186,10 +186,14 @@ def _same(n, h, w, cin, taps, cout=PERSISTENT_COUT):
 # every border) for the direct one.
 EPILOGUE_CASES.update({f"pw{k}": _same(2, 13, 11, k, [(0, 0)]) for k in PW_K.values()})
 EPILOGUE_CASES.update({f"d{c}": _same(2, 21, 19, c, _T3) for c in (32, 64)})
-EPILOGUE_SHORT = ["c72", "c136", "phase"] + [f"pw{k}" for k in PW_K.values()] + ["d32", "d64"]
+# "m35" (tests/test_gpu_multi_exact.py): one tap, 40 -> 72 channels, 35 pixels -- ONE workgroup under any tile with 128 channels, a
+# single-workgroup member that sits between larger ones in a multi-problem launch
+EPILOGUE_CASES["m35"] = (1, 5, 7, 40, 5, 7, 72, 5, 7, 1, 1, 0, 0, [(0, 0)])
+EPILOGUE_SHORT = ["c72", "c136", "phase"] + [f"pw{k}" for k in PW_K.values()] + ["d32", "d64", "m35"]
 # "exact" ranges widened where the default ones leave too few accumulators that need rounding (one tap, short K): (case, precision) ->
 # (a for x and gx, a for w).  From the failures of tests/test_exact_host.py; never narrower.
-EPILOGUE_WIDER = {("pw40", "bf16"): (16, 8), ("pw40", "fp16"): (64, 16), ("pw72", "fp16"): (64, 16)}
+EPILOGUE_WIDER = {("pw40", "bf16"): (16, 8), ("pw40", "fp16"): (64, 16), ("pw72", "fp16"): (64, 16),
+                  ("m35", "bf16"): (16, 8), ("m35", "fp16"): (64, 16)}
 
 
 # Long cases: enough pixels that EVERY wave of a pointwise launch (workgroup of a direct one) walks its tile loop at least twice and some
@@ -916,3 +920,185 @@ def bneck_check(d, r):
     worst = [float(r["mag1"].max()), float(r["mag2"].max()), float(r["mag3"].max()), last]
     assert max(worst) < LIMIT, f"bottleneck: sums of magnitudes {worst} (>= 2^24 somewhere)"
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The multi-problem launches (tests/test_gpu_multi_exact.py): lh_igemm_multi and lh_wgrad_fused_multi.
+#
+# A. lh_igemm_multi.  The four-wave tiled configurations the multi-problem kernel is instantiated for, (tile channels, tile pixels, ring
+# depth, K bytes per stage): a literal copy of LH_RING_CFGS_MID + LH_RING_CFGS_SMALL (csrc/igemm_ring_cfgs.h), held against
+# lh_igemm_candidates by tests/test_exact_host.py.
+MULTI_RING_CFGS = [
+    (128, 128, 2, 64), (128, 128, 3, 64), (128, 128, 4, 64), (128, 128, 2, 128), (128, 128, 3, 128), (128, 128, 4, 128),
+    (128, 64, 2, 64), (128, 64, 4, 64), (128, 64, 2, 128), (128, 64, 3, 128), (128, 64, 4, 128),
+    (64, 128, 2, 64), (64, 128, 4, 64), (64, 128, 2, 128), (64, 128, 3, 128), (64, 128, 4, 128),
+    (64, 64, 2, 64), (64, 64, 4, 64), (64, 64, 2, 128), (64, 64, 3, 128), (64, 64, 4, 128),
+]
+# The members of a call, in caller order: the K loop (taps x K steps per tap: 1, 4, 1, 9, 9) is no descending sequence, so the library's
+# stable sort by loop length really permutes the first four -- (c72, phase, pw40, m35) -- and the fifth runs alone on the plain kernel.
+MULTI_MEMBERS = ["pw40", "phase", "m35", "c72", "c136"]
+MULTI_PAIR = ["c136", "pw40"]                      # n = 2
+MULTI_TRIPLE = ["phase", "m35", "c72"]             # n = 3: sorted to (c72, phase, m35)
+# The mixed-mode assignments: member i of MULTI_MEMBERS takes MULTI_MODES[i + r] in rotation r.  Rotations 0 and 1 are the two calls of all
+# five members, rotation 2 is spread over the n = 2 and n = 3 calls.  The order is chosen so that every window of three holds an addend mode
+# and an epilogue-vector mode: every member has an addend, an epilogue vector and (rotation 0 of pw40, and the all-"stats" call) a slab at
+# least once and lacks each of them at least once, the members of one call never agree, and "phase" -- whose placement is strided, while
+# mask bits index a dense output -- never meets "addend_mask" (its window is bias, addend, relu).
+MULTI_MODES = ["stats", "bias", "addend", "relu", "affine_relu", "addend_mask", "plain"]
+
+
+def multi_mode(member, rotation):
+    return MULTI_MODES[MULTI_MEMBERS.index(member) + rotation]
+
+
+def multi_igemm_calls():
+    """Every call the GPU test makes per configuration and precision: (name, flavour, [(member, mode)])."""
+    return [("five r0", "exact", [(m, multi_mode(m, 0)) for m in MULTI_MEMBERS]),
+            ("five r1", "exact", [(m, multi_mode(m, 1)) for m in MULTI_MEMBERS]),
+            ("five stats", "exact_small", [(m, "stats") for m in MULTI_MEMBERS]),
+            ("pair r2", "exact", [(m, multi_mode(m, 2)) for m in MULTI_PAIR]),
+            ("triple r2", "exact", [(m, multi_mode(m, 2)) for m in MULTI_TRIPLE])]
+
+
+def multi_launch_order(members, kb):
+    """The order lh_igemm_multi gives the members of one launch (<= 4): longest K loop first, ties in caller order."""
+    def steps(m):
+        return len(EPILOGUE_CASES[m][13]) * -(-EPILOGUE_CASES[m][3] * 2 // kb)
+    return sorted(range(len(members)), key=lambda i: -steps(members[i]))
+
+
+_EXPECTED = {}
+
+
+def epilogue_expected(case, precision, mode, flavour):
+    """Host-only twin of tests/test_gpu_epilogue_modes._host for the modes lh_igemm_multi takes (no gate): the values a launch must store
+    at its own pixels, [pixels of the launch][cout] float32 -- the accumulator rounded to 16 bits, the (masked) addend added in fp32, the sum
+    rounded again, then ReLU; "bias" and "affine_relu" as igemm_epilogue_consts folds them.  The GPU test holds it against _host."""
+    key = (case, precision, mode, flavour)
+    if key in _EXPECTED:
+        return _EXPECTED[key]
+    n, hi, wi, cin, ho, wo, cout, OH, OW, osh, osw, ooh, oow, taps = EPILOGUE_CASES[case]
+    dt = DTYPES[precision]
+    if (case, precision, flavour) not in _EXPECTED:
+        d = epilogue_data(case, precision, flavour)
+        check_exact_epilogue(case, d)
+        _EXPECTED[(case, precision, flavour)] = (d, tap_conv(d["x"], d["w"], taps, ho, wo).reshape(-1, cout))
+    d, acc = _EXPECTED[(case, precision, flavour)]
+    pos = ((torch.arange(n).view(n, 1, 1) * OH + torch.arange(ho).view(1, ho, 1) * osh + ooh) * OW
+           + torch.arange(wo).view(1, 1, wo) * osw + oow).reshape(-1)
+    if mode == "bias":
+        v = (acc + d["bias"]).to(dt).float()
+    elif mode == "affine_relu":
+        v = (acc * d["scale"] + (d["bias"] * d["scale"] + d["shift"])).to(dt).float().clamp_min(0.0)
+    else:
+        v = acc.to(dt).float()
+    if mode in ("addend", "addend_mask"):
+        a = d["addend"][pos]
+        if mode == "addend_mask":
+            bits = ((d["amask"].view(-1, 1) >> torch.arange(8, dtype=torch.uint8).view(1, 8)) & 1).bool().view(n * OH * OW, cout)
+            a = torch.where(bits[pos], a, torch.zeros_like(a))
+        v = (v + a).to(dt).float()
+    if mode == "relu":
+        v = v.clamp_min(0.0)
+    assert mode in MULTI_MODES
+    _EXPECTED[key] = v
+    return v
+
+
+# B. lh_wgrad_fused_multi.  Members (cin, cout, k, stride, pad, n, h, w): channel counts from {72, 136}, so that every four-wave tile
+# fits (wcfg_fits: more than half a 128-wide tile) and is ragged.
+#   W1  286 pixels: 9 stages of 32 rows or 5 of 64, the last one ragged (30 rows)       W2  35 pixels: less than one 64-row stage
+#   W3  stride 2, 5 x 4 = 20 output pixels                                              W4  strided 1x1, 3 x 7 x 9 = 189 pixels
+#   W5  60 pixels
+WGRAD_MULTI_CASES = {
+    "W1": (72, 136, 3, 1, 1, 2, 13, 11), "W2": (136, 72, 1, 1, 0, 1, 5, 7), "W3": (72, 72, 3, 2, 1, 1, 9, 7),
+    "W4": (136, 136, 1, 2, 0, 3, 13, 17), "W5": (136, 136, 3, 1, 1, 1, 6, 10),
+}
+# (tile output channels, tile input channels, pixel rows per ring stage, ring depth): a literal copy of the four-wave entries of
+# LH_WGRAD_CFGS (csrc/wgrad_cfgs.h), held against lh_wgrad_candidates by tests/test_exact_host.py
+WGRAD_MULTI_CFGS = [(bo, bi, kps, d) for bo, bi in ((128, 128), (128, 64), (64, 128), (64, 64)) for kps, d in ((32, 2), (32, 4), (64, 2), (64, 3))]
+WGRAD_BIG_CFG = (256, 256, 32, 3)                  # the eight-wave tile: not batchable, fits 136 x 136 only
+# Requested pixel splits (cfg[7], low 16 bits); the rest take one.  W1: 3 + 3 + 3 stages of 32 rows or 2 + 2 + 1 of 64; W4: 3 + 3 or 2 + 1.
+WGRAD_MULTI_SPLITS = {"W1": 3, "W4": 2}
+# What varies inside one call: W3 adds onto a gradient that holds small integers, W5 writes the ConvTranspose layout [cin][cout][k][k]
+# (so = k * k, si = cout * k * k), W2 has operand rows 8 channels longer than the run, the slack filled with a large finite integer.
+WGRAD_MULTI_ACCUMULATE, WGRAD_MULTI_TRANSPOSED, WGRAD_MULTI_SLACK = "W3", "W5", "W2"
+WGRAD_SLACK_FILL = 16384.0
+WGRAD_PREFILL = 16                                 # the accumulating member's gradient holds integers from [-16, 16]
+# Caller order per tile class: tiles with bo = 128 take the members with cout = 136, tiles with bi = 128 those with cin = 136.  Each order is
+# chosen so that the library's stable sort of a launch by stages per split (longest first) is no identity (tests/test_exact_host.py).
+WGRAD_MULTI_ORDER = {(64, 64): ["W1", "W2", "W3", "W4", "W5"], (128, 64): ["W5", "W1", "W4"], (64, 128): ["W2", "W4", "W5"], (128, 128): ["W5", "W4"]}
+
+
+def wgrad_fits(member, bo, bi):
+    cin, cout = WGRAD_MULTI_CASES[member][:2]
+    return (bo < 128 or cout == 136) and (bi < 128 or cin == 136)
+
+
+def wgrad_sizes(member):
+    """(output pixels, ho, wo) of a member."""
+    cin, cout, k, s, p, n, h, w = WGRAD_MULTI_CASES[member]
+    ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+    return n * ho * wo, ho, wo
+
+
+def wgrad_slack(member):
+    return 8 if member == WGRAD_MULTI_SLACK else 0
+
+
+def wgrad_desc(desc, member, cfg=None, splits=None):
+    """Fill an lh_igemm_desc (lighthand_amd._lib.IgemmDesc) with the forward convolution of a member, as Plan._c_conv does: taps (r - p,
+    s - p), sh = sw = stride, k_run = cin; cfg = (bo, bi, kps, depth) goes to cfg[5..7] with the member's split request.  Returns desc."""
+    cin, cout, k, s, p, n, h, w = WGRAD_MULTI_CASES[member]
+    _, ho, wo = wgrad_sizes(member)
+    desc.n, desc.hi, desc.wi, desc.in_pix_stride, desc.k_run = n, h, w, cin + wgrad_slack(member), cin
+    desc.ho, desc.wo, desc.sh, desc.sw, desc.cout = ho, wo, s, s, cout
+    desc.OH, desc.OW, desc.osh, desc.osw, desc.ooh, desc.oow, desc.out_pix_stride = ho, wo, 1, 1, 0, 0, cout
+    desc.ntaps, desc.relu = k * k, 0
+    for t in range(k * k):
+        desc.dh[t], desc.dw[t] = t // k - p, t % k - p
+    if cfg is not None:
+        bo, bi, kps, depth = cfg
+        want = WGRAD_MULTI_SPLITS.get(member, 1) if splits is None else splits
+        desc.cfg[5], desc.cfg[6], desc.cfg[7] = bo, bi, want | (kps << 16) | (depth << 24)
+    return desc
+
+
+def wgrad_plan(member, kps, splits=None):
+    """(stages, stages per split, splits) as wgrad_plan (csrc/wgrad_plan.h) resolves an explicit request."""
+    want = WGRAD_MULTI_SPLITS.get(member, 1) if splits is None else splits
+    stages = -(-wgrad_sizes(member)[0] // kps)
+    sps = -(-stages // want)
+    return stages, sps, -(-stages // sps)
+
+
+def wgrad_launch_order(members, kps):
+    """The order lh_wgrad_fused_multi gives the weight-gradient launch of <= 4 members: most stages per split first, ties in caller order."""
+    return sorted(range(len(members)), key=lambda i: -wgrad_plan(members[i], kps)[1])
+
+
+_WGRAD = {}
+
+
+def wgrad_member(member, precision):
+    """Integer x, w, dy (NCHW, float32) of a member, the fp64 weight gradient [cout][cin][k][k] and the integer prefill of the accumulating
+    member (or None): made once, never changed."""
+    key = (member, precision)
+    if key not in _WGRAD:
+        case = WGRAD_MULTI_CASES[member]
+        x, w, _, dy = conv_data(case, precision, seed=300 + int(member[1]), bias=False)
+        dw = reference(x, w, None, dy, case)["dw"]
+        pre = None
+        if member == WGRAD_MULTI_ACCUMULATE:
+            pre = ints(dw.shape, WGRAD_PREFILL, torch.Generator().manual_seed(399))
+        _WGRAD[key] = dict(x=x, w=w, dy=dy, dw=dw, pre=pre)
+    return _WGRAD[key]
+
+
+def wgrad_expected(member, precision):
+    """The fp32 tensor a member's gradient buffer must hold, in the layout the member writes."""
+    m = wgrad_member(member, precision)
+    g = m["dw"] + (m["pre"].double() if m["pre"] is not None else 0.0)
+    assert torch.equal(g.float().double(), g)
+    g = g.float()
+    return g.permute(1, 0, 2, 3).contiguous() if member == WGRAD_MULTI_TRANSPOSED else g

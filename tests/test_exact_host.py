@@ -501,3 +501,220 @@ def test_multi_tile_cases_walk_the_persistent_loops():
                 assert grid == tiles
     assert lib.lh_bottleneck_infer_grid(C.byref(_lib.BottleneckDesc(0, 17, 17, 64, 64, 256))) == 0 and lib.lh_bottleneck_infer_grid(None) == 0
     assert sorted((cin // 32 + 5) % 4 for cin in E.BNECK_CIN) == [0, 1, 2, 3]           # every phase of the four-slot ring at a tile boundary
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The multi-problem launches of tests/test_gpu_multi_exact.py: the configuration lists against the library's candidate queries, the
+# arithmetic of the members (stages, splits, launch order), their preconditions, and that no two members of a call expect the same
+# values -- a launch that pairs a member with another member's buffer cannot pass (host arithmetic: no GPU).
+_CODE = dict(bf16=1, fp16=2, fp32=0)                  # LH_BF16, LH_F16, LH_F32
+
+
+def _epilogue_desc(case, cfg=None):
+    from lighthand_amd import _lib
+    n, hi, wi, cin, ho, wo, cout, OH, OW, osh, osw, ooh, oow, taps = E.EPILOGUE_CASES[case]
+    d = _lib.IgemmDesc()
+    d.n, d.hi, d.wi, d.in_pix_stride, d.k_run = n, hi, wi, cin, cin
+    d.ho, d.wo, d.sh, d.sw, d.cout = ho, wo, 1, 1, cout
+    d.OH, d.OW, d.osh, d.osw, d.ooh, d.oow, d.out_pix_stride = OH, OW, osh, osw, ooh, oow, cout
+    d.ntaps = len(taps)
+    for t, (dh, dw) in enumerate(taps):
+        d.dh[t], d.dw[t] = dh, dw
+    for i, v in enumerate(cfg or ()):
+        d.cfg[i] = v
+    return d
+
+
+def _igemm_candidates(lib, d, code):
+    import ctypes as C
+    buf = (C.c_int * (5 * 320))()
+    nc = lib.lh_igemm_candidates(C.byref(d), code, buf, 320)
+    assert 0 < nc < 320
+    return [tuple(buf[5 * i:5 * i + 4]) for i in range(nc)]
+
+
+def _engine_merges(c):
+    """The rule of BatchGroups._merge_groups for a tiled member configuration (bm, bp, depth, kb)."""
+    from lighthand_amd.batch_groups import BatchGroups
+    return 2 <= c[2] < 10 and (c[0], c[1]) in BatchGroups._MULTI_TILES
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_multi_ring_cfgs_are_the_four_wave_candidates_and_the_engine_s_partition(precision):
+    """exact_data.MULTI_RING_CFGS against the library and the engine: lh_igemm_candidates offers the largest member every entry; every
+    candidate of any member that the engine's rule would merge is an entry (the GPU test runs every entry), every other candidate is one
+    the rule rejects; and no entry is refused for any member (cfg_safe: K = 40 is 80 bytes, above the 64 of the 128-byte stage)."""
+    import ctypes as C
+    lib = _library()
+    copy = set(E.MULTI_RING_CFGS)
+    assert len(E.MULTI_RING_CFGS) == len(copy) == 21 and all(_engine_merges(c) for c in copy)
+    cands = _igemm_candidates(lib, _epilogue_desc("c136"), _CODE[precision])
+    assert copy <= set(cands), copy - set(cands)
+    assert {c for c in cands if 2 <= c[2] < 10 and c[0] <= 128 and c[1] <= 128} == copy
+    rejected = set()
+    for case in E.MULTI_MEMBERS:
+        for c in _igemm_candidates(lib, _epilogue_desc(case), _CODE[precision]):
+            assert _engine_merges(c) == (c in copy), (case, c)
+            if not _engine_merges(c):
+                rejected.add(c)
+        for c in E.MULTI_RING_CFGS:
+            got = (C.c_int * 5)()
+            assert lib.lh_igemm_config(C.byref(_epilogue_desc(case, c)), _CODE[precision], got) == 0, (case, c, lib.lh_last_error())
+            assert tuple(got[:4]) == c
+    # what the rule rejects and the GPU test must see refused: dense-wave forms, 256-wide tiles, the pointwise kernel
+    assert {_kind(c) for c in rejected} == {"dense", "wide", "pointwise"}, rejected
+
+
+def _kind(c):
+    from lighthand_amd import _lib
+    k = _lib.conv_kind(c[2])
+    return "wide" if k == "tiled" and max(c[0], c[1]) == 256 else k
+
+
+def test_multi_igemm_members_sit_where_the_test_says():
+    """m35 is one workgroup under a 128-channel tile and the smallest member; the library's sort (longest K loop first, stable) is a real
+    permutation of the first four members and of the n = 3 call for both stage sizes; every mode is used, "phase" never with mask bits,
+    and the members of a call never share a mode (but in the all-"stats" call)."""
+    assert E.EPILOGUE_CASES["m35"][:9] == (1, 5, 7, 40, 5, 7, 72, 5, 7) and len(E.EPILOGUE_CASES["m35"][13]) == 1
+    for bm, bp, _, kb in E.MULTI_RING_CFGS:
+        tiles = {m: -(-(E.EPILOGUE_CASES[m][0] * E.EPILOGUE_CASES[m][4] * E.EPILOGUE_CASES[m][5]) // bp) * -(-E.EPILOGUE_CASES[m][6] // bm) for m in E.MULTI_MEMBERS}
+        assert tiles["m35"] == (1 if bm == 128 else 2) and all(tiles[m] > tiles["m35"] for m in E.MULTI_MEMBERS if m != "m35"), tiles
+        for members in (E.MULTI_MEMBERS[:4], E.MULTI_TRIPLE):
+            order = E.multi_launch_order(members, kb)
+            assert sorted(order) == list(range(len(members))) and order != list(range(len(members))), (members, kb, order)
+        assert E.multi_launch_order(E.MULTI_MEMBERS[:4], kb) == [3, 1, 0, 2]
+    used = set()
+    for name, flavour, call in E.multi_igemm_calls():
+        modes = [mode for _, mode in call]
+        used |= set(modes)
+        assert ("phase", "addend_mask") not in call and (len(set(modes)) == len(modes) or name == "five stats")
+    assert used == set(E.MULTI_MODES) and len(E.MULTI_MODES) == 7
+    for m in E.MULTI_MEMBERS:              # an addend and an epilogue vector at least once each, and a call without either
+        mine = {E.multi_mode(m, r) for r in range(3)}
+        assert mine & {"addend", "addend_mask"} and mine & {"bias", "affine_relu"} and len(mine) == 3, (m, mine)
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_multi_igemm_members_expect_different_values(precision):
+    """For every call of the GPU test, any two members' expected outputs differ in EVERY one of the first min(rows) rows they share (on the
+    channels they share), and in the all-"stats" call any two members' column sums differ in both rows: no swap of two members' output,
+    addend, vector or slab pointers can pass.  The rows that must be exact are: the sums of any "stats" member, and in "exact_small" the sums
+    of squares as well."""
+    dt = E.DTYPES[precision]
+    for name, flavour, call in E.multi_igemm_calls():
+        want = [E.epilogue_expected(m, precision, mode, flavour) for m, mode in call]
+        for i in range(len(call)):
+            for j in range(i + 1, len(call)):
+                r, c = min(want[i].shape[0], want[j].shape[0]), min(want[i].shape[1], want[j].shape[1])
+                assert bool((want[i][:r, :c] != want[j][:r, :c]).any(1).all()), (name, call[i], call[j])
+        sums = {}
+        for (m, mode), v in zip(call, want):
+            assert torch.equal(v.to(dt).float(), v)
+            if mode == "stats":
+                sd = v.double()
+                assert E.check_exact_rows(sd)[0] and (flavour == "exact" or E.check_exact_rows(sd * sd)[0]), (name, m)
+                sums[m] = torch.stack([sd.sum(0), (sd * sd).sum(0)])
+        for a in sums:
+            for b in sums:
+                if a < b:
+                    c = min(sums[a].shape[1], sums[b].shape[1])
+                    differ = (sums[a][:, :c] != sums[b][:, :c]).double().mean(1)
+                    assert float(differ.min()) > 0.9, (name, a, b, differ)
+
+
+def test_wgrad_multi_cfgs_are_the_four_wave_candidates():
+    """exact_data.WGRAD_MULTI_CFGS against lh_wgrad_candidates on a member both of whose channel counts fill more than half of any tile: the
+    four-wave plans offered are exactly the copy; the 256 x 256 tile is offered to (and resolves for) the members with 136 channels on both
+    sides only."""
+    import ctypes as C
+    from lighthand_amd import _lib
+    lib = _library()
+    assert len(set(E.WGRAD_MULTI_CFGS)) == 16
+    for precision in ("bf16", "fp16"):
+        seen = {}
+        for member, (cin, cout, *_rest) in E.WGRAD_MULTI_CASES.items():
+            buf = (C.c_int * (5 * 320))()
+            nc = lib.lh_wgrad_candidates(C.byref(E.wgrad_desc(_lib.IgemmDesc(), member)), cout, cin, _CODE[precision], buf, 320)
+            assert 0 < nc < 320
+            seen[member] = {(buf[5 * i], buf[5 * i + 1], (buf[5 * i + 2] >> 16) & 0xff, (buf[5 * i + 2] >> 24) & 0xff) for i in range(nc)}
+            assert {c for c in seen[member] if c[0] <= 128 and c[1] <= 128} == set(E.WGRAD_MULTI_CFGS), member
+            big = C.byref(E.wgrad_desc(_lib.IgemmDesc(), member, E.WGRAD_BIG_CFG, 1))
+            out = [C.c_int() for _ in range(4)]
+            rc = lib.lh_wgrad_tile(big, cout, cin, _CODE[precision], *[C.byref(v) for v in out])
+            assert (rc == 0) == (E.WGRAD_BIG_CFG in seen[member]) == (cin == 136 and cout == 136), (member, rc)
+        assert E.WGRAD_BIG_CFG in seen["W5"]
+    # fp32 has no LDS-DMA weight gradient: no candidates, and an explicit ring plan is refused (LH_ERR_UNSUPPORTED)
+    d = E.wgrad_desc(_lib.IgemmDesc(), "W5", E.WGRAD_MULTI_CFGS[0])
+    out = [C.c_int() for _ in range(4)]
+    assert lib.lh_wgrad_candidates(C.byref(d), 136, 136, 0, (C.c_int * 50)(), 10) == 0
+    assert lib.lh_wgrad_tile(C.byref(d), 136, 136, 0, *[C.byref(v) for v in out]) == -3 and b"is not available for this launch" in lib.lh_last_error()
+
+
+def test_wgrad_multi_stage_and_split_arithmetic():
+    """The members' pixel counts, stage counts and ragged last stages from the shapes; the plans lh_wgrad_tile resolves for every compiled
+    four-wave configuration and fitting member -- the requested tile, stage, depth and split count, unchanged --; at least two members
+    fit every configuration; and the library's order of every first launch (most stages per split first, stable) is a real permutation of
+    the caller's.  Static plans (cfg[5..7] = 0) put all five members into one tile class."""
+    import ctypes as C
+    from lighthand_amd import _lib
+    lib = _library()
+    assert {m: E.wgrad_sizes(m) for m in E.WGRAD_MULTI_CASES} == {"W1": (286, 13, 11), "W2": (35, 5, 7), "W3": (20, 5, 4), "W4": (189, 7, 9), "W5": (60, 6, 10)}
+    assert E.wgrad_plan("W1", 32) == (9, 3, 3) and E.wgrad_plan("W1", 64) == (5, 2, 3) and 286 % 32 == 286 % 64 == 30      # ragged last stage
+    assert E.wgrad_plan("W4", 32) == (6, 3, 2) and E.wgrad_plan("W4", 64) == (3, 2, 2) and 189 % 32 == 29 and 189 % 64 == 61
+    assert E.wgrad_plan("W2", 64) == (1, 1, 1) and E.wgrad_plan("W2", 32) == (2, 2, 1) and E.wgrad_plan("W3", 32) == (1, 1, 1) and E.wgrad_plan("W5", 32) == (2, 2, 1)
+    for cfg in E.WGRAD_MULTI_CFGS:
+        bo, bi, kps, depth = cfg
+        members = E.WGRAD_MULTI_ORDER[(bo, bi)]
+        assert members == [m for m in members if E.wgrad_fits(m, bo, bi)] and set(members) == {m for m in E.WGRAD_MULTI_CASES if E.wgrad_fits(m, bo, bi)}
+        assert len(members) >= 2
+        order = E.wgrad_launch_order(members[:4], kps)
+        assert sorted(order) == list(range(len(order))) and order != list(range(len(order))), (cfg, order)
+        for precision in ("bf16", "fp16"):
+            for m in members:
+                cin, cout, k = E.WGRAD_MULTI_CASES[m][:3]
+                d = E.wgrad_desc(_lib.IgemmDesc(), m, cfg)
+                out = [C.c_int() for _ in range(4)]
+                assert lib.lh_wgrad_tile(C.byref(d), cout, cin, _CODE[precision], *[C.byref(v) for v in out]) == 0, (cfg, m, lib.lh_last_error())
+                assert [v.value for v in out] == [bo, bi, E.wgrad_plan(m, kps)[2], kps * 10 + depth], (cfg, m)
+                assert out[2].value == E.WGRAD_MULTI_SPLITS.get(m, 1)                     # the request, unchanged
+                assert lib.lh_wgrad_workspace_bytes(C.byref(d), cout, cin, _CODE[precision]) == out[2].value * k * k * cout * cin * 4
+    # members the slack / layout / accumulate variations sit on run under every tile class they fit
+    assert E.WGRAD_MULTI_ACCUMULATE in E.WGRAD_MULTI_ORDER[(64, 64)] and all(E.WGRAD_MULTI_TRANSPOSED in v for v in E.WGRAD_MULTI_ORDER.values())
+    for precision in ("bf16", "fp16"):
+        plans = set()
+        for m, (cin, cout, *_r) in E.WGRAD_MULTI_CASES.items():
+            out = [C.c_int() for _ in range(4)]
+            assert lib.lh_wgrad_tile(C.byref(E.wgrad_desc(_lib.IgemmDesc(), m)), cout, cin, _CODE[precision], *[C.byref(v) for v in out]) == 0
+            plans.add((out[0].value, out[1].value, out[3].value))
+        assert plans == {(128, 128, 324)}
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16", "fp32"])
+@pytest.mark.parametrize("member", list(E.WGRAD_MULTI_CASES))
+def test_wgrad_multi_members_meet_the_preconditions(member, precision):
+    """check_exact on every member in every precision; fp32 holds the expected gradient (with the accumulating member's prefill) exactly;
+    the gradient is dense, so every pixel counts; and the slack fill is held by both 16-bit types."""
+    m = E.wgrad_member(member, precision)
+    dt = E.DTYPES[precision]
+    for k in ("x", "dy"):
+        assert torch.equal(m[k].to(dt).float(), m[k]) and torch.equal(m[k], m[k].round())
+    worst = E.check_exact(m["x"], m["w"], None, m["dy"], E.WGRAD_MULTI_CASES[member])
+    want = E.wgrad_expected(member, precision)
+    cin, cout, k = E.WGRAD_MULTI_CASES[member][:3]
+    assert want.shape == ((cin, cout, k, k) if member == E.WGRAD_MULTI_TRANSPOSED else (cout, cin, k, k)) and want.dtype == torch.float32
+    assert float((m["dw"] != 0).double().mean()) > 0.9
+    assert (m["pre"] is not None) == (member == E.WGRAD_MULTI_ACCUMULATE)
+    assert float(torch.tensor(E.WGRAD_SLACK_FILL).to(torch.bfloat16)) == float(torch.tensor(E.WGRAD_SLACK_FILL).to(torch.float16)) == E.WGRAD_SLACK_FILL
+    print(member, precision, f"largest sum of magnitudes {worst:.0f}, largest gradient element {float(m['dw'].abs().max()):.0f}")
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_wgrad_multi_members_expect_different_gradients(precision):
+    """Any two members' expected gradient tensors differ in most of the elements they share (compared flat, in the layout each is stored
+    in, over the shorter one's length): a gradient folded from another member's slab, or written to another member's tensor, cannot pass."""
+    want = {m: E.wgrad_expected(m, precision).flatten() for m in E.WGRAD_MULTI_CASES}
+    for a in want:
+        for b in want:
+            if a < b:
+                n = min(want[a].numel(), want[b].numel())
+                assert float((want[a][:n] != want[b][:n]).double().mean()) > 0.9, (a, b)

@@ -79,6 +79,7 @@ for _kc, _k in E.PW_K.items():
 for _c in (32, 64):
     CASES[f"d{_c}"] = E.EPILOGUE_CASES[f"d{_c}"] + ([f"direct {_c}"],)
     CASES[f"long_d{_c}"] = E.EPILOGUE_CASES[f"long_d{_c}"] + ([f"direct {_c}"],)
+CASES["m35"] = E.EPILOGUE_CASES["m35"] + ([],)       # a member of tests/test_gpu_multi_exact.py's calls: no form of this file runs it
 # case -> (operand slack, output slack) in channels
 SLACK = {"pw72": (8, 0), "pw136": (0, 8)}
 
